@@ -14,12 +14,17 @@ path over one batch of VisDrone-shaped synthetic uint8 images already resident i
   --model yolov5s:   stock YOLOv5s, 80 classes (BASELINE configs[0]; use --batch 2)
 
 Training shards data-parallel (weak scaling, per-rank batch fixed); inference shards by image with no collective ("replicas only").
-value = images all ranks processed / max-over-ranks time.  Rank 0 prints ONE JSON line with
+value = images all ranks processed / max-over-ranks time.  Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up and K timed
+steps and prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step, config); nothing else runs.  `--full` adds
+  settle           un-timed steps before the warm-up until the step time is steady (--settle-max);
+  infer_images_per_s_per_gpu   (--mode train) a side measurement of one model's forward + NMS rate, before the training steps;
   roofline         the dominant kernel = the fp32-MFMA implicit-GEMM conv variant with the largest total time: algorithmic FLOPs of
                    its launches / HIP-event time of those launches inside the timed region (events on the launch stream);
   roofline_dcnv3   (DCN graph) the DCNv3 operator kernels inside the step against the HBM roofline: algorithmic bytes / event time;
+  configs4         (N=1, default training shape) the BASELINE configs[4] inference pipeline, timed after the training region;
   cpu_baseline     (N=1) the CPU oracle on the host cores, bounded sample, protocol of BASELINE.md section 3;
   allreduce        (N>1) the gradient exchange on its own, after the timed region.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs).
 """
 import argparse
 import json
@@ -203,12 +208,60 @@ def pmc_traffic_op(op):
     return round(total / calls)
 
 
+DUMP_MAX_ELEMS = 1 << 21    # per array: at most 4 arrays of 8 MiB (float32) each, under the 64 MB the dump may take
+
+
+def _dump_sample(t):
+    """t itself, or above DUMP_MAX_ELEMS a fixed, seeded sample of its flattened elements (the same positions whenever t has the same size,
+    so the parameters and their EMA are sampled at the same places)."""
+    if t.numel() <= DUMP_MAX_ELEMS:
+        return t.detach()
+    flat = t.detach().reshape(-1)
+    idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy: float64 stays float64, everything else becomes float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = _dump_sample(t).cpu()
+        np.save(os.path.join(path, name + '.npy'), a.numpy() if a.dtype == torch.float64 else a.float().numpy())
+
+
+def step_outputs(mode, result, model=None, trainer=None):
+    """What a caller of the timed step receives from its last call, as named tensors.
+    train: (loss, loss_items) and the model the step updated - its parameters and their EMA, each flattened in named_parameters order.
+    infer: the detections kept per image (NMS rows, or the fused WBF boxes / scores / labels; padding rows dropped) and their count per
+    image, or the decoded predictions when --no-nms."""
+    if mode == 'train':
+        loss, items = result
+        names = [n for n, _ in model.named_parameters()]
+        ema = trainer.optimizer.ema_state_dict()
+        return {'loss': loss, 'loss_items': items, 'params': torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+                'params_ema': torch.cat([ema[n].reshape(-1) for n in names])}
+    if torch.is_tensor(result):                                   # --no-nms: decoded predictions (B, anchors, 5 + nc)
+        return {'predictions': result}
+    if isinstance(result, tuple):                                 # WBF: boxes (B,N,4), scores (B,N), labels (B,N), count (B)
+        boxes, scores, labels, cnt = result
+        n = cnt.tolist()
+        return {'boxes': torch.cat([boxes[b, :k] for b, k in enumerate(n)]), 'scores': torch.cat([scores[b, :k] for b, k in enumerate(n)]),
+                'labels': torch.cat([labels[b, :k] for b, k in enumerate(n)]), 'counts': cnt.double()}
+    return {'detections': torch.cat(result), 'counts': torch.tensor([float(d.shape[0]) for d in result], dtype=torch.float64)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)       # SURVEY 8d: >= 20 timed iterations after >= 10 warm-ups
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--settle-max', type=int, default=30, help='un-timed steps before the warm-up until the step time is steady (0: none)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the side measurements: settle phase, inference rate, per-launch roofline figures, configs[4], CPU baseline, all-reduce')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; rank 0's)")
+    ap.add_argument('--settle-max', type=int, default=None,
+                    help='un-timed steps before the warm-up until the step time is steady (0: none; default 30 with --full, else 0)')
     ap.add_argument('--batch', type=int, default=None, help='images per GPU per step (default 32: BASELINE configs[1]; 2 for yolov5s)')
     ap.add_argument('--size', type=int, default=640)
     ap.add_argument('--nc', type=int, default=None, help='classes (default 10, yolov5s 80; 3 = UAVDT, BASELINE configs[3])')
@@ -218,13 +271,17 @@ def main():
     ap.add_argument('--amp', choices=['bf16', 'bf16x3'], default=None,
                     help='opt-in reduced precision of the conv products (train.py:263 autocast): bf16 operands, or bf16x3 split; fp32 accumulate, '
                          'fp32 tensors / BN / loss / optimizer.  The default (and the headline) is exact fp32')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: without the CPU baseline')
     ap.add_argument('--no-nms', action='store_true')
     ap.add_argument('--no-wbf', action='store_true', help='--mode infer: one model, forward + NMS only (no second model, no fusion step)')
-    ap.add_argument('--no-infer', action='store_true', help='skip the side measurement of the inference rate (profiling runs)')
+    ap.add_argument('--no-infer', action='store_true', help='--full: without the side measurements of the inference rate and configs[4]')
     ap.add_argument('--mode', choices=['train', 'infer'], default='train',
                     help='train: forward(train)+loss+backward+Adam+EMA step (BASELINE configs[1]); infer: forward+NMS (configs[4])')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.settle_max is None:
+        args.settle_max = 30 if args.full else 0
     if args.no_dcn and args.model == 'somi-dcn':
         args.model = 'somi'
     if args.batch is None:
@@ -291,16 +348,16 @@ def main():
             if ensemble:
                 return ensemble_step(model, model2, imgs)
             z, _ = model(imgs)
-            return None if args.no_nms else non_max_suppression(z, 0.001, 0.6, multi_label=True)
+            return z if args.no_nms else non_max_suppression(z, 0.001, 0.6, multi_label=True)
 
     def single_step():                                          # one model: forward + decode + NMS
         with torch.no_grad():
             z, _ = model(imgs)
             return None if args.no_nms else non_max_suppression(z, 0.001, 0.6, multi_label=True)
 
-    # single-model inference throughput (eval mode) is measured beside the headline number: a few steps
+    # --full: single-model inference throughput (eval mode) is measured beside the headline number: a few steps
     infer_ips = None
-    if not (args.no_infer and args.mode == 'train'):
+    if args.full and not (args.no_infer and args.mode == 'train'):
         for _ in range(2):
             single_step()
         torch.cuda.synchronize()
@@ -325,10 +382,11 @@ def main():
     from somi_amd.dist import timed_steps, whole_job_rate
     if args.mode == 'infer':
         ops.CONV_PREC = ops.PREC[args.amp]                          # (training: TrainStep sets it around its forward + backward)
-    # settle phase, before the W warm-up steps and disclosed in the line (`settle`): un-timed steps until the step time has stopped moving (the mean of
-    # the last three within 2 % of the three before; 6 ... --settle-max steps).  One of round 4's default runs on a fresh box measured 402 ms per step
-    # where every later run on the same box measured 329: whatever ramps up on a fresh box (clocks, the host's caches) is not what a training run of
-    # thousands of steps sees.  With several ranks the decision is taken on the MAX over ranks, so every rank runs the same number of steps.
+    # settle phase (--full, or --settle-max > 0), before the W warm-up steps and disclosed in the line (`settle`): un-timed steps until the step time has
+    # stopped moving (the mean of the last three within 2 % of the three before; 6 ... --settle-max steps).  One of round 4's default runs on a fresh box
+    # measured 402 ms per step where every later run on the same box measured 329: whatever ramps up on a fresh box (clocks, the host's caches) is not
+    # what a training run of thousands of steps sees.  With several ranks the decision is taken on the MAX over ranks, so every rank runs the same number
+    # of steps.  Its step count depends on timing, so training outputs after a settle phase differ from run to run: a plain run has none.
     settle = None
     if args.settle_max > 0:
         hist = []
@@ -347,14 +405,23 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ops.PROFILE = prof = []                                     # per-launch HIP events around every conv / DCNv3 launch
-    dt = timed_steps(step, args.steps, dist=dist, sync=torch.cuda.synchronize, device=dev)   # barrier+sync both sides, MAX over ranks
-    ops.PROFILE = None
+    prof = []
+    if args.full:
+        ops.PROFILE = prof                                      # per-launch HIP events around every conv / DCNv3 launch
+    last = [None]
 
-    # the gradient exchange on its own (algorithmic and bus bandwidth against the xGMI links) - after the
+    def timed_step():
+        last[0] = step()
+    dt = timed_steps(timed_step, args.steps, dist=dist, sync=torch.cuda.synchronize, device=dev)   # barrier+sync both sides, MAX over ranks
+    ops.PROFILE = None
+    if args.dump_outputs and rank == 0:                         # before anything below runs another step
+        dump_outputs(args.dump_outputs, step_outputs(args.mode, last[0], model, trainer if args.mode == 'train' else None))
+    last[0] = None
+
+    # --full: the gradient exchange on its own (algorithmic and bus bandwidth against the xGMI links) - after the
     # timed region, collective over all ranks
     exchange = None
-    if (world > 1 or rehearsal) and args.mode == 'train' and trainer.buckets is not None:
+    if args.full and (world > 1 or rehearsal) and args.mode == 'train' and trainer.buckets is not None:
         # one more, instrumented, step: HIP events around every bucket on the side stream against the end of the backward pass on the
         # compute stream - whether the side-stream overlap works, not only that it ran
         trainer.buckets.timing = True
@@ -374,8 +441,8 @@ def main():
     # two synthetic models x (forward + NMS) + device WBF - runs 2 warm + 5 timed steps with the trained weights in eval mode, so the one line
     # the driver records covers both halves.  Inference shards by image with no collective: replicas only, so N = 1 only.
     configs4 = None
-    if (args.mode == 'train' and world == 1 and not rehearsal and not args.no_infer and args.model != 'yolov5s' and args.size == 640 and nc == 10
-            and args.amp is None):
+    if (args.full and args.mode == 'train' and world == 1 and not rehearsal and not args.no_infer and args.model != 'yolov5s' and args.size == 640
+            and nc == 10 and args.amp is None):
         torch.cuda.empty_cache()
         model.eval()
         m2 = fill_state(Model(cfg), 2).to(dev).eval()           # the second synthetic "model": same graph, other weights
@@ -395,18 +462,6 @@ def main():
         model.train()
 
     if rank == 0:
-        # dominant kernel = the conv tile variant with the largest total time; DCNv3 launches carry bytes instead of FLOPs
-        by, dcn = {}, {}
-        for name, work, e0, e1, _ in prof:
-            d = (dcn if name.startswith('dcnv3') else by).setdefault(name, [0, 0.0, 0.0])
-            d[0] += 1
-            d[1] += work
-            d[2] += e0.elapsed_time(e1) * 1e-3
-        name, (cnt, flops, secs) = max(by.items(), key=lambda kv: kv[1][2])
-        all_flops, all_secs = sum(v[1] for v in by.values()), sum(v[2] for v in by.values())
-        achieved = flops / secs / 1e12
-        # peak of the matrix instruction the products go through, in ALGORITHMIC FLOPs: bf16x3 issues 3 MFMAs per product
-        peak_tf = {None: F32_MFMA_PEAK_TFLOPS, 'bf16': BF16_MFMA_PEAK_TFLOPS, 'bf16x3': round(BF16_MFMA_PEAK_TFLOPS / 3, 1)}[args.amp]
         label = MODELS[args.model]
         step_txt = (f'{label} training step: uint8 ingest + forward (batch-stat BN) + ComputeLoss + backward + '
                     f'{"gradient all-reduce + " if world > 1 else ""}Adam + EMA' if args.mode == 'train' else
@@ -443,38 +498,57 @@ def main():
                        'batch_per_gpu': args.batch, 'imgsz': args.size, 'params': nparams, 'classes': nc,
                        'parallelism': ((f'dp{world}' + (' sync-bn' if args.sync_bn and world > 1 else '')) if args.mode == 'train'
                                        else f'replicas x{world}')},
-            'infer_images_per_s_per_gpu': None if infer_ips is None else round(infer_ips, 2),   # ONE model: forward + decode + NMS
             'latency_ms_per_image': round(dt / args.steps * 1e3 / args.batch, 4),   # device time of one step / images in it (throughput latency)
-            'roofline': {'bound': 'mfma', 'kernel': name, 'achieved': round(achieved, 2), 'peak': peak_tf,
-                         'unit': 'TFLOP/s', 'frac': round(achieved / peak_tf, 4), 'traffic': None,
-                         'launches': cnt, 'avg_launch_us': round(secs / cnt * 1e6, 2),
-                         'avg_launch_gflop': round(flops / cnt / 1e9, 3),
-                         'all_conv_tflops': round(all_flops / all_secs / 1e12, 2),
-                         'conv_share_of_step': round(all_secs / dt, 3)},
         }
-        # the committed counter passes are of the DEFAULT command (DCN graph, training, batch 32, 640): null for any other workload
-        profiled = args.model == 'somi-dcn' and args.mode == 'train' and args.batch == 32 and args.size == 640 and args.amp is None
-        out['roofline']['traffic'] = pmc_traffic(name) if profiled else None
-        if dcn:                                                  # the DCNv3 operator kernels of the step against the HBM roofline
-            kernels = {}
-            for k, (c_, b_, s_) in sorted(dcn.items()):
-                kernels[k] = {'launches': c_, 'avg_launch_us': round(s_ / c_ * 1e6, 2), 'avg_launch_MB': round(b_ / c_ / 1e6, 1),
-                              'achieved_GBps': round(b_ / s_ / 1e9, 1), 'frac': round(b_ / s_ / 1e9 / HBM_PEAK_GBPS, 4),
-                              'traffic': pmc_traffic_op(k) if profiled else None}
-            tb, ts = sum(v[1] for v in dcn.values()), sum(v[2] for v in dcn.values())
-            out['roofline_dcnv3'] = {'bound': 'hbm', 'achieved': round(tb / ts / 1e9, 1), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                                     'frac': round(tb / ts / 1e9 / HBM_PEAK_GBPS, 4), 'share_of_step': round(ts / dt, 4), 'kernels': kernels,
-                                     'note': 'algorithmic bytes 4(2C+3GK) forward / 4(4C+6GK) backward per output pixel (SURVEY 8d)'}
-        if configs4:
-            out['configs4'] = configs4
-        if exchange:
-            out['allreduce'] = exchange
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(args.model, args.mode, args.size, nc, wbf=ensemble)
+        if args.full:
+            full_report(out, args, prof, dt, infer_ips, configs4, exchange, nc, ensemble)
         sys.stdout.flush()
         os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (json.dumps(out) + '\n').encode())
     if dist:
         dist.destroy_process_group()
+
+
+def full_report(out, args, prof, dt, infer_ips, configs4, exchange, nc, ensemble):
+    """--full: the side measurements into the line - the inference rate, the roofline figures of the per-launch events of the timed region,
+    configs[4], the all-reduce report and the CPU baseline."""
+    out['infer_images_per_s_per_gpu'] = None if infer_ips is None else round(infer_ips, 2)   # ONE model: forward + decode + NMS
+    # dominant kernel = the conv tile variant with the largest total time; DCNv3 launches carry bytes instead of FLOPs
+    by, dcn = {}, {}
+    for name, work, e0, e1, _ in prof:
+        d = (dcn if name.startswith('dcnv3') else by).setdefault(name, [0, 0.0, 0.0])
+        d[0] += 1
+        d[1] += work
+        d[2] += e0.elapsed_time(e1) * 1e-3
+    name, (cnt, flops, secs) = max(by.items(), key=lambda kv: kv[1][2])
+    all_flops, all_secs = sum(v[1] for v in by.values()), sum(v[2] for v in by.values())
+    achieved = flops / secs / 1e12
+    # peak of the matrix instruction the products go through, in ALGORITHMIC FLOPs: bf16x3 issues 3 MFMAs per product
+    peak_tf = {None: F32_MFMA_PEAK_TFLOPS, 'bf16': BF16_MFMA_PEAK_TFLOPS, 'bf16x3': round(BF16_MFMA_PEAK_TFLOPS / 3, 1)}[args.amp]
+    out['roofline'] = {'bound': 'mfma', 'kernel': name, 'achieved': round(achieved, 2), 'peak': peak_tf,
+                       'unit': 'TFLOP/s', 'frac': round(achieved / peak_tf, 4), 'traffic': None,
+                       'launches': cnt, 'avg_launch_us': round(secs / cnt * 1e6, 2),
+                       'avg_launch_gflop': round(flops / cnt / 1e9, 3),
+                       'all_conv_tflops': round(all_flops / all_secs / 1e12, 2),
+                       'conv_share_of_step': round(all_secs / dt, 3)}
+    # the committed counter passes are of the DEFAULT command (DCN graph, training, batch 32, 640): null for any other workload
+    profiled = args.model == 'somi-dcn' and args.mode == 'train' and args.batch == 32 and args.size == 640 and args.amp is None
+    out['roofline']['traffic'] = pmc_traffic(name) if profiled else None
+    if dcn:                                                      # the DCNv3 operator kernels of the step against the HBM roofline
+        kernels = {}
+        for k, (c_, b_, s_) in sorted(dcn.items()):
+            kernels[k] = {'launches': c_, 'avg_launch_us': round(s_ / c_ * 1e6, 2), 'avg_launch_MB': round(b_ / c_ / 1e6, 1),
+                          'achieved_GBps': round(b_ / s_ / 1e9, 1), 'frac': round(b_ / s_ / 1e9 / HBM_PEAK_GBPS, 4),
+                          'traffic': pmc_traffic_op(k) if profiled else None}
+        tb, ts = sum(v[1] for v in dcn.values()), sum(v[2] for v in dcn.values())
+        out['roofline_dcnv3'] = {'bound': 'hbm', 'achieved': round(tb / ts / 1e9, 1), 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                                 'frac': round(tb / ts / 1e9 / HBM_PEAK_GBPS, 4), 'share_of_step': round(ts / dt, 4), 'kernels': kernels,
+                                 'note': 'algorithmic bytes 4(2C+3GK) forward / 4(4C+6GK) backward per output pixel (SURVEY 8d)'}
+    if configs4:
+        out['configs4'] = configs4
+    if exchange:
+        out['allreduce'] = exchange
+    if out['n_gpus'] == 1 and not args.no_cpu_baseline:
+        out['cpu_baseline'] = cpu_baseline(args.model, args.mode, args.size, nc, wbf=ensemble)
 
 
 _REAL_STDOUT = None

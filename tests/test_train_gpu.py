@@ -729,7 +729,7 @@ def test_rccl_call_pattern_single_rank_rehearsal():
     env = dict(os.environ, SOMI_DDP_SINGLE_RANK='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--batch', '4', '--size', '256',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--batch', '4', '--size', '256',
                         '--model', 'somi', '--no-cpu-baseline', '--no-infer'], capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -751,13 +751,46 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', '29571', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
+                        '--master-port', '29571', os.path.join(root, 'bench.py'), '--gpus', '2', '--full', '--steps', '2', '--warmup', '1', '--batch', '2',
                         '--size', '256', '--no-infer'], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['config']['parallelism'] == 'dp2' and line['scaling'] == 'weak' and line['value'] > 0
     assert line['allreduce']['ranks'] == 2 and line['allreduce']['backend'] == 'gloo' and 'cpu_baseline' not in line
     assert line['roofline_dcnv3']['bound'] == 'hbm' and set(line['roofline_dcnv3']['kernels']) == {'dcnv3_fwd_kernel', 'dcnv3_bwd_kernel'}
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the headline without the side measurements, and with
+    --dump-outputs writes the last timed step's loss, loss items, parameters and EMA as float32 .npy files under 64 MB - the same
+    numbers from two runs with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '4', '--size', '256',
+                            '--dump-outputs', str(out)], capture_output=True, text=True, timeout=420, env=env, cwd=root)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0 and line['settle'] is None
+        assert line['unit'] == 'images/s' and line['higher_is_better'] is True and line['dtype'] == 'f32' and line['metric'].startswith('images/sec train')
+        assert not {'roofline', 'roofline_dcnv3', 'configs4', 'cpu_baseline', 'allreduce', 'infer_images_per_s_per_gpu'} & set(line)
+        files = sorted(os.listdir(out))
+        assert files == ['loss.npy', 'loss_items.npy', 'params.npy', 'params_ema.npy']
+        assert sum(os.path.getsize(out / f) for f in files) <= 64e6
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def _optimizer_snapshot(opt):

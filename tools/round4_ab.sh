@@ -1,6 +1,6 @@
 # same-box A/B of the round-4 CBAM fusions (run through gpurun): step time with each one switched off
 mkdir -p gpurun_out/r4
-B="python bench.py --no-cpu-baseline --no-infer --steps 20 --warmup 6"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 20 --warmup 6"
 $B > gpurun_out/r4/ab_all.json 2> gpurun_out/r4/ab.err
 SOMI_FUSE_POOL=0 $B > gpurun_out/r4/ab_nofusepool.json 2>> gpurun_out/r4/ab.err
 SOMI_AMAX_BY_VALUE=0 $B > gpurun_out/r4/ab_noamax.json 2>> gpurun_out/r4/ab.err

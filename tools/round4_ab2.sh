@@ -1,6 +1,6 @@
 # interleaved same-box A/B, 40 timed steps each: does GPU time removed from the DCNv3 backward / the CBAM pooled pass show in the step?
 mkdir -p gpurun_out/r4
-B="python bench.py --no-cpu-baseline --no-infer --steps 40 --warmup 8"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 40 --warmup 8"
 for r in 1 2; do
   $B > gpurun_out/r4/ab2_all_$r.json 2>> gpurun_out/r4/ab2.err
   SOMI_DCN_SLAB=1 $B > gpurun_out/r4/ab2_dcnslab_$r.json 2>> gpurun_out/r4/ab2.err

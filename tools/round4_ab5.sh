@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r4
 python -m pytest tests/test_kernels_gpu.py tests/test_train_gpu.py -x -q -m gpu -k "spatial_attention_backward or step_c_inside or c2fcbam or attention or whole_model_train_step or bit_repro or isolated_at_320" > gpurun_out/r4/t_ab5.log 2>&1 || { tail -n 30 gpurun_out/r4/t_ab5.log; exit 1; }
 tail -n 2 gpurun_out/r4/t_ab5.log
-B="python bench.py --no-cpu-baseline --no-infer --steps 40 --warmup 8"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 40 --warmup 8"
 for r in 1 2; do
   $B > gpurun_out/r4/ab5_all_$r.json 2>> gpurun_out/r4/ab5.err
   SOMI_CBAM_FUSED_BN=0 $B > gpurun_out/r4/ab5_nofusedbn_$r.json 2>> gpurun_out/r4/ab5.err

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r4
 python -m pytest tests/test_train_gpu.py -x -q -m gpu -k "whole_model or bit_reproducible or train_step or packed_conv_masters or rehearsal or sync_bn or accumulation or end_to_end or two_ranks or amp_training or multi_scale" > gpurun_out/r4/t_ab6.log 2>&1 || { tail -n 30 gpurun_out/r4/t_ab6.log; exit 1; }
 tail -n 2 gpurun_out/r4/t_ab6.log
-B="python bench.py --no-cpu-baseline --no-infer --steps 40 --warmup 8"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 40 --warmup 8"
 for r in 1 2; do
   $B > gpurun_out/r4/ab6_all_$r.json 2>> gpurun_out/r4/ab6.err
   SOMI_SIDE_REDUCE=0 $B > gpurun_out/r4/ab6_noside_$r.json 2>> gpurun_out/r4/ab6.err

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r4
 python -m pytest tests/test_train_gpu.py tests/test_kernels_gpu.py -x -q -m gpu -k "sppf_seam or whole_model or bit_reproducible or full_width_well or attention_pieces" > gpurun_out/r4/t_ab9.log 2>&1 || { tail -n 30 gpurun_out/r4/t_ab9.log; exit 1; }
 tail -n 2 gpurun_out/r4/t_ab9.log
-B="python bench.py --no-cpu-baseline --no-infer --steps 40 --warmup 8"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 40 --warmup 8"
 for r in 1 2; do
   $B > gpurun_out/r4/ab9_all_$r.json 2>> gpurun_out/r4/ab9.err
   SOMI_FUSE_POOL=0 $B > gpurun_out/r4/ab9_nofusepool_$r.json 2>> gpurun_out/r4/ab9.err

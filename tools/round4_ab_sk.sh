@@ -1,7 +1,7 @@
 # hybrid stream-K: parity of the conv family, then interleaved same-box step times (40 steps) for the pure and hybrid schedules
 mkdir -p gpurun_out/r4
 timeout -k 10 400 python -m pytest tests/test_kernels_gpu.py tests/test_train_gpu.py -q -m gpu -x -k "conv or whole_model or bit_reproducible or stream or amp" > gpurun_out/r4/t_sk.log 2>&1; tail -3 gpurun_out/r4/t_sk.log
-B="python bench.py --no-cpu-baseline --no-infer --steps 40 --warmup 8"
+B="python bench.py --full --no-cpu-baseline --no-infer --steps 40 --warmup 8"
 for r in 1 2; do
   SOMI_SK_HYBRID=0 $B > gpurun_out/r4/absk_pure_$r.json 2>> gpurun_out/r4/absk.err
   $B > gpurun_out/r4/absk_hyb4_$r.json 2>> gpurun_out/r4/absk.err
