@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SOMI_ABI_VERSION 14
+#define SOMI_ABI_VERSION 15
 
 #define SOMI_EINVAL   (-1) /* bad shape / stride / alignment */
 #define SOMI_ENOTIMPL (-2) /* configuration outside the SOMI path */
@@ -128,6 +128,8 @@ int somi_conv2d_wgrad_nhwc_f32(const somi_conv_desc *fwd, const float *x, int x_
 /* Name of the kernel instantiation somi_conv2d_nhwc_f32 would launch for this descriptor (for profiling: matches the
  * kernel name rocprofv3 reports), or NULL for an invalid descriptor. */
 const char *somi_conv2d_kernel_name(const somi_conv_desc *d);
+/* The same for the kernel somi_conv2d_wgrad_nhwc_f32 would launch for this forward geometry (the fp32 instantiation's name), or NULL. */
+const char *somi_conv2d_wgrad_kernel_name(const somi_conv_desc *fwd);
 
 /* ------------------------------------------------------------------------------------------
  * DCNv3 operator.  Replaces `dcnv3_forward` / `dcnv3_backward` of the reference extension
@@ -401,12 +403,9 @@ int somi_chan_sum_nhwc_f32(const float *x, int x_cs, int x_coff, long npix, int 
  * See yolo-somi_amd/csrc/train_blocks.hip for the derivation.  Per-image reductions use nchunk = somi_img_nchunk(H*W).
  */
 int somi_img_nchunk(int HW);
-/* A: dlogit[p] = (sum_c dt2*t*ca) * sa*(1-sa), amaxc[p] = argmax_c(t*ca) */
-int somi_cbam_bwd_pixel_f32(const float *dt2, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
-                            const float *sa, float *dlogit, int32_t *amaxc, int B, int HW, int C, somi_stream_t stream);
-/* A + D: as somi_cbam_bwd_pixel_f32, and amaxp[b,c] = first pixel index p with t[b,p,c] == t_max[b,c], where t_max (B,C) is the spatial maximum the
- * forward pooled from the same tensor (somi_global_pool_nhwc_f32's out_max) - the arg-max of the channel attention's max-pool without the pass
- * over t that somi_pool_argmax_nhwc_f32 takes (integer min over the matching pixels: order-independent). */
+/* A + D: dlogit[p] = (sum_c dt2*t*ca) * sa*(1-sa), amaxc[p] = argmax_c(t*ca), and amaxp[b,c] = first pixel index p with t[b,p,c] == t_max[b,c],
+ * where t_max (B,C) is the spatial maximum the forward pooled from the same tensor (somi_global_pool_nhwc_f32's out_max) - the arg-max of the
+ * channel attention's max-pool without a pass of its own over t (integer min over the matching pixels: order-independent). */
 int somi_cbam_bwd_pixel_argmax_f32(const float *dt2, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
                                    const float *sa, const float *t_max, float *dlogit, int32_t *amaxc, int32_t *amaxp, int B, int HW, int C,
                                    somi_stream_t stream);
@@ -435,9 +434,6 @@ int somi_cbam_bn_bwd_apply_f32(const float *d, int d_cs, int d_coff, const float
 int somi_cbam_bwd_chan_f32(float *dt2_inout, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
                            const float *sa, const float *dstats, const int32_t *amaxc, float *dca, float *workspace, int B, int HW,
                            int C, somi_stream_t stream);
-/* D: amaxp[b,c] = first pixel index of max_p x[b,p,c]. workspace: 2*B*nchunk*C 4-byte words */
-int somi_pool_argmax_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int HW, int C, int32_t *amaxp, void *workspace,
-                              somi_stream_t stream);
 /* E: backward of somi_attn_mlp_f32 (same modes); dW1/db1/dW2/db2 ACCUMULATED (db* may be NULL), davg / dmax overwritten.
  *    The sum over samples runs in ascending order (no atomics).  workspace: somi_attn_mlp_bwd_workspace_floats(B, C, mid) floats. */
 size_t somi_attn_mlp_bwd_workspace_floats(int B, int C, int mid);

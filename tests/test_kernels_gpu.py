@@ -110,9 +110,9 @@ def test_conv_igemm(case):
     rel_close(got, nhwc(want), what='conv')
 
 
-def test_conv_streamk_matches_tile_schedule():
+def test_conv_streamk_matches_the_workspace_less_tile_schedule(monkeypatch):
     """The stream-K schedule only changes the order in which K-tiles of a cut tile are added: same result to fp32 rounding,
-    and bit-identical from run to run (fixed combination order)."""
+    and bit-identical from run to run (fixed combination order).  Without the stream-K workspace the descriptor runs one workgroup per tile."""
     from somi_amd import ops
     from somi_amd.pack import pack_conv_weight
     g = torch.Generator().manual_seed(77)
@@ -120,14 +120,11 @@ def test_conv_streamk_matches_tile_schedule():
     x = torch.randn(5, 40, 40, 128, generator=g).to(d)
     w = pack_conv_weight(torch.randn(256, 128, 3, 3, generator=g) / 34).to(d)
     b = torch.randn(256, generator=g).to(d)
-    assert ops.STREAMK
     y1 = ops.conv2d_nhwc(x, w, b, kh=3, kw=3, pad=1, act='silu')
     y2 = ops.conv2d_nhwc(x, w, b, kh=3, kw=3, pad=1, act='silu')
-    ops.STREAMK = False
-    try:
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, '_conv_workspace', lambda d, dev: None)
         y0 = ops.conv2d_nhwc(x, w, b, kh=3, kw=3, pad=1, act='silu')
-    finally:
-        ops.STREAMK = True
     assert torch.equal(y1, y2)
     assert not torch.equal(y0, y1), 'the stream-K schedule was not taken for a shape it is meant for'
     rel_close(y1, y0, rel=1e-5, what='stream-K vs one workgroup per tile')

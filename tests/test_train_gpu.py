@@ -186,12 +186,12 @@ def test_c2fcbam_train_forward_backward(c1, c2, n, shortcut):
 
 
 @pytest.mark.parametrize('c,n,B,H,W', [(64, 2, 3, 37, 29), (256, 1, 2, 20, 20), (32, 1, 5, 45, 31)])
-def test_cbam_step_c_inside_the_batchnorm_backward_equals_the_three_pass_form(c, n, B, H, W, monkeypatch):
+def test_cbam_step_c_inside_the_batchnorm_backward_equals_the_three_pass_fallback(c, n, B, H, W, monkeypatch):
     """somi_cbam_bn_bwd_reduce_f32 / _apply_f32 (step C of the CBAM backward rebuilt in registers inside the first conv's BatchNorm + SiLU backward)
     against the form it replaces (somi_cbam_bwd_chan_f32 writing dt, then the pooled BatchNorm backward): same block, same tensors, every parameter
     gradient and the input gradient.  Ragged maps (chunks that end inside an image, arg-max pixels in the last chunk), hidden widths 32 / 128 / 16;
     both forms are separately held to the oracle by test_c2fcbam_train_forward_backward."""
-    from somi_amd import blocks as MB, ops
+    from somi_amd import blocks as MB
     g = torch.Generator().manual_seed(c + H)
     blk = MB.C2fCBAM(c, c, n, True)
     with torch.no_grad():
@@ -204,8 +204,9 @@ def test_cbam_step_c_inside_the_batchnorm_backward_equals_the_three_pass_form(c,
     x = torch.randn(B, H, W, c, generator=g).cuda()
     dy = torch.randn(B, H, W, c, generator=g).cuda()
     res = {}
+    fuse_step_c = MB.CBAMBottleneck._step_c_in_bn
     for fused in (True, False):
-        monkeypatch.setattr(ops, 'CBAM_FUSED_BN', fused)
+        monkeypatch.setattr(MB.CBAMBottleneck, '_step_c_in_bn', fuse_step_c if fused else lambda self, d, t: False)
         for p_ in blk.parameters():
             p_.grad = None
         blk(MB.Act(x.clone()))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise tools/pmc_conv_round4.sh: per conv kernel variant and launch geometry (kernel, grid, workgroup) the mean duration, the MFMA-pipe
+"""Summarise the counter passes of the removed tools/pmc_conv_round4.sh (profiles/r04_conv_pmc.txt): per conv kernel variant and launch geometry (kernel, grid, workgroup) the mean duration, the MFMA-pipe
 busy share and the sustained clock, for the isolated probes and for the launches inside the training step.
 
   mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x 256 CUs x shader cycles of the dispatch), shader cycles = GRBM_GUI_ACTIVE / 8

@@ -15,7 +15,6 @@
 // for this file (hipcc's default would fuse a*r + b*(1-r) into an fma and move a mixup result across an integer boundary).
 // Arithmetic is written with plain operators: the *_rn intrinsics inline library code that still allows contraction.
 #include "common.h"
-#include <stdlib.h>
 
 #pragma clang fp contract(off)
 
@@ -275,8 +274,7 @@ extern "C" int somi_augment_u8(const somi_aug_sample *samples, int B, int H, int
     SOMI_REQUIRE(B <= 65535, SOMI_EINVAL, "augment: at most 65535 samples per launch");
     SOMI_REQUIRE(H <= 16384 && W <= 16384, SOMI_EINVAL, "augment: output larger than 16384 px");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static const int px_env = getenv("SOMI_AUG_PX") ? atoi(getenv("SOMI_AUG_PX")) : 4;
-    if (px_env == 4 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0)
+    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0)
         hipLaunchKernelGGL(augment_kernel<4>, dim3(cdiv((long)H * W / 4, 256), B), dim3(256), 0, st, samples, H, W, fill, out);
     else
         hipLaunchKernelGGL(augment_kernel<1>, dim3(cdiv((long)H * W, 256), B), dim3(256), 0, st, samples, H, W, fill, out);

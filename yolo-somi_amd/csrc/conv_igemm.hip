@@ -30,7 +30,6 @@
 //
 // Reference being replaced: F.conv2d + BatchNorm2d(eval) + SiLU in Conv.forward (models/common.py:64-70,
 // folded as utils/torch_utils.py:202-222), ODConv2d_3rd's grouped per-sample conv (models/common.py:4602-4605).
-#include <stdlib.h>
 #include "common.h"
 
 namespace somi {
@@ -42,7 +41,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 32;                    // K-tile (floats)
-constexpr int LDS_LD = BK + 4;            // sizes the LDS array (the epilogue stages D tiles with this row stride)
 constexpr int OP_LD = BK;                 // operand image row stride in floats (128 B, chunks XOR-swizzled)
 constexpr unsigned OOB = 0xFFFFFFE0u;     // byte offset beyond every descriptor: the load returns 0
 constexpr unsigned OOB_BASE = 0xF0000000u;  // + any K offset (< 2^27) still beyond every descriptor
@@ -72,9 +70,6 @@ struct ConvArgs {
     int dgrad;    // 1: data-gradient geometry (rows = forward-input pixels, source = dy, taps walk backwards, stride parity)
     int cls;      // dgrad on the FAST path: grid.y = stride^2 parity classes, each walks only the taps that reach it
     int sk;       // stream-K: gridDim.x persistent workgroups share tiles_m*tiles_n*nkt units (FAST, no strided classes)
-    int sk_whole; // hybrid: every workgroup first takes sk_whole WHOLE tiles (tile j * gridDim.x + wg), only the tiles behind them are streamed
-    int sk_rem_g; // ... over this many workgroups (<= gridDim.x: pieces shorter than a few K-tiles are not worth a partial store)
-    int sk_grid_main;   // gridDim.x of the main kernel (the fix-up kernel needs it to find the first streamed tile)
     float *ws;    // stream-K partial accumulators: [workgroup][2][BM*BN]
     int ns;       // 0: exact fp32; 1: bf16 operands; 2: bf16x3 split (plain FAST launches of the 8-wave tiles only)
 };
@@ -87,14 +82,11 @@ struct RowMap {
     bool strided;
 };
 
-// LDS floats of a tile variant: the two operand buffers, or the epilogue's D staging if that is larger.  The staging is split into
-// 32-column slabs when the whole D tile would not fit the (padded) operand area.
+// LDS floats of a tile variant: the two operand buffers, or the epilogue's D staging if that is larger.
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 struct TileLds {
     static constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, W = WAVES_M * WAVES_N;
-    static constexpr bool SPLIT = W * WM * (WN + 4) > 2 * (BM + BN) * LDS_LD;
-    static constexpr int SW = SPLIT ? 32 : WN;
-    static constexpr int STAGE = W * WM * (SW + 4), OPS = 2 * (BM + BN) * OP_LD;
+    static constexpr int STAGE = W * WM * (WN + 4), OPS = 2 * (BM + BN) * OP_LD;
     static constexpr int FLOATS = STAGE > OPS ? STAGE : OPS;
 };
 
@@ -105,11 +97,8 @@ struct TileLds {
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[BN / WAVES_N / 32][BM / WAVES_M / 32], float *lds, const ConvArgs &a,
                                               const RowMap &rm, int m0, int n0) {
-    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32;
-    // the whole D tile staged at once when it fits the operand buffers, else one 32-column slab of every wave tile per pass
-    using TL = TileLds<BM, BN, WAVES_M, WAVES_N>;
-    constexpr int SW = TL::SW, NPASS = WN / SW, SLD = SW + 4;
-    static_assert(WAVES_M * WAVES_N * WM * SLD <= TL::FLOATS, "epilogue staging does not fit the LDS array");
+    constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32, TN = WN / 32, SLD = WN + 4;
+    static_assert(WAVES_M * WAVES_N * WM * SLD <= TileLds<BM, BN, WAVES_M, WAVES_N>::FLOATS, "epilogue staging does not fit the LDS array");
     const somi_conv_desc &d = a.d;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -117,83 +106,78 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[BN / WAVES_N / 32][B
     const int h4 = (lane >> 5) * 4;
     const float *bias = d.bias ? d.bias + (size_t)rm.bz * d.Cout : nullptr;
     const size_t row_base = (size_t)rm.bz * a.M;
-    constexpr int NQ = SW / 4;                                    // float4 per staged row
+    constexpr int NQ = WN / 4;                                    // float4 per staged row
     const int mw = m0 + wm * WM;
     const bool stats = d.stat_sum != nullptr;
 #pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-        if (pass) __syncthreads();                                // the previous slab has been swept
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+        for (int jn = 0; jn < TN; ++jn)
 #pragma unroll
-            for (int js = 0; js < SW / 32; ++js)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int jn = pass * (SW / 32) + js;
-                    const f32x4 v = {acc[jn][i][4 * g], acc[jn][i][4 * g + 1], acc[jn][i][4 * g + 2], acc[jn][i][4 * g + 3]};
-                    *reinterpret_cast<f32x4 *>(&stage[(i * 32 + (lane & 31)) * SLD + js * 32 + 8 * g + h4]) = v;
-                }
-        __syncthreads();
-        const int nw = n0 + wn * WN + pass * SW;
-        // optional BatchNorm statistics: a lane always sweeps the same column quad (64 % NQ == 0), so it keeps that quad's sums
-        f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv = st1;
-        if (stats && d.stat_pivot && nw + (lane % NQ) * 4 < d.Cout) piv = *reinterpret_cast<const f32x4 *>(d.stat_pivot + nw + (lane % NQ) * 4);
-        for (int idx = lane; idx < WM * NQ; idx += 64) {
-            const int ml = idx / NQ, n = nw + (idx % NQ) * 4, m = mw + ml;
-            if (m >= rm.Mrows || n >= d.Cout) continue;
-            f32x4 v = *reinterpret_cast<const f32x4 *>(&stage[ml * SLD + (idx % NQ) * 4]);
-            size_t row = row_base + m;
-            if (rm.strided) {
-                const int rem = m % rm.HoWo;
-                row = ((size_t)(m / rm.HoWo + rm.bz) * d.Ho + rm.h0 + (rem / rm.Wc) * rm.cstep) * d.Wo + rm.w0 + (rem % rm.Wc) * rm.cstep;
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 v = {acc[jn][i][4 * g], acc[jn][i][4 * g + 1], acc[jn][i][4 * g + 2], acc[jn][i][4 * g + 3]};
+                *reinterpret_cast<f32x4 *>(&stage[(i * 32 + (lane & 31)) * SLD + jn * 32 + 8 * g + h4]) = v;
             }
-            float *yrow = d.y + row * d.y_cs + d.y_coff;
-            const float *rrow = d.residual ? d.residual + row * d.res_cs + d.res_coff : nullptr;
-            const float *rrow2 = d.residual2 ? d.residual2 + row * d.res2_cs + d.res2_coff : nullptr;
-            if (n + 3 < d.Cout) {
-                if (bias) v += *reinterpret_cast<const f32x4 *>(bias + n);
-                if (d.act == SOMI_ACT_SILU) {
+    __syncthreads();
+    const int nw = n0 + wn * WN;
+    // optional BatchNorm statistics: a lane always sweeps the same column quad (64 % NQ == 0), so it keeps that quad's sums
+    f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv = st1;
+    if (stats && d.stat_pivot && nw + (lane % NQ) * 4 < d.Cout) piv = *reinterpret_cast<const f32x4 *>(d.stat_pivot + nw + (lane % NQ) * 4);
+    for (int idx = lane; idx < WM * NQ; idx += 64) {
+        const int ml = idx / NQ, n = nw + (idx % NQ) * 4, m = mw + ml;
+        if (m >= rm.Mrows || n >= d.Cout) continue;
+        f32x4 v = *reinterpret_cast<const f32x4 *>(&stage[ml * SLD + (idx % NQ) * 4]);
+        size_t row = row_base + m;
+        if (rm.strided) {
+            const int rem = m % rm.HoWo;
+            row = ((size_t)(m / rm.HoWo + rm.bz) * d.Ho + rm.h0 + (rem / rm.Wc) * rm.cstep) * d.Wo + rm.w0 + (rem % rm.Wc) * rm.cstep;
+        }
+        float *yrow = d.y + row * d.y_cs + d.y_coff;
+        const float *rrow = d.residual ? d.residual + row * d.res_cs + d.res_coff : nullptr;
+        const float *rrow2 = d.residual2 ? d.residual2 + row * d.res2_cs + d.res2_coff : nullptr;
+        if (n + 3 < d.Cout) {
+            if (bias) v += *reinterpret_cast<const f32x4 *>(bias + n);
+            if (d.act == SOMI_ACT_SILU) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fast_silu(v[e]);
-                } else if (d.act != SOMI_ACT_NONE) {
+                for (int e = 0; e < 4; ++e) v[e] = fast_silu(v[e]);
+            } else if (d.act != SOMI_ACT_NONE) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = apply_act_rt(v[e], d.act);
-                }
-                if (d.post_scale)
-                    v = v * *reinterpret_cast<const f32x4 *>(d.post_scale + n) + *reinterpret_cast<const f32x4 *>(d.post_shift + n);
-                if (rrow) v += *reinterpret_cast<const f32x4 *>(rrow + n);
-                if (rrow2) v += *reinterpret_cast<const f32x4 *>(rrow2 + n);
-                *reinterpret_cast<f32x4 *>(yrow + n) = v;
-                if (stats) {
-                    const f32x4 t = v - piv;
-                    st1 += t;
-                    st2 += t * t;
-                }
-            } else {
-                for (int e = 0; e < 4 && n + e < d.Cout; ++e) {          // ragged Cout tail
-                    float t = v[e] + (bias ? bias[n + e] : 0.f);
-                    t = apply_act_rt(t, d.act);
-                    if (d.post_scale) t = t * d.post_scale[n + e] + d.post_shift[n + e];
-                    if (rrow) t += rrow[n + e];
-                    if (rrow2) t += rrow2[n + e];
-                    yrow[n + e] = t;
-                }
+                for (int e = 0; e < 4; ++e) v[e] = apply_act_rt(v[e], d.act);
+            }
+            if (d.post_scale)
+                v = v * *reinterpret_cast<const f32x4 *>(d.post_scale + n) + *reinterpret_cast<const f32x4 *>(d.post_shift + n);
+            if (rrow) v += *reinterpret_cast<const f32x4 *>(rrow + n);
+            if (rrow2) v += *reinterpret_cast<const f32x4 *>(rrow2 + n);
+            *reinterpret_cast<f32x4 *>(yrow + n) = v;
+            if (stats) {
+                const f32x4 t = v - piv;
+                st1 += t;
+                st2 += t * t;
+            }
+        } else {
+            for (int e = 0; e < 4 && n + e < d.Cout; ++e) {          // ragged Cout tail
+                float t = v[e] + (bias ? bias[n + e] : 0.f);
+                t = apply_act_rt(t, d.act);
+                if (d.post_scale) t = t * d.post_scale[n + e] + d.post_shift[n + e];
+                if (rrow) t += rrow[n + e];
+                if (rrow2) t += rrow2[n + e];
+                yrow[n + e] = t;
             }
         }
-        if (stats) {                                              // fold the 64 / NQ lanes that share a column quad, then one row per (tile, wave row)
+    }
+    if (stats) {                                              // fold the 64 / NQ lanes that share a column quad, then one row per (tile, wave row)
 #pragma unroll
-            for (int off = NQ; off < 64; off <<= 1)
+        for (int off = NQ; off < 64; off <<= 1)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    st1[e] += __shfl_xor(st1[e], off);
-                    st2[e] += __shfl_xor(st2[e], off);
-                }
-            const int n = nw + lane * 4;
-            if (lane < NQ && n < d.Cout) {
-                const size_t prow = (size_t)(m0 / BM) * WAVES_M + wm;
-                *reinterpret_cast<f32x4 *>(d.stat_sum + prow * d.Cout + n) = st1;
-                *reinterpret_cast<f32x4 *>(d.stat_sumsq + prow * d.Cout + n) = st2;
+            for (int e = 0; e < 4; ++e) {
+                st1[e] += __shfl_xor(st1[e], off);
+                st2[e] += __shfl_xor(st2[e], off);
             }
+        const int n = nw + lane * 4;
+        if (lane < NQ && n < d.Cout) {
+            const size_t prow = (size_t)(m0 / BM) * WAVES_M + wm;
+            *reinterpret_cast<f32x4 *>(d.stat_sum + prow * d.Cout + n) = st1;
+            *reinterpret_cast<f32x4 *>(d.stat_sumsq + prow * d.Cout + n) = st2;
         }
     }
 }
@@ -214,12 +198,12 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned of
 // bf16 values and hi*hi + hi*lo + lo*hi accumulated in fp32 - 16 mantissa bits per operand, ~1e-5 relative error, 3 MFMAs at 16x the
 // fp32 rate.  The operands stay fp32 in HBM and are converted while they are staged into LDS ([row][32 bf16 hi | 32 bf16 lo] = the
 // fp32 image's 128-byte rows), so nothing outside this kernel changes.
-// Waves per SIMD the register budget is set for: 4 (two 8-wave workgroups per CU), 2 for the big experiment tile, and 6 for the 8-wave
+// Waves per SIMD the register budget is set for: 2 (two 4-wave workgroups per CU), 4 (two 8-wave workgroups per CU), and 6 for the 8-wave
 // 128 x 64 tile's plain fp32 form - its 48 KB of LDS let THREE workgroups share a CU, which the 64-channel layers (K = 576: 18 K-tiles
 // between a prologue and an epilogue) use to hide those phases behind two neighbours instead of one.
 template <int BM, int BN, int WAVES, bool MODULATE, bool FAST, int NS>
 constexpr int conv_waves_per_simd() {
-    return BM + BN > 320 ? 2 : (WAVES == 8 && BM + BN <= 192 && !MODULATE && FAST && NS == 0 ? 6 : WAVES / 2);
+    return WAVES == 8 && BM + BN <= 192 && !MODULATE && FAST && NS == 0 ? 6 : WAVES / 2;
 }
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool MODULATE, bool FAST, int NS = 0>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN, WAVES_M * WAVES_N, MODULATE, FAST, NS>())) void conv_igemm_f32_kernel(const ConvArgs a) {
@@ -267,15 +251,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
     const int ntile = a.tiles_m * a.tiles_n;
     const bool sk = FAST && a.sk;
     const int wg = sk ? xcd_remap(blockIdx.x, gridDim.x) : 0;
-    // hybrid stream-K (round 4, an experiment switch: sk_whole = 0 by default): whole rounds of tiles run like the plain schedule - tile
-    // j * G + wg, no cut, no partial store - and only the tiles behind them (fewer than G) are streamed, over sk_rem_g workgroups.  The partials
-    // and the fix-up shrink from one seam per workgroup (64 MiB written + read, 19.4 us x 193 launches per step) to the seams of the last partial
-    // round - and the step does not get faster (launch<>).
-    const int sk_whole = sk ? a.sk_whole : 0, tile_base = sk ? sk_whole * (int)gridDim.x : 0, Gr = sk ? a.sk_rem_g : 1;
-    const long U = (long)(ntile - tile_base) * nkt;                  // streamed units
-    long u = sk ? sk_lo(min(wg, Gr), U, Gr) : (long)xcd_remap(blockIdx.x, ntile) * (nkt > 0 ? nkt : 1);
-    const long u_lo = u, u_hi = sk ? sk_lo(min(wg + 1, Gr), U, Gr) : u + (nkt > 0 ? nkt : 1);
-    int whole_left = sk_whole;
+    const long U = (long)ntile * nkt;
+    long u = sk ? sk_lo(wg, U, gridDim.x) : (long)xcd_remap(blockIdx.x, ntile) * (nkt > 0 ? nkt : 1);
+    const long u_lo = u, u_hi = sk ? sk_lo(wg + 1, U, gridDim.x) : u + (nkt > 0 ? nkt : 1);
 
     // A thread owns LDS chunk slot (tid & 7) of rows row0 + RPP*i; the slot holds k-chunk slot ^ ((row >> 1) & 7), and (row >> 1) & 7 is
     // the same for all of a thread's rows (RPP, BM are multiples of 16), so the swizzle is one XOR on the thread's fetch column.
@@ -296,20 +274,11 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
 #pragma unroll
     for (int j = 0; j < 4; ++j) fo[j] = ((2 * j + (lane >> 5)) ^ ((lane >> 1) & 7)) << 2;
 
-    while (whole_left > 0 || u < u_hi) {
-        int tile, kt0, kt1;
-        const bool whole = whole_left > 0;
-        if (whole) {                                                  // a whole tile of this workgroup's rounds
-            tile = (sk_whole - whole_left) * (int)gridDim.x + wg;
-            kt0 = 0;
-            kt1 = nkt;
-            --whole_left;
-        } else {
-            tile = tile_base + (int)(u / (nkt > 0 ? nkt : 1));
-            kt0 = nkt > 0 ? (int)(u % nkt) : 0;
-            kt1 = sk ? (int)min((long)nkt, kt0 + (u_hi - u)) : nkt;
-            u += sk ? kt1 - kt0 : (nkt > 0 ? nkt : 1);
-        }
+    while (u < u_hi) {
+        const int tile = (int)(u / (nkt > 0 ? nkt : 1));
+        const int kt0 = nkt > 0 ? (int)(u % nkt) : 0;
+        const int kt1 = sk ? (int)min((long)nkt, kt0 + (u_hi - u)) : nkt;
+        u += sk ? kt1 - kt0 : (nkt > 0 ? nkt : 1);
         const int tile_m = tile / a.tiles_n, tile_n = tile % a.tiles_n;   // n fastest: neighbours share the activation rows
         const int m0 = tile_m * BM, n0 = tile_n * BN;
         if (m0 >= Mrows) return;                                          // smaller class than the grid was sized for (never stream-K)
@@ -594,7 +563,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         } else {
             // a cut tile: raw accumulators to this workgroup's slot (0: the run starts with this piece, 1: it ends with it),
             // one coalesced float per lane per register
-            const bool first_piece = (long)(tile - tile_base) * nkt + kt0 == u_lo;
+            const bool first_piece = (long)tile * nkt + kt0 == u_lo;
             float *slot = a.ws + ((size_t)wg * 2 + (first_piece ? 0 : 1)) * (BM * BN);
 #pragma unroll
             for (int jn = 0; jn < TN; ++jn)
@@ -610,16 +579,15 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
 // Stream-K fix-up: workgroup j looks at the boundary between the runs of workgroups j and j+1; if it cuts a tile and is the
 // first cut inside that tile, it adds the tile's pieces in ascending workgroup order and runs the epilogue.
 template <int BM, int BN, int WAVES_M, int WAVES_N>
-__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (BM + BN > 320 ? 2 : WAVES_M * WAVES_N / 2)) void conv_streamk_fixup_kernel(const ConvArgs a, int G) {
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WAVES_M * WAVES_N / 2) void conv_streamk_fixup_kernel(const ConvArgs a, int G) {
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32, TN = WN / 32, NT = WAVES_M * WAVES_N * 64;
     __shared__ __attribute__((aligned(16))) float lds[TileLds<BM, BN, WAVES_M, WAVES_N>::FLOATS];
     const int nkt = a.K / BK, ntile = a.tiles_m * a.tiles_n;
-    const int tile_base = a.sk_whole * a.sk_grid_main;               // the streamed tiles sit behind the whole rounds; G = sk_rem_g
-    const long U = (long)(ntile - tile_base) * nkt;
+    const long U = (long)ntile * nkt;                                  // G: the main kernel's grid
     const int g = blockIdx.x + 1;
     const long b = sk_lo(g, U, G);
     if (b % nkt == 0) return;                                         // the boundary coincides with a tile boundary
-    const int tile = (int)(b / nkt);                                  // index among the streamed tiles
+    const int tile = (int)(b / nkt);
     const long t_lo = (long)tile * nkt, t_hi = t_lo + nkt;
     if (sk_lo(g - 1, U, G) > t_lo) return;                            // an earlier boundary inside this tile does the work
     const int tid = threadIdx.x;
@@ -670,28 +638,22 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (BM + BN > 320 ? 2 : WAVES_
         if (!s1) break;
     }
     const RowMap rmap = {a.M, a.d.Ho * a.d.Wo, a.d.Wo, 1, 0, 0, 0, false};
-    const int gt = tile_base + tile;
-    conv_epilogue<BM, BN, WAVES_M, WAVES_N>(acc, lds, a, rmap, (gt / a.tiles_n) * BM, (gt % a.tiles_n) * BN);
+    conv_epilogue<BM, BN, WAVES_M, WAVES_N>(acc, lds, a, rmap, (tile / a.tiles_n) * BM, (tile % a.tiles_n) * BN);
 }
 
 struct TilePlan {
-    int variant;   // 0: 128x128, 1: 64x128, 2: 128x64, 3: 128x32, 4: 128x128 with 8 waves (2 per SIMD and workgroup), 5: 128x64 8 waves,
-                   // 6: 256x128 (experiment), 7: 256x64 with 8 waves of 32x64 (64-channel layers on large maps)
+    int variant;   // 0: 128x128 (8 waves, 2 per SIMD and workgroup), 1: 64x128, 2: 128x64 (8 waves), 3: 128x32
     bool sk;       // stream-K schedule
 };
-static const int kTileBM[8] = {128, 64, 128, 128, 128, 128, 256, 256}, kTileBN[8] = {128, 128, 64, 32, 128, 64, 128, 64};
-// resident workgroups chip-wide: two per CU; one for the big tile; three for the plain fp32 form of the 8-wave 128 x 64 tile
-static inline bool three_per_cu(int variant, const somi_conv_desc &d) {
-    static const bool on = [] { const char *e = getenv("SOMI_CONV_3WG"); return !(e && e[0] == '0'); }();
-    return on && variant == 5 && !d.a_chan_scale && !d.a_pix_scale && d.prec != 1 && d.prec != 2;
-}
-static bool fast_path(const somi_conv_desc &d);
-static inline int sk_slots(int variant, const somi_conv_desc &d) {
-    return variant == 6 ? SK_GRID / 2 : (three_per_cu(variant, d) && fast_path(d) ? SK_GRID * 3 / 2 : SK_GRID);
-}
+static const int kTileBM[4] = {128, 64, 128, 128}, kTileBN[4] = {128, 128, 64, 32};
 
 static bool fast_path(const somi_conv_desc &d) {
     return d.Cin % BK == 0 && d.kh * d.kw <= 32 && (size_t)d.kh * d.kw * d.Cin * 4 < (1u << 27);
+}
+// resident workgroups chip-wide (stream-K slots): two per CU; three for the plain fp32 form of the 8-wave 128 x 64 tile
+static inline int sk_slots(int variant, const somi_conv_desc &d) {
+    const bool three = variant == 2 && !d.a_chan_scale && !d.a_pix_scale && d.prec != 1 && d.prec != 2 && fast_path(d);
+    return three ? SK_GRID * 3 / 2 : SK_GRID;
 }
 
 // Tile variant and schedule.  Widest N tile that Cout fills reasonably.  With a workspace the 128-row tile is kept for small
@@ -708,37 +670,21 @@ static TilePlan plan_tiles(const somi_conv_desc &d, int M, int dgrad) {
     } else {
         p.variant = d.Cout > 32 ? 2 : 3;
     }
-    static const int eight = getenv("SOMI_CONV_8WAVE") ? atoi(getenv("SOMI_CONV_8WAVE")) : 2;
-    if (eight && p.variant == 0) p.variant = 4;
-    if (eight > 1 && p.variant == 2) p.variant = 5;
-    // 64 output channels on a large map: a 256 x 64 tile of 8 waves x (32 x 64) issues as many MFMAs per barrier as the 128 x 128 form
-    // (the 128 x 64 tile half of them) at 1.25x its operand bytes per FLOP; 80 KB of LDS, two per CU.  Measured round 3: no gain - the
-    // 64 -> 64 3x3 layers at 160x160 ran 98-100 TFLOP/s with it against 101-103 with the 128 x 64 tile, so MFMAs per barrier are not what
-    // holds those layers at 100 (their K = 576 is 18 K-tiles: prologue + epilogue weigh twice what they do at K = 1152).  Off by default.
-    static const int tall = getenv("SOMI_CONV_TALL64") ? atoi(getenv("SOMI_CONV_TALL64")) : 0;
-    if (tall && p.variant == 5 && d.Cout > 32 && fast_path(d) && !d.a_chan_scale && !d.a_pix_scale && M >= 256 * 512) p.variant = 7;
-    // 256 x 128 tile, 8 waves of 64 x 64 (a third fewer LDS operand bytes per MFMA than the 64 x 32 wave tile).  Measured (round 2):
-    // SLOWER - 109.7 vs 118.8 TFLOP/s on 128->128 3x3 at 160x160, 109 vs 114 at 80x80.  The premise was wrong: a 32x32x2 fp32 MFMA
-    // occupies the pipe for 64 cycles, so the 128 x 128 form's operand reads + tile writes are ~31 B/clk per CU, a quarter of the LDS
-    // port - LDS bandwidth is not what holds the kernel at 72-78 % MFMA busy; and the big tile's 110 KB of LDS leave one workgroup per CU
-    // (two waves per SIMD instead of four), which costs latency hiding.  Kept behind SOMI_CONV_BIG=1 for experiments.
-    static const int big = getenv("SOMI_CONV_BIG") ? atoi(getenv("SOMI_CONV_BIG")) : 0;
-    if (big && p.variant == 4 && fast_path(d) && !d.per_sample_w && !d.a_chan_scale && !d.a_pix_scale && M >= 256 * 256) p.variant = 6;
     if (sk_ok) {
         const int bm = kTileBM[p.variant], bn = kTileBN[p.variant];
         const long ntile = (long)cdiv(M, bm) * cdiv(d.Cout, bn), nkt = (long)d.kh * d.kw * d.Cin / BK;
         const int slots = sk_slots(p.variant, d);
         const long rounds = (ntile + slots - 1) / slots;
-        static const int sk_pct = getenv("SOMI_SK_PCT") ? atoi(getenv("SOMI_SK_PCT")) : 90;   // stream-K below this slot efficiency (%)
-        p.sk = ntile * 100 < rounds * slots * sk_pct && ntile * nkt >= 32 &&       // (the grid shrinks to >= 8 K-tiles per workgroup)
-               d.workspace_bytes >= (size_t)slots * 2 * bm * bn * sizeof(float);
+        p.sk = ntile * 100 < rounds * slots * 90 && ntile * nkt >= 32 &&       // stream-K below 90 % slot efficiency
+               d.workspace_bytes >= (size_t)slots * 2 * bm * bn * sizeof(float);   // (the grid shrinks to >= 8 K-tiles per workgroup)
     }
     return p;
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch(const ConvArgs &a, bool sk, hipStream_t s) {
+static int launch(const ConvArgs &a, const TilePlan &tp, hipStream_t s) {
     ConvArgs args = a;
+    const bool sk = tp.sk;
     const bool mod = a.d.a_chan_scale || a.d.a_pix_scale;
     const bool fast = fast_path(a.d);
     args.cls = a.dgrad && fast;
@@ -748,41 +694,26 @@ static int launch(const ConvArgs &a, bool sk, hipStream_t s) {
     const int m_cls = args.cls ? (a.d.per_sample_w ? 1 : a.d.B) * cdiv(a.d.Ho, st) * cdiv(a.d.Wo, st) : a.M;   // largest class
     args.tiles_m = cdiv(m_cls, BM);
     args.tiles_n = cdiv(a.d.Cout, BN);
-    // stream-K grid: all 512 slots, unless that would leave a workgroup fewer than min_kt K-tiles (prologue, partial store and
-    // fix-up then cost more than the MFMA work of the piece)
-    static const int min_kt = getenv("SOMI_SK_MIN_KT") ? atoi(getenv("SOMI_SK_MIN_KT")) : 8;
-    int sk_grid = BM + BN > 320 ? SK_GRID / 2 : (WAVES_M * WAVES_N == 8 && BM + BN <= 192 && fast && three_per_cu(5, a.d) ? SK_GRID * 3 / 2 : SK_GRID);
-    int fix_grid = 0;
-    args.sk_whole = 0;
-    args.sk_rem_g = args.sk_grid_main = 1;
+    // stream-K grid: all slots, unless that would leave a workgroup fewer than 8 K-tiles (prologue, partial store and fix-up then cost
+    // more than the MFMA work of the piece)
+    int sk_grid = sk_slots(tp.variant, a.d);
     if (sk) {
-        const long ntile = (long)args.tiles_m * args.tiles_n, nkt = a.K / BK, U = ntile * nkt;
-        if (U / min_kt < sk_grid) sk_grid = (int)(U / min_kt);
+        const long U = (long)args.tiles_m * args.tiles_n * (a.K / BK);
+        if (U / 8 < sk_grid) sk_grid = (int)(U / 8);
         if (sk_grid < 2) sk_grid = 2;
-        // hybrid (SOMI_SK_HYBRID=1): whole rounds first, only the remainder streamed.  Measured round 4 (interleaved 40-step runs on one box):
-        // 330.1 - 330.8 ms per step against 329.6 - 329.9 with everything streamed - the fix-up shrinks, but the short remainder pieces and the
-        // lost balance cost as much.  Off by default.
-        static const int hybrid = getenv("SOMI_SK_HYBRID") ? atoi(getenv("SOMI_SK_HYBRID")) : 0;
-        const int whole = hybrid ? (int)(ntile / sk_grid) : 0;
-        const long u_rem = (ntile - (long)whole * sk_grid) * nkt;
-        int gr = sk_grid;
-        static const int rem_min_kt = getenv("SOMI_SK_REM_MIN_KT") ? atoi(getenv("SOMI_SK_REM_MIN_KT")) : 4;
-        if (whole > 0 && u_rem / rem_min_kt < gr) gr = (int)(u_rem / rem_min_kt);   // no streamed piece shorter than this many K-tiles
-        if (gr < 1) gr = 1;
-        args.sk_whole = whole;
-        args.sk_rem_g = gr;
-        args.sk_grid_main = sk_grid;
-        fix_grid = u_rem > 0 ? gr - 1 : 0;                              // one seam per boundary between streamed runs
     }
     const dim3 grid(sk ? sk_grid : args.tiles_m * args.tiles_n, ncls, a.d.per_sample_w ? a.d.B : 1);
-    if constexpr (WAVES_M * WAVES_N == 8 && BM + BN <= 320) {
+    // the fix-up: one workgroup per boundary between stream-K runs
+    auto fixup = [&] {
+        if (sk) hipLaunchKernelGGL((conv_streamk_fixup_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(sk_grid - 1), dim3(WAVES_M * WAVES_N * 64), 0, s, args, sk_grid);
+    };
+    if constexpr (WAVES_M * WAVES_N == 8) {
         if (a.ns && fast && !mod) {                                // reduced-precision forms (opt-in): same schedule, fix-up and epilogue
             if (a.ns == 1)
                 hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 1>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
             else
                 hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 2>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
-            if (sk && fix_grid > 0)
-                hipLaunchKernelGGL((conv_streamk_fixup_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(fix_grid), dim3(WAVES_M * WAVES_N * 64), 0, s, args, args.sk_rem_g);
+            fixup();
             return launch_status("somi_conv2d_nhwc_f32 (bf16)");
         }
     }
@@ -794,8 +725,7 @@ static int launch(const ConvArgs &a, bool sk, hipStream_t s) {
         hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
     else
         hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, false>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
-    if (sk && fix_grid > 0)
-        hipLaunchKernelGGL((conv_streamk_fixup_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(fix_grid), dim3(WAVES_M * WAVES_N * 64), 0, s, args, args.sk_rem_g);
+    fixup();
     return launch_status("somi_conv2d_nhwc_f32");
 }
 
@@ -878,14 +808,10 @@ static int conv_launch(const somi_conv_desc *dp, somi_stream_t stream, int dgrad
     hipStream_t s = static_cast<hipStream_t>(stream);
     const TilePlan tp = plan_tiles(d, a.M, dgrad);
     switch (tp.variant) {
-        case 0: return launch<128, 128, 2, 2>(a, tp.sk, s);
-        case 1: return launch<64, 128, 1, 4>(a, tp.sk, s);
-        case 2: return launch<128, 64, 2, 2>(a, tp.sk, s);
-        case 4: return launch<128, 128, 2, 4>(a, tp.sk, s);
-        case 5: return launch<128, 64, 4, 2>(a, tp.sk, s);
-        case 6: return launch<256, 128, 4, 2>(a, tp.sk, s);
-        case 7: return launch<256, 64, 8, 1>(a, tp.sk, s);
-        default: return launch<128, 32, 4, 1>(a, tp.sk, s);
+        case 0: return launch<128, 128, 2, 4>(a, tp, s);
+        case 1: return launch<64, 128, 1, 4>(a, tp, s);
+        case 2: return launch<128, 64, 4, 2>(a, tp, s);
+        default: return launch<128, 32, 4, 1>(a, tp, s);
     }
 }
 }  // namespace somi
@@ -920,7 +846,7 @@ extern "C" const char *somi_conv2d_kernel_name(const somi_conv_desc *dp) {
     const int M = dp->per_sample_w ? dp->Ho * dp->Wo : dp->B * dp->Ho * dp->Wo;
     const int mod = (dp->a_chan_scale || dp->a_pix_scale) ? 1 : 0;
     const int fast = (dp->Cin % somi::BK == 0 && dp->kh * dp->kw <= 32) ? 1 : 0;
-    static const char *tiles[8] = {"128,128,2,2", "64,128,1,4", "128,64,2,2", "128,32,4,1", "128,128,2,4", "128,64,4,2", "256,128,4,2", "256,64,8,1"};
+    static const char *tiles[4] = {"128,128,2,4", "64,128,1,4", "128,64,4,2", "128,32,4,1"};
     static thread_local char name[96];
     snprintf(name, sizeof(name), "conv_igemm_f32_kernel<%s,%s,%s>", tiles[somi::plan_tiles(*dp, M, 0).variant], mod ? "true" : "false",
              fast ? "true" : "false");
@@ -929,7 +855,7 @@ extern "C" const char *somi_conv2d_kernel_name(const somi_conv_desc *dp) {
 
 extern "C" int somi_conv2d_stat_rows(const somi_conv_desc *dp) {
     if (!dp || dp->Cout <= 0 || dp->Ho <= 0 || dp->Wo <= 0 || dp->B <= 0 || dp->per_sample_w) return 0;
-    static const int waves_m[8] = {2, 1, 2, 4, 2, 4, 4, 8};
+    static const int waves_m[4] = {2, 1, 4, 4};
     const int M = dp->B * dp->Ho * dp->Wo;
     const int v = somi::plan_tiles(*dp, M, 0).variant;
     return somi::cdiv(M, somi::kTileBM[v]) * waves_m[v];

@@ -10,7 +10,6 @@
 // conflict-free).  The image is lane-linear (thread t owns floats [4t, 4t+4) of every pass), so it is filled by LDS-DMA
 // (`buffer_load_dwordx4 ... lds`): no VGPR staging and no ds_write pass.  Partial tiles of the splits go to a workspace and are summed in a fixed order (deterministic), optionally
 // on top of an existing gradient.
-#include <stdlib.h>
 #include "common.h"
 
 namespace somi {
@@ -70,11 +69,11 @@ __device__ __forceinline__ i16x4 lds_read_tr16(const char *p) {
 // 8 waves) convert dy / x while they are staged into a [pixel][channel] bf16 image (256-byte rows, 16-byte chunks XOR-swizzled by
 // ((row & 3) << 2) | ((row >> 2) & 3)) and read their MFMA operands - 8 consecutive PIXELS of one channel per lane - with the hardware
 // transposing read.
-template <int BM, int BN, int NW = 4, int NS = 0>   // co rows x k columns per tile: 128 x {128,64,32} or 64 x {128,64}; NW waves (8: 128 x 128 only)
+template <int BM, int BN, int NW = 4, int NS = 0>   // co rows x k columns per tile: 128 x {128,64,32} or 64 x {128,64}; NW waves (8: the 128-column tiles)
 __global__ __launch_bounds__(NW * 64, NW / 2) void conv_wgrad_f32_kernel(const WgradArgs a) {
     constexpr int NT = NW * 64;
     static_assert(NS == 0 || ((BM == 128 || BM == 64) && BN == 128 && NW == 8), "the bf16 forms exist for the 128 / 64 x 128 tiles with 8 waves");
-    constexpr int WAVES_N = NW == 8 ? 4 : (BM == 64 ? 2 : (BN == 128 ? 2 : 1)), WAVES_M = NW / WAVES_N;
+    constexpr int WAVES_N = NW == 8 ? 4 : (BM == 64 ? 2 : 1), WAVES_M = NW / WAVES_N;
     static_assert(BM / WAVES_M >= 32 && BN / WAVES_N >= 32, "bad wgrad tiling");
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32, TN = WN / 32;
     constexpr int A_LD = BM, B_LD = BN;
@@ -372,8 +371,7 @@ static int plan(const somi_conv_desc &f, WgradArgs &a) {
     a.tiles_k = cdiv(a.K, a.bn);
     const long tiles = (long)a.tiles_co * a.tiles_k * (a.per_sample ? f.B : 1);
     // enough splits to fill the chip a few times over, but at least 8 K-tiles of work per split
-    static const long target = getenv("SOMI_WGRAD_WGS") ? atol(getenv("SOMI_WGRAD_WGS")) : 1024;
-    long want = target / tiles;                                          // whole rounds of the 512 workgroup slots, never a bit more
+    long want = 1024 / tiles;                                          // whole rounds of the 512 workgroup slots, never a bit more
     const long max_splits = (a.npix + WG_PIX * 8 - 1) / (WG_PIX * 8);
     if (want > max_splits) want = max_splits;
     if (want < 1) want = 1;
@@ -391,6 +389,16 @@ extern "C" size_t somi_conv2d_wgrad_workspace_bytes(const somi_conv_desc *fwd) {
     if (!fwd || plan(*fwd, a)) return 0;
     // also with a single split: accumulating on top of an existing gradient goes through the workspace + reduce pass
     return (size_t)(a.splits < 1 ? 1 : a.splits) * (a.per_sample ? a.B : 1) * a.Cout * a.K * 4 + 256;
+}
+
+// Name of the fp32 kernel plan() picks for this forward geometry (the 128-column tiles run 8 waves), as somi_conv2d_kernel_name
+// gives it: without the reduced-precision template argument.
+extern "C" const char *somi_conv2d_wgrad_kernel_name(const somi_conv_desc *fwd) {
+    WgradArgs a{};
+    if (!fwd || plan(*fwd, a)) return nullptr;
+    static thread_local char name[64];
+    snprintf(name, sizeof(name), "conv_wgrad_f32_kernel<%d,%d,%d>", a.bm, a.bn, a.bn == 128 ? 8 : 4);
+    return name;
 }
 
 extern "C" int somi_conv2d_wgrad_nhwc_f32(const somi_conv_desc *fwd, const float *x, int x_cs, int x_coff, const float *dy, int dy_cs,
@@ -427,18 +435,15 @@ extern "C" int somi_conv2d_wgrad_nhwc_f32(const somi_conv_desc *fwd, const float
     a.out = direct ? dw : static_cast<float *>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(a.tiles_co * a.tiles_k * a.splits, 1, sets);
-    static const int eight = getenv("SOMI_WGRAD_8WAVE") ? atoi(getenv("SOMI_WGRAD_8WAVE")) : 2;
     a.ns = (fwd->prec == 1 || fwd->prec == 2) && !a.per_sample && a.bn == 128 ? fwd->prec : 0;
     if (a.ns == 1 && a.bm == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 128, 8, 1>), grid, dim3(512), 0, s, a);
     else if (a.ns == 2 && a.bm == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 128, 8, 2>), grid, dim3(512), 0, s, a);
     else if (a.ns == 1) hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 128, 8, 1>), grid, dim3(512), 0, s, a);
     else if (a.ns == 2) hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 128, 8, 2>), grid, dim3(512), 0, s, a);
-    else if (a.bm == 128 && a.bn == 128 && eight) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 128, 8>), grid, dim3(512), 0, s, a);
-    else if (a.bm == 128 && a.bn == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 128>), grid, dim3(256), 0, s, a);
+    else if (a.bm == 128 && a.bn == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 128, 8>), grid, dim3(512), 0, s, a);
     else if (a.bm == 128 && a.bn == 64) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 64>), grid, dim3(256), 0, s, a);
     else if (a.bm == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<128, 32>), grid, dim3(256), 0, s, a);
-    else if (a.bn == 128 && eight > 1) hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 128, 8>), grid, dim3(512), 0, s, a);
-    else if (a.bn == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 128>), grid, dim3(256), 0, s, a);
+    else if (a.bn == 128) hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 128, 8>), grid, dim3(512), 0, s, a);
     else hipLaunchKernelGGL((conv_wgrad_f32_kernel<64, 64>), grid, dim3(256), 0, s, a);
     if (!direct) {
         const long n = (long)sets * a.Cout * a.K;

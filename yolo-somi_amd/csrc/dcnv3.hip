@@ -1313,11 +1313,11 @@ static void launch_win(const DcnArgs &a, const GinGeo &q, size_t lds, hipStream_
     }
 }
 
-// geometry of the windowed forms (tile + kernel reach + R pixels of offset slack); false for other group widths
+// geometry of the windowed forms (tile + kernel reach + R = 2 pixels of offset slack, SOMI_DCN_SLACK in somi_hip.h); false for other
+// group widths
 static bool win_geo(const DcnArgs &a, GinGeo &q) {
     if (!(a.Gc == 8 || a.Gc == 16 || a.Gc == 32 || a.Gc == 64)) return false;
-    static const int slack = [] { const char *e = getenv("SOMI_DCN_SLACK"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 8 ? 8 : v); }();
-    q.R = slack;
+    q.R = 2;
     const int half_h = (a.dh * (a.kh - 1)) >> 1, half_w = (a.dw * (a.kw - 1)) >> 1;
     const int lo_rh = (int)ceilf((float)half_h * a.offset_scale), hi_rh = (int)ceilf((float)((a.kh - 1) * a.dh - half_h) * a.offset_scale);
     const int lo_rw = (int)ceilf((float)half_w * a.offset_scale), hi_rw = (int)ceilf((float)((a.kw - 1) * a.dw - half_w) * a.offset_scale);
@@ -1361,19 +1361,15 @@ static bool gin_plan(const DcnArgs &a, GinGeo &q, GinPlan &pl) {
     pl.lds = (size_t)GIN_TP * a.Gc * sizeof(float) + (size_t)GIN_TP * a.K * (sizeof(RecG) + 4 * sizeof(float) + 4) + GIN_OVF_CAP * sizeof(OvfG) +
              3 * ((size_t)q.WH * q.WW + 1) * sizeof(int);
     if (pl.lds > 150 * 1024 || (long)q.tiles_h * q.tiles_w > 65535L * 32) return false;
-    // B on the matrix cores for 32-wide groups when its LDS image fits (SOMI_DCN_GIN=exact keeps the list sums for comparisons) ...
-    const char *gsel = getenv("SOMI_DCN_GIN");
+    // B on the matrix cores for 32-wide groups when its LDS image fits ...
     const size_t ncell_ = (size_t)q.WH * q.WW, recb = (size_t)GIN_TP * a.K * sizeof(RecM), gotb = (size_t)a.Gc * GMM_LD * sizeof(float);
     pl.mlds = ncell_ * GMM_LD * sizeof(float) + ((recb > gotb ? recb : gotb) + 15) / 16 * 16 + GMM_OVF_CAP * sizeof(OvfG);
-    pl.mfma = a.Gc == 32 && pl.mlds <= 78 * 1024 + 512 && !(gsel && gsel[0] == 'e');
-    // ... and, stride 1 with the near pass on, in its COLOURED form: tiles whose windows cannot overlap run together and add straight into
-    // grad_input - no staging slab, no combine pass.  Up to 2 x 2 colours (a 3 x 3 kernel); SOMI_DCN_SLAB=1 keeps the slab form (A/B runs).
-    static const bool near_on = [] { const char *e = getenv("SOMI_DCN_NEAR"); return !(e && e[0] == '0'); }();
-    const char *slab_env = getenv("SOMI_DCN_SLAB");
+    pl.mfma = a.Gc == 32 && pl.mlds <= 78 * 1024 + 512;
+    // ... and, stride 1, in its COLOURED form: tiles whose windows cannot overlap run together and add straight into grad_input - no
+    // staging slab, no combine pass.  Up to 2 x 2 colours (a 3 x 3 kernel).
     pl.nch = (q.WH + GIN_TH * a.sh - 1) / (GIN_TH * a.sh);
     pl.ncw = (q.WW + GIN_TW * a.sw - 1) / (GIN_TW * a.sw);
-    pl.coloured = pl.mfma && near_on && a.sh == 1 && a.sw == 1 && pl.nch * pl.ncw <= 4 && a.N <= 65535 && q.WH * q.WW <= GMM_MAX_CELLS &&
-                  !(slab_env && slab_env[0] == '1');
+    pl.coloured = pl.mfma && a.sh == 1 && a.sw == 1 && pl.nch * pl.ncw <= 4 && a.N <= 65535 && q.WH * q.WW <= GMM_MAX_CELLS;
     static const long cap_mb = [] { const char *e = getenv("SOMI_DCN_SLAB_MB"); const long v = e ? atol(e) : 1024; return v < 1 ? 1 : v; }();
     const size_t per_img = (size_t)a.G * q.tiles_h * q.tiles_w * q.WH * q.WW * a.Gc * sizeof(float);
     long c = (long)(((size_t)cap_mb << 20) / per_img);
@@ -1512,8 +1508,7 @@ extern "C" int somi_dcnv3_backward_strided_f32(const float *input, const float *
         unsigned *const any_words = reinterpret_cast<unsigned *>(wsb + slab + pl.near_bytes);          // one near_any word per chunk
         q.overflow = reinterpret_cast<unsigned *>(wsb + pl.workspace_bytes - 256);
         // the near pass needs stride 1 (source tile t then sits over destination tile t + const) and 8-aligned tiles of the INPUT image
-        static const bool near_on = [] { const char *e = getenv("SOMI_DCN_NEAR"); return !(e && e[0] == '0'); }();
-        q.near = (near_on && stride_h == 1 && stride_w == 1) ? reinterpret_cast<unsigned *>(wsb + slab) : nullptr;
+        q.near = (stride_h == 1 && stride_w == 1) ? reinterpret_cast<unsigned *>(wsb + slab) : nullptr;
         (void)hipMemsetAsync(any_words, 0, pl.any_bytes + 256, s);    // the per-chunk near_any words and the far-tap counter behind them
         const size_t mlds = pl.mlds;
         const bool mfma = pl.mfma;

@@ -7,7 +7,7 @@
 //   A  per pixel:   dlogit = (sum_c dt2*t*ca) * sa*(1-sa);  amaxc = argmax_c (t*ca)
 //   B  7x7 conv:    dstats = conv7x7^T(dlogit);  dW7 += sum_p dlogit * stats(shifted);  db7 += sum_p dlogit
 //   C  per element: dt1 = dt2*sa + dstats[.,0]/C + [c==amaxc]*dstats[.,1];  dca[b,c] = sum_p dt1*t;  dt = dt1*ca
-//   D  per (b,c):   amaxp = argmax_p t            (the max-pool's winner)
+//   D  per (b,c):   amaxp = argmax_p t            (the max-pool's winner: the first pixel equal to the forward's max, found inside A)
 //   E  per sample:  MLP backward -> dW1,db1,dW2,db2 (accumulated), d avg, d max
 //   F  per element: dt += davg/HW + [p==amaxp]*dmax
 #include "common.h"
@@ -315,90 +315,6 @@ __global__ __launch_bounds__(256) void img_partial_sum_kernel(const float *__res
     out[i] = (float)s;
 }
 
-// ------------------------------------------------------------------------------------------------ D
-__global__ __launch_bounds__(256) void pool_argmax_stage1(const float *__restrict__ x, int x_cs, int x_coff, int HW, int C,
-                                                          float *__restrict__ pmax, int *__restrict__ pidx, int nchunk) {
-    __shared__ float lm[256][4];
-    __shared__ int li[256][4];
-    const int chunk = blockIdx.x, b = blockIdx.y;
-    const int C4 = C >> 2;
-    const int p0 = chunk * IMG_CHUNK, p1 = min(p0 + IMG_CHUNK, HW);
-    for (int cq0 = 0; cq0 < C4; cq0 += 256) {
-        const int ncq = min(256, C4 - cq0);
-        const int rows_par = 256 / ncq;
-        const int cq = threadIdx.x % ncq, rr = threadIdx.x / ncq;
-        const int c = (cq0 + cq) * 4;
-        float m[4];
-        int mi[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { m[e] = -__builtin_huge_valf(); mi[e] = 0x7fffffff; }
-        if (rr < rows_par) {
-#pragma unroll 4
-            for (int pl = p0 + rr; pl < p1; pl += rows_par) {            // unrolled: four rows' loads in flight
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(x + ((long)b * HW + pl) * x_cs + x_coff + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (v[e] > m[e]) { m[e] = v[e]; mi[e] = pl; }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lm[threadIdx.x][e] = m[e]; li[threadIdx.x][e] = mi[e]; }
-        __syncthreads();
-        if (threadIdx.x < ncq) {
-            for (int r2 = 1; r2 < rows_par; ++r2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float om = lm[r2 * ncq + cq][e];
-                    const int oi = li[r2 * ncq + cq][e];
-                    if (om > m[e] || (om == m[e] && oi < mi[e])) { m[e] = om; mi[e] = oi; }
-                }
-            const long o = ((long)b * nchunk + chunk) * C + c;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { pmax[o + e] = m[e]; pidx[o + e] = mi[e]; }
-        }
-        __syncthreads();
-    }
-}
-// 16 columns x 16 chunk groups; a group keeps its first maximum (chunks ascend in pixel order inside a group), the groups are merged by
-// (value, lowest pixel index) - the first maximum in pixel order, as torch.max returns it
-__global__ __launch_bounds__(256) void pool_argmax_stage2(const float *__restrict__ pmax, const int *__restrict__ pidx, int nchunk, int C, int B,
-                                                          int *__restrict__ amaxp) {
-    __shared__ float lm[256];
-    __shared__ int li[256];
-    const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + cl;
-    float m = -__builtin_huge_valf();
-    int mi = 0x7fffffff;
-    if (i < B * C) {
-        const int b = i / C, c = i % C;
-        const long base = (long)b * nchunk * C + c;
-        for (int k = grp; k < nchunk; k += 64) {
-            float v[4];
-            int x[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool ok = k + u * 16 < nchunk;
-                v[u] = ok ? pmax[base + (long)(k + u * 16) * C] : -__builtin_huge_valf();
-                x[u] = ok ? pidx[base + (long)(k + u * 16) * C] : 0x7fffffff;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (v[u] > m || (v[u] == m && x[u] < mi)) { m = v[u]; mi = x[u]; }
-        }
-    }
-    lm[threadIdx.x] = m;
-    li[threadIdx.x] = mi;
-    __syncthreads();
-    if (grp != 0 || i >= B * C) return;
-#pragma unroll
-    for (int g = 1; g < 16; ++g) {
-        const float om = lm[g * 16 + cl];
-        const int oi = li[g * 16 + cl];
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    amaxp[i] = mi;
-}
-
 // ------------------------------------------------------------------------------------------------ E
 // one workgroup per sample.  mode 0 (CBAM): out = sigmoid(o_avg + o_max), o_x = W2 relu(W1 x + b1) + b2
 //                            mode 1 (SEAM): out = exp(sigmoid(W2 relu(W1 avg)))               (no biases)
@@ -549,15 +465,6 @@ using namespace somi;
 
 extern "C" int somi_img_nchunk(int HW) { return (HW + IMG_CHUNK - 1) / IMG_CHUNK; }
 
-extern "C" int somi_cbam_bwd_pixel_f32(const float *dt2, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
-                                       const float *sa, float *dlogit, int32_t *amaxc, int B, int HW, int C, somi_stream_t stream) {
-    SOMI_REQUIRE(sl_ok(dt2, d_cs, d_coff, C) && sl_ok(t, t_cs, t_coff, C) && ca && sa && dlogit && amaxc && B > 0 && HW > 0 && C % 4 == 0 &&
-                     aligned16(ca), SOMI_EINVAL, "cbam bwd pixel: bad arguments");
-    hipLaunchKernelGGL(cbam_bwd_pixel_kernel, dim3(ew_grid((long)B * HW * 64)), dim3(256), 0, (hipStream_t)stream, dt2, d_cs, d_coff, t, t_cs,
-                       t_coff, ca, sa, dlogit, amaxc, B, HW, C, nullptr, nullptr);
-    return launch_status("somi_cbam_bwd_pixel_f32");
-}
-
 extern "C" int somi_cbam_bwd_pixel_argmax_f32(const float *dt2, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
                                               const float *sa, const float *t_max, float *dlogit, int32_t *amaxc, int32_t *amaxp, int B, int HW,
                                               int C, somi_stream_t stream) {
@@ -605,18 +512,6 @@ extern "C" int somi_cbam_bwd_chan_f32(float *dt2_inout, int d_cs, int d_coff, co
                        workspace, HW, C, nchunk);
     hipLaunchKernelGGL(img_partial_sum_kernel, dim3(cdiv((long)B * C, 16)), dim3(256), 0, s, workspace, nchunk, C, B, dca);
     return launch_status("somi_cbam_bwd_chan_f32");
-}
-
-extern "C" int somi_pool_argmax_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int HW, int C, int32_t *amaxp, void *workspace,
-                                         somi_stream_t stream) {
-    SOMI_REQUIRE(sl_ok(x, x_cs, x_coff, C) && amaxp && workspace && B > 0 && HW > 0 && C % 4 == 0, SOMI_EINVAL, "pool argmax: bad arguments");
-    const int nchunk = somi_img_nchunk(HW);
-    float *pm = static_cast<float *>(workspace);
-    int *pi = reinterpret_cast<int *>(pm + (size_t)B * nchunk * C);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pool_argmax_stage1, dim3(nchunk, B), dim3(256), 0, s, x, x_cs, x_coff, HW, C, pm, pi, nchunk);
-    hipLaunchKernelGGL(pool_argmax_stage2, dim3(cdiv((long)B * C, 16)), dim3(256), 0, s, pm, pi, nchunk, C, B, amaxp);
-    return launch_status("somi_pool_argmax_nhwc_f32");
 }
 
 extern "C" size_t somi_attn_mlp_bwd_workspace_floats(int B, int C, int mid) { return (size_t)B * (C + 3 * mid); }

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SOMI_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'lib', 'libsomi_hip.so')   # override: kernel experiments
 
-ABI_VERSION = 14         # SOMI_ABI_VERSION of include/somi_hip.h this binding was written against
+ABI_VERSION = 15         # SOMI_ABI_VERSION of include/somi_hip.h this binding was written against
 c_f32p = C.c_void_p      # device pointers travel as integers
 c_stream = C.c_void_p
 
@@ -68,6 +68,7 @@ SIGNATURES = {
     'somi_conv2d_wgrad_workspace_bytes': (Z, [C.POINTER(ConvDesc)]),
     'somi_conv2d_wgrad_nhwc_f32': (I, [C.POINTER(ConvDesc), P, I, I, P, I, I, P, P, P, Z, S]),
     'somi_conv2d_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
+    'somi_conv2d_wgrad_kernel_name': (C.c_char_p, [C.POINTER(ConvDesc)]),
     'somi_dcnv3_forward_f32': (I, [P, P, P, P] + [I] * 13 + [F, I, S]),
     'somi_dcnv3_backward_workspace_bytes': (Z, [I] * 13 + [F]),
     'somi_dcnv3_backward_f32': (I, [P, P, P, P, P, P, P] + [I] * 13 + [F, I, P, Z, S]),
@@ -119,14 +120,12 @@ SIGNATURES = {
     'somi_add_nhwc_f32': (I, [P, I, I, P, I, I, P, I, I, C.c_long, I, S]),
     'somi_chan_sum_nhwc_f32': (I, [P, I, I, C.c_long, I, P, P, S]),
     'somi_img_nchunk': (I, [I]),
-    'somi_cbam_bwd_pixel_f32': (I, [P, I, I, P, I, I, P, P, P, P, I, I, I, S]),
     'somi_cbam_bwd_pixel_argmax_f32': (I, [P, I, I, P, I, I, P, P, P, P, P, P, I, I, I, S]),
     'somi_cbam_bn_bwd_workspace_floats': (C.c_size_t, [I, I, I]),
     'somi_cbam_bn_bwd_reduce_f32': (I, [P, I, I, P, I, I, P, P, P, P, P, P, P, P, P, P, I, I, I, S]),
     'somi_cbam_bn_bwd_apply_f32': (I, [P, I, I, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, P, P, I, I, I, S]),
     'somi_spatial_attn_bwd_f32': (I, [P, P, P, P, P, P, P, I, I, I, I, I, S]),
     'somi_cbam_bwd_chan_f32': (I, [P, I, I, P, I, I, P, P, P, P, P, P, I, I, I, S]),
-    'somi_pool_argmax_nhwc_f32': (I, [P, I, I, I, I, I, P, P, S]),
     'somi_attn_mlp_bwd_workspace_floats': (Z, [I, I, I]),
     'somi_attn_mlp_bwd_f32': (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, S]),
     'somi_pool_bwd_add_nhwc_f32': (I, [P, I, I, P, P, P, I, I, I, S]),

@@ -221,7 +221,7 @@ class Conv(_Packed):
         B, H, W, _ = x.shape
         Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
         y = torch.empty(B, Ho, Wo, cp, device=x.t.device, dtype=torch.float32)
-        if ops.FUSED_BN_STATS and y.numel() * 4 <= 0xE0000000:      # the conv epilogue leaves the per-channel partial sums of y
+        if y.numel() * 4 <= 0xE0000000:                          # the conv epilogue leaves the per-channel partial sums of y
             st = {'pivot': pk['rm']}
             ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
                             alg_cin=x.c, alg_cout=c2, bn_stats=st)
@@ -392,11 +392,10 @@ class ChannelAttentionModule(_Packed):
             self.__dict__['_ctx'] = (x, avg, mx, ca, (W1, b1, W2, b2))
         return ca
 
-    def backward(self, dca, dt, amaxp=None, defer=False):
+    def backward(self, dca, dt, amaxp, defer=False):
         """dca (B,C): gradient w.r.t. the attention vector; adds the pooled-input gradient into dt (Act) in place - or, defer=True, returns
         (davg, dmax, amaxp) for the producer's BatchNorm backward to fold in (Conv.backward(pooled=...)) and leaves dt alone.
-        amaxp (B,C) int32: first pixel of every channel's spatial maximum when the caller already has it (the CBAM backward takes it in its own
-        pass over x); else it is found here."""
+        amaxp (B,C) int32: first pixel of every channel's spatial maximum (the CBAM backward finds it in its own pass over x)."""
         x, avg, mx, ca, (W1, b1, W2, b2) = self.__dict__.pop('_ctx')
         l1, l2 = self.shared_MLP[0], self.shared_MLP[2]
         prms = (l1.weight, l1.bias, l2.weight, l2.bias)
@@ -405,8 +404,6 @@ class ChannelAttentionModule(_Packed):
         for prm, (gr, scratch) in zip(prms, g):
             if scratch:
                 _acc_grad(prm, gr)
-        if amaxp is None:
-            amaxp = ops.pool_argmax(x.t, x.c, x.coff)
         if defer:
             return davg, dmax, amaxp
         ops.pool_backward_add_(dt.t, dt.coff, x.c, davg, dmax, amaxp)
@@ -442,10 +439,10 @@ class SpatialAttentionModule(_Packed):
         self.__dict__['_ctx'] = (x, ca, stats, sa, w)
         return Act(out, 0, x.c)
 
-    def backward(self, dt2, t_max=None, bn=None):
+    def backward(self, dt2, t_max, bn=None):
         """dt2: gradient tensor w.r.t. x*ca*sa (whole tensor, modified in place into the x-gradient through both products and
-        the spatial branch).  Returns dca (B,C) and - with t_max (B,C), the spatial maximum of x the channel attention pooled - amaxp (B,C): the
-        first pixel holding each channel's maximum (for the max-pool's gradient), else None.
+        the spatial branch).  Returns dca (B,C) and amaxp (B,C): the first pixel holding each channel's maximum (for the max-pool's gradient),
+        found from t_max (B,C), the spatial maximum of x the channel attention pooled.
         bn = (y, scale, shift, mean) of the Conv that produced x: dt2 is left as it is and a third value - the state for that Conv's
         backward(cbam=...) - is returned (ops.cbam_backward)."""
         x, ca, stats, sa, w = self.__dict__.pop('_ctx')
@@ -474,7 +471,7 @@ class CBAMBottleneck(nn.Module):
         self.spatial_attention = SpatialAttentionModule(kernel_size)
 
     def forward(self, x, out=None):
-        pool = {} if (self.training and ops.FUSE_POOL) else None
+        pool = {} if self.training else None
         t = self.cv1(x, pool=pool)                                # training: the BatchNorm + SiLU pass also takes the attention's global pools
         ca = self.channel_attention(t, pooled=(pool['avg'], pool['max']) if pool else None)
         t2 = self.spatial_attention(t, ca)
@@ -482,20 +479,22 @@ class CBAMBottleneck(nn.Module):
             self.__dict__['_ctx'] = (x, t)
         return self.cv2(t2, out=out, residual=x if self.add else None)
 
+    def _step_c_in_bn(self, d, t):
+        """Step C inside cv1's BatchNorm + SiLU backward (else a pass of its own): local batch statistics, a SiLU, whole unpadded d and t."""
+        c_ = self.cv1.conv.out_channels
+        return ops.SYNC_BN is None and isinstance(self.cv1.act, nn.SiLU) and pad4(c_) == c_ and d.coff == t.coff == 0 and d.t.shape[3] == c_
+
     def backward(self, dout, dx_out):
         """dout: gradient w.r.t. the block output (Act); the input gradient is ADDED into dx_out (Act, e.g. a slice of the
         C2f gradient buffer that already holds the gradient of the input's other consumers)."""
         x, t = self.__dict__.pop('_ctx')
         d = self.cv2.backward(dout)                               # d(t*ca*sa)
-        # d.t then holds the direct part of dt; the channel attention's pooled maximum lets the same pass find its arg-max pixels
-        t_max = self.channel_attention.__dict__['_ctx'][2] if ops.AMAX_BY_VALUE else None
-        c_ = self.cv1.conv.out_channels
         bn = None
-        if (ops.CBAM_FUSED_BN and ops.BN_POOLED and ops.SYNC_BN is None and t_max is not None and isinstance(self.cv1.act, nn.SiLU) and pad4(c_) == c_
-                and d.coff == 0 and d.t.shape[3] == c_ and t.coff == 0):
+        if self._step_c_in_bn(d, t):
             _, y1, mean1, _, scale1, shift1, _ = self.cv1.__dict__['_ctx']      # step C + the pooled terms + BatchNorm backward: two passes over (d, y1)
             bn = (y1, scale1, shift1, mean1)
-        dca, amaxp, *state = self.spatial_attention.backward(d.t, t_max=t_max, bn=bn)
+        # d.t then holds the direct part of dt; the channel attention's pooled maximum lets the same pass find its arg-max pixels
+        dca, amaxp, *state = self.spatial_attention.backward(d.t, t_max=self.channel_attention.__dict__['_ctx'][2], bn=bn)
         pooled = self.channel_attention.backward(dca, d, amaxp, defer=True)   # the pooled paths join d inside cv1's BatchNorm backward
         c1 = self.cv1.conv.in_channels
         fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0  # the shortcut's gradient rides the dgrad epilogue
@@ -882,7 +881,7 @@ class SEAM(_Packed):
         u1 = ops.dwconv3x3(y0, pk['dw1'], pk['b1'])
         y1, s1 = self._bn_train(u1, st[0].fn[2], residual=y0)    # Residual: fn(y0) + y0
         u2 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1)
-        if ops.SYNC_BN is None and ops.FUSE_POOL:
+        if ops.SYNC_BN is None:
             # BN(GELU(u2)) is read by the global average pool only, and the mean of an affine map is the affine map of the mean: the statistics pass,
             # then ONE pass that averages gelu(u2) per image and applies scale / shift to the (B,C) result - the normalised tensor is never written
             bn2 = st[3]
@@ -1255,7 +1254,7 @@ class DCNv3_YOLO(_Packed):
         self.invalidate()
         bn, dev = self.bn, x.t.device
         rm, rv = bn.running_mean.detach().clone(), bn.running_var.detach().clone()
-        sd = {'pivot': rm} if ops.FUSED_BN_STATS and x.t.numel() * 4 <= 0xE0000000 else None
+        sd = {'pivot': rm} if x.t.numel() * 4 <= 0xE0000000 else None
         u, saved = self.dcnv3._forward_impl(x.t, keep=True, bn_stats=sd)
         if sd is not None and 'part' in sd:                       # the output projection's epilogue left the partial sums: no extra read of u
             st = ops.bn_stats_from_partials(sd['part'], sd['rows'], u.numel() // c, c, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum,

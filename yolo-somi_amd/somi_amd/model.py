@@ -269,14 +269,13 @@ class Model(nn.Module):
                 kw = {'pooled': pend} if pend is not None else {}
                 if (have is not None and isinstance(m, (B.Conv, B.C2fCBAM, B.C3, B.SPPF, B.SPP, B.ODConv_3rd)) and have.coff == 0 and
                         have.t.shape[3] == B.pad4(have.c) and have.t.is_contiguous() and have.pooled is None and
-                        (not isinstance(m, B.ODConv_3rd) or (ops.ODCONV_INPLACE and have.t.shape[3] == have.c))):
+                        (not isinstance(m, B.ODConv_3rd) or have.t.shape[3] == have.c)):
                     # the input already holds another consumer's gradient: the data-gradient epilogue adds to it in place
-                    if (isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.BN_POOLED and ops.SYNC_BN is None):
+                    if isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.SYNC_BN is None:
                         have.pooled = m.backward(g, dx_out=have, accumulate=True, defer_pool=True).pooled    # the last consumer to arrive: see below
                     else:
                         m.backward(g, dx_out=have, accumulate=True, **kw)
-                elif (have is None and isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.BN_POOLED and
-                      ops.SYNC_BN is None and ops.ODCONV_INPLACE):
+                elif have is None and isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.SYNC_BN is None:
                     # the only consumer of a plain Conv's output (later layers have all been walked): its squeeze gradient rides that Conv's BatchNorm backward
                     give(srcs[0], m.backward(g, defer_pool=True))
                 else:
@@ -299,7 +298,7 @@ class Model(nn.Module):
                 if m.f != -1:
                     a = y[m.f] if isinstance(m.f, int) else [a if j == -1 else y[j] for j in m.f]
                 nxt = self.model[m.i + 1] if m.i + 1 < len(self.model) else None
-                if (self.training and ops.FUSE_POOL and ops.ODCONV_INPLACE and type(m) in (B.Conv, B.C2fCBAM) and isinstance(nxt, B.ODConv_3rd) and nxt.f == -1):
+                if self.training and type(m) in (B.Conv, B.C2fCBAM) and isinstance(nxt, B.ODConv_3rd) and nxt.f == -1:
                     pool = {}                                     # the next layer squeezes this output: its last BatchNorm + SiLU pass takes the average
                     a = m(a, pool=pool)
                     if 'avg' in pool:

@@ -11,8 +11,6 @@ import torch
 from . import _lib
 from ._lib import ConvDesc, check
 
-STREAMK = os.environ.get('SOMI_CONV_STREAMK', '1') != '0'
-FUSED_BN_STATS = os.environ.get('SOMI_FUSED_BN_STATS', '1') != '0'   # batch statistics from the conv epilogue (training forward)
 DCN_DIRECT = os.environ.get('SOMI_DCN_DIRECT', '0') == '1'          # 1: DCNv3 backward scatters with fp32 atomics (the reference's form)
 PROFILE = None   # bench.py sets this to a list: every conv launch appends (kernel name, algorithmic FLOPs, ev0, ev1)
 
@@ -24,19 +22,11 @@ _CONV_WS = {}
 # claim is made on), 1 bf16 operands, 2 bf16x3 split (somi_conv_desc.prec).  train.TrainStep(amp=...) / bench.py --amp set it.
 CONV_PREC = 0
 PREC = {None: 0, 'f32': 0, 'bf16': 1, 'bf16x3': 2}
-FUSE_POOL = os.environ.get('SOMI_FUSE_POOL', '1') != '0'      # 0: the channel attention pools its input in a pass of its own (round-3 form; A/B runs)
-AMAX_BY_VALUE = os.environ.get('SOMI_AMAX_BY_VALUE', '1') != '0'   # 0: the max-pool's arg-max from somi_pool_argmax_nhwc_f32's own pass over the tensor
-ODCONV_INPLACE = os.environ.get('SOMI_ODCONV_INPLACE', '1') != '0'   # 0: ODConv's squeeze pools its input itself; its input gradient goes through a tensor of its own + add passes (A/B runs)
-FUSE_DWLN = os.environ.get('SOMI_FUSE_DWLN', '1') != '0'    # 0: the DCNv3 block's depthwise conv and LayerNorm + GELU as two passes (A/B runs)
-CBAM_FUSED_BN = os.environ.get('SOMI_CBAM_FUSED_BN', '1') != '0'   # 0: CBAM's step C as a pass of its own before the BatchNorm backward (A/B runs)
-BN_POOLED = os.environ.get('SOMI_BN_POOLED', '1') != '0'    # 0: CBAM's pooled gradients are added by a pass of their own (round-3 form; A/B runs)
 
 
 def _conv_workspace(d, dev):
     """Attach the stream-K scratch of the current stream to a conv descriptor (launches on one stream are ordered, so they
-    can share it).  SOMI_CONV_STREAMK=0 keeps the one-workgroup-per-tile schedule."""
-    if not STREAMK:
-        return
+    can share it).  A descriptor without it runs the one-workgroup-per-tile schedule."""
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     ws = _CONV_WS.get(key)
     if ws is None:
@@ -635,12 +625,7 @@ def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, cin=None, x_coff=0, cou
                                        _ptr(accumulate), _ptr(ws), nbytes, _stream()), 'conv2d_wgrad_nhwc')
     if prof:
         e1.record()
-        bm = 64 if -(-cout // 64) * 64 < -(-cout // 128) * 128 else 128            # conv_wgrad.hip plan()
-        K = kh * kw * cin
-        bn = 128 if K > 64 else (64 if (K > 32 or bm == 64) else 32)
-        eight = int(os.environ.get('SOMI_WGRAD_8WAVE', '2'))
-        nw = 8 if ((bm, bn) == (128, 128) and eight >= 1) or ((bm, bn) == (64, 128) and eight >= 2) else 4
-        PROFILE.append((f'conv_wgrad_f32_kernel<{bm},{bn},{nw}>', 2.0 * B * Ho * Wo * cout * cin * kh * kw, e0, e1,
+        PROFILE.append((L.somi_conv2d_wgrad_kernel_name(C.byref(d)).decode(), 2.0 * B * Ho * Wo * cout * cin * kh * kw, e0, e1,
                         (B, H, W, cin, cout, kh, stride, 3)))
     return out
 
@@ -738,7 +723,7 @@ def bn_act_backward(dz, dz_coff, x, x_coff, c, mean, rstd, scale, shift, act, or
     n = _npix(x)
     if pooled is not None:
         davg, dmax, amaxp = pooled
-        if BN_POOLED and SYNC_BN is None and batch_stats and davg.shape[1] == c and x.dim() == 4:
+        if SYNC_BN is None and batch_stats and davg.shape[1] == c and x.dim() == 4:
             B, HW = x.shape[0], x.shape[1] * x.shape[2]
             L = _lib.lib()
             ws = torch.empty(2 * L.somi_bn_pooled_rows(B, HW) * c + 3 * ((c + 3) // 4 * 4), device=x.device, dtype=torch.float32)
@@ -788,26 +773,21 @@ def add_(a, a_coff, b, b_coff, c, out=None, out_coff=None):
     return out
 
 
-def cbam_backward(dt2, t, t_coff, c, ca, sa, stats, w7, k, dw7, db7, t_max=None, dw_chw=False, bn=None):
-    """Steps A-C of train_blocks.hip: turns d(t*ca*sa) (dt2, whole tensor, modified in place) into the part of dt that flows
-    through the two multiplications and the spatial branch; returns dca (B,C) and, when t_max (B,C) - the spatial maximum of t the forward pooled -
-    is given, amaxp (B,C) int32: the first pixel that holds each channel's maximum (step D, found by value inside step A's pass), else None.
+def cbam_backward(dt2, t, t_coff, c, ca, sa, stats, w7, k, dw7, db7, t_max, dw_chw=False, bn=None):
+    """Steps A-D of train_blocks.hip: turns d(t*ca*sa) (dt2, whole tensor, modified in place) into the part of dt that flows
+    through the two multiplications and the spatial branch; returns dca (B,C) and amaxp (B,C) int32: the first pixel that holds each channel's
+    maximum (step D, found by value inside step A's pass from t_max (B,C), the spatial maximum of t the forward pooled).
     dw7 / db7 are accumulated; dw7 is [k][k][2] like w7, or (dw_chw) laid out (2,k,k) like nn.Conv2d's weight.
-    bn = (y, scale, shift, mean) of the Conv -> BatchNorm -> SiLU that produced t (needs t_max): step C is NOT run as a pass of its own - dt2 is left
+    bn = (y, scale, shift, mean) of the Conv -> BatchNorm -> SiLU that produced t: step C is NOT run as a pass of its own - dt2 is left
     alone, dca comes from the reduction half of the fused BatchNorm backward, and a third value is returned: the state cbam_bn_backward_apply needs."""
     B, H, W, _ = t.shape
     dev = t.device
     L = _lib.lib()
     dlogit = torch.empty(B, H, W, device=dev, dtype=torch.float32)
     amaxc = torch.empty(B, H, W, device=dev, dtype=torch.int32)
-    amaxp = None
-    if t_max is not None:
-        amaxp = torch.empty(B, c, device=dev, dtype=torch.int32)
-        check(L.somi_cbam_bwd_pixel_argmax_f32(_ptr(_f32c(dt2)), dt2.shape[3], 0, _ptr(_f32c(t)), t.shape[3], t_coff, _ptr(ca), _ptr(sa), _ptr(t_max),
-                                               _ptr(dlogit), _ptr(amaxc), _ptr(amaxp), B, H * W, c, _stream()), 'cbam_bwd_pixel')
-    else:
-        check(L.somi_cbam_bwd_pixel_f32(_ptr(_f32c(dt2)), dt2.shape[3], 0, _ptr(_f32c(t)), t.shape[3], t_coff, _ptr(ca), _ptr(sa), _ptr(dlogit),
-                                        _ptr(amaxc), B, H * W, c, _stream()), 'cbam_bwd_pixel')
+    amaxp = torch.empty(B, c, device=dev, dtype=torch.int32)
+    check(L.somi_cbam_bwd_pixel_argmax_f32(_ptr(_f32c(dt2)), dt2.shape[3], 0, _ptr(_f32c(t)), t.shape[3], t_coff, _ptr(ca), _ptr(sa), _ptr(t_max),
+                                           _ptr(dlogit), _ptr(amaxc), _ptr(amaxp), B, H * W, c, _stream()), 'cbam_bwd_pixel')
     dstats = torch.empty(B, H, W, 2, device=dev, dtype=torch.float32)
     ws = torch.empty(((B * H * W + 511) // 512) * (2 * k * k + 1), device=dev, dtype=torch.float32)
     check(L.somi_spatial_attn_bwd_f32(_ptr(dlogit), _ptr(stats), _ptr(w7), _ptr(dstats), _ptr(dw7), _ptr(db7), _ptr(ws), B, H, W, k,
@@ -835,15 +815,6 @@ def cbam_bn_backward_apply(state, rstd, davg, dmax, dx, dgamma, dbeta):
                                                 _ptr(sa), _ptr(dstats), _ptr(amaxc), _ptr(amaxp), _ptr(davg), _ptr(dmax), _ptr(_f32c(dx)), dx.shape[3], 0,
                                                 _ptr(dgamma), _ptr(dbeta), _ptr(ws), B, H * W, c, _stream()), 'cbam_bn_bwd_apply')
     return dx
-
-
-def pool_argmax(x, c, x_coff=0):
-    B, H, W, cs = x.shape
-    L = _lib.lib()
-    out = torch.empty(B, c, device=x.device, dtype=torch.int32)
-    ws = torch.empty(2 * B * L.somi_img_nchunk(H * W) * c, device=x.device, dtype=torch.float32)
-    check(L.somi_pool_argmax_nhwc_f32(_ptr(_f32c(x)), cs, x_coff, B, H * W, c, _ptr(out), _ptr(ws), _stream()), 'pool_argmax')
-    return out
 
 
 def attn_mlp_backward(mode, dout, out, avg, mx, W1, b1, W2, dW1, db1, dW2, db2):
