@@ -507,6 +507,31 @@ int somi_axpby_f32(float *y, const float *x, long n, float a, float b, somi_stre
 int somi_pack_dgrad_weights_f32(const float *w_packed, float *w_dgrad, int Cout, int taps, int Cin, somi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouped / depthwise convolution (Conv with g > 1, DWConv, the GhostConv cheap operation; models/common.py:53-70, 9580-9583, 2001-2011).
+ * NHWC fp32; C1 input and C2 output channels in `groups` groups of cin_g = C1/groups and cout_g = C2/groups; k in {1, 3, 5},
+ * stride 1 or 2, pad k/2, dilation 1; cin_g <= 16.  Depthwise (cin_g = cout_g = 1) reads float4 quads of channels.
+ * Weights are packed [k*k][cin_g][w_cs] (tap-major, output channel fastest, columns >= C2 zero).  Channel slices: offsets and row
+ * strides multiples of 4.  Deterministic: fixed-order reductions, no float atomics.  fp32 only (the conv precision switch does not apply).
+ *
+ * Forward: y[.., y_coff + co] = act(conv + bias) [+ residual] for co < Cw (Cw >= C2, a multiple of 4; channels C2..Cw come out zero
+ * when their weights and bias are).  stat_sum / stat_sumsq (optional, [somi_gconv2d_stat_rows][Cw] each): per-channel partial sums of
+ * (y - stat_pivot) and its square, the format of the dense conv epilogue's (somi_conv_desc.stat_sum), for somi_bn_stats_partials_f32. */
+int somi_gconv2d_stat_rows(int B, int Ho, int Wo, int Cw);
+int somi_gconv2d_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int H, int W, int C1, const float *w, int w_cs, const float *bias,
+                          int groups, int k, int stride, float *y, int y_cs, int y_coff, int C2, int Cw, int act, const float *residual,
+                          int res_cs, int res_coff, float *stat_sum, float *stat_sumsq, const float *stat_pivot, somi_stream_t stream);
+/* Data gradient: dx[.., dx_coff + ci] = conv^T(dy) [+ acc1] [+ acc2] for ci < Cx (Cx >= C1, a multiple of 4); acc1 may be dx itself
+ * (accumulate in place).  w is the forward packing. */
+int somi_gconv2d_dgrad_nhwc_f32(const float *dy, int dy_cs, int dy_coff, int B, int Ho, int Wo, int C2, const float *w, int w_cs, int groups,
+                                int k, int stride, float *dx, int dx_cs, int dx_coff, int H, int W, int C1, int Cx, const float *acc1,
+                                int acc1_cs, int acc1_coff, const float *acc2, int acc2_cs, int acc2_coff, somi_stream_t stream);
+/* Weight gradient into dw (C2, cin_g, k, k) - the nn.Conv2d layout - written, or added to when accumulate != 0. */
+size_t somi_gconv2d_wgrad_workspace_floats(int B, int Ho, int Wo, int C2, int cin_g, int k);
+int somi_gconv2d_wgrad_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int H, int W, int C1, const float *dy, int dy_cs, int dy_coff,
+                                int Ho, int Wo, int C2, int groups, int k, int stride, float *dw, int accumulate, float *workspace,
+                                size_t workspace_floats, somi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stock YOLOv5 module set (north_star "CSP/Darknet backbone, PANet/FPN neck, anchor-based detection head"; BASELINE configs[0]).
  * Bottleneck / C3 / SPP (models/common.py:1494-1509,1541-1565,1806-1826) are compositions of the convolution entry points above
  * (C3's torch.cat never materialises: cv2 and the last bottleneck write the two halves of cv3's input; SPP's parallel 5/9/13

@@ -150,6 +150,11 @@ SIGNATURES = {
     'somi_adam_ema_step_f32': (I, [P, P, P, P, P, C.c_long, F, F, F, F, F, I, F, S]),
     'somi_sgd_ema_step_f32': (I, [P, P, P, P, C.c_long, F, F, F, I, F, S]),
     'somi_pack_dgrad_weights_f32': (I, [P, P, I, I, I, S]),
+    'somi_gconv2d_stat_rows': (I, [I, I, I, I]),
+    'somi_gconv2d_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, P, I, I, I, P, I, I, I, I, I, P, I, I, P, P, P, S]),
+    'somi_gconv2d_dgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, P, I, I, I, I, I, I, P, I, I, P, I, I, S]),
+    'somi_gconv2d_wgrad_workspace_floats': (Z, [I, I, I, I, I, I]),
+    'somi_gconv2d_wgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, P, Z, S]),
     'somi_axpby_f32': (I, [P, P, C.c_long, F, F, S]),
     'somi_nms_workspace_bytes': (Z, [I, I, I, I]),
     'somi_nms_f32': (I, [P, I, I, I, F, F, I, I, P, I, P, P, P, Z, S]),

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .pack import pack_conv_weight, pack_dgrad_weight, pad4, bn_fold
+from .pack import pack_conv_weight, pack_dgrad_weight, pack_gconv_weight, pad4, bn_fold
 
 
 class Act:
@@ -174,21 +174,29 @@ def _pack_wb(w, b, dev):
 
 
 class Conv(_Packed):
-    """conv2d(bias=False) -> BatchNorm2d -> SiLU as one fused launch (models/common.py:53-70)."""
+    """conv2d(bias=False) -> BatchNorm2d -> SiLU as one fused launch (models/common.py:53-70).  g > 1 runs on the grouped / depthwise
+    kernels (gconv.hip): k 1, 3 or 5, stride 1 or 2, pad k // 2, at most 16 input channels per group."""
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
-        if g != 1 or d != 1:
-            raise NotImplementedError('grouped / dilated Conv is not on the SOMI path')
+        if d != 1:
+            raise NotImplementedError('dilated Conv is not on the SOMI path')
         if isinstance(k, (tuple, list)):                         # C3 hands its bottlenecks (1, 1) / (3, 3) (models/common.py:1558)
             if len(k) != 2 or k[0] != k[1]:
                 raise NotImplementedError('square kernels only')
             k = int(k[0])
+        if g != 1:
+            if k not in (1, 3, 5) or s not in (1, 2) or autopad(k, p, d) != k // 2:
+                raise NotImplementedError(f'grouped Conv with k={k}, s={s}, p={p} is not on the SOMI path (k 1/3/5, stride 1/2, pad k // 2)')
+            if c1 % g == 0 and c1 // g > 16:
+                raise NotImplementedError(f'grouped Conv with {c1 // g} input channels per group is not on the SOMI path (at most 16)')
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p, d), groups=g, dilation=d, bias=False)
         self.bn = nn.BatchNorm2d(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
 
     def _pack(self, dev):
+        if self.conv.groups > 1:
+            return self._pack_grouped(dev)
         if self.training:                                        # raw weights, batch-norm applied from batch statistics
             w = self.conv.weight
             c2, c1, k = w.shape[0], w.shape[1], w.shape[2]
@@ -210,6 +218,22 @@ class Conv(_Packed):
             return dict(wp=wp, gp=gp, wt=wt, **vec)
         return _pack_wb(*_fold_conv_bn(self.conv, getattr(self, 'bn', None)), dev)
 
+    def _pack_grouped(self, dev):
+        """training: raw weights [k*k][cin_g][pad4(c2)] and the padded BatchNorm vectors; eval: BatchNorm folded into weights and bias."""
+        c2, cp = self.conv.out_channels, pad4(self.conv.out_channels)
+        if not self.training:
+            w, b = _fold_conv_bn(self.conv, getattr(self, 'bn', None))
+            bp = torch.zeros(cp, device=dev)
+            bp[:c2] = b.to(dev)
+            return pack_gconv_weight(w, cp).to(dev), bp
+        bn = self.bn
+        if cp == c2 and bn.weight.device == dev:
+            vec = dict(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var, inplace=True)
+        else:
+            padv = lambda t, fill: torch.cat([t.detach().float().to(dev), torch.full((cp - c2,), fill, device=dev)])   # noqa: E731
+            vec = dict(gamma=padv(bn.weight, 0.), beta=padv(bn.bias, 0.), rm=padv(bn.running_mean, 0.), rv=padv(bn.running_var, 1.), inplace=False)
+        return dict(gw=pack_gconv_weight(self.conv.weight.detach(), cp).to(dev), **vec)
+
     # ------------------------------------------------------------------------------------------ training mode
     def _forward_train(self, x, out, residual, pool=None):
         """y = conv(x) (raw) -> batch statistics -> z = act(y*scale+shift) [+ residual]; keeps what backward needs.
@@ -221,7 +245,13 @@ class Conv(_Packed):
         B, H, W, _ = x.shape
         Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
         y = torch.empty(B, Ho, Wo, cp, device=x.t.device, dtype=torch.float32)
-        if y.numel() * 4 <= 0xE0000000:                          # the conv epilogue leaves the per-channel partial sums of y
+        if self.conv.groups > 1:                                 # grouped / depthwise: the same partial sums, from the stencil kernel
+            st = {'pivot': pk['rm']}
+            ops.gconv2d_nhwc(x.t, pk['gw'], c1=self.conv.in_channels, c2=c2, groups=self.conv.groups, k=k, stride=s, x_coff=x.coff, out=y, cw=cp,
+                             bn_stats=st)
+            mean, rstd, scale, shift = ops.bn_stats_from_partials(st['part'], st['rows'], B * Ho * Wo, cp, pk['gamma'], pk['beta'],
+                                                                  self.bn.eps, self.bn.momentum, pk['rm'], pk['rv'])
+        elif y.numel() * 4 <= 0xE0000000:                        # the conv epilogue leaves the per-channel partial sums of y
             st = {'pivot': pk['rm']}
             ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
                             alg_cin=x.c, alg_cout=c2, bn_stats=st)
@@ -289,6 +319,8 @@ class Conv(_Packed):
             _acc_grad(self.bn.weight, dgam[:c2])
             _acc_grad(self.bn.bias, dbet[:c2])
         B, H, W, _ = x.shape
+        if self.conv.groups > 1:
+            return self._backward_grouped(x, dy, pk, dx_out, accumulate, need_dx, also_add)
         if pk['gp'] is not None:                                  # accumulate into the packed gradient master
             ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=s, pad=p, cin=pad4(c1), x_coff=x.coff, cout=cp, out=pk['gp'],
                                   accumulate=pk['gp'])
@@ -305,9 +337,33 @@ class Conv(_Packed):
                               acc2_coff=0 if also_add is None else also_add.coff)
         return dx_out
 
+    def _backward_grouped(self, x, dy, pk, dx_out, accumulate, need_dx, also_add):
+        """Weight gradient straight into .grad ((c2, c1/g, k, k), no packed master for grouped weights), then the data gradient: written into
+        dx_out (added to it if accumulate, + also_add's slice)."""
+        k, s = self.conv.kernel_size[0], self.conv.stride[0]
+        c1, c2, g = self.conv.in_channels, self.conv.out_channels, self.conv.groups
+        B, H, W, _ = x.shape
+        (gw,), fin = _grad_targets(self.conv.weight)
+        ops.gconv2d_wgrad_nhwc(x.t, dy, c1=c1, c2=c2, groups=g, k=k, stride=s, x_coff=x.coff, out=gw, accumulate=True)
+        fin()
+        if not need_dx:
+            return None
+        whole = also_add is None and (dx_out is None or (dx_out.coff == 0 and dx_out.t.shape[3] == pad4(c1)))
+        cx = pad4(c1) if whole else c1                            # a whole tensor gets its pad channels written (zero, + what accumulates there)
+        if cx % 4:
+            raise NotImplementedError('grouped Conv backward into a channel slice needs in_channels % 4 == 0')
+        if dx_out is None:
+            dx_out = Act((torch.empty if cx == pad4(c1) else torch.zeros)(B, H, W, pad4(c1), device=dy.device, dtype=torch.float32), 0, c1)
+        ops.gconv2d_dgrad_nhwc(dy, pk['gw'], H=H, W=W, c1=c1, c2=c2, groups=g, k=k, stride=s, out=dx_out.t, dx_coff=dx_out.coff, cx=cx,
+                               accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff,
+                               accumulate2=None if also_add is None else also_add.t, acc2_coff=0 if also_add is None else also_add.coff)
+        return dx_out
+
     def forward(self, x, out=None, residual=None, a_chan=None, a_pix=None, pool=None):
         if self.training:
             return self._forward_train(x, out, residual, pool)
+        if self.conv.groups > 1:
+            return self._forward_grouped(x, out, residual, a_chan, a_pix)
         wp, bp = self._packed(x.t.device)
         k, s, p = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0]
         c2 = self.conv.out_channels
@@ -325,6 +381,26 @@ class Conv(_Packed):
                         residual=None if residual is None else residual.t,
                         res_coff=0 if residual is None else residual.coff, a_chan_scale=a_chan, a_pix_scale=a_pix,
                         alg_cin=x.c, alg_cout=c2)
+        return Act(out.t, out.coff, c2)
+
+    def _forward_grouped(self, x, out, residual, a_chan, a_pix):
+        """Eval: BatchNorm folded, act, optional residual slice - one launch of the grouped kernel."""
+        if a_chan is not None or a_pix is not None:
+            raise NotImplementedError('attention scales are not folded into the grouped conv')
+        wp, bp = self._packed(x.t.device)
+        k, s = self.conv.kernel_size[0], self.conv.stride[0]
+        c1, c2 = self.conv.in_channels, self.conv.out_channels
+        B, H, W, _ = x.shape
+        Ho, Wo = ops.conv_out_size(H, k, s, k // 2), ops.conv_out_size(W, k, s, k // 2)
+        if out is None:
+            out, cw = new_act(x.t, Ho, Wo, c2), pad4(c2)
+        else:
+            if c2 % 4:
+                raise NotImplementedError('writing into a channel slice needs c2 % 4 == 0')
+            cw = c2
+        ops.gconv2d_nhwc(x.t, wp, bp, c1=c1, c2=c2, groups=self.conv.groups, k=k, stride=s, x_coff=x.coff, out=out.t, y_coff=out.coff, cw=cw,
+                         act=_act_name(self.act), residual=None if residual is None else residual.t,
+                         res_coff=0 if residual is None else residual.coff)
         return Act(out.t, out.coff, c2)
 
 
@@ -1127,6 +1203,99 @@ class Focus(nn.Module):
             raise NotImplementedError('Focus writes its own input gradient')
         c = self.conv.conv.in_channels // 4
         return Act(ops.space_to_depth(d.t, d.coff, c, inverse=True), 0, c)
+
+
+class DWConv(Conv):
+    """Conv with g = gcd(c1, c2) (models/common.py:9580-9583): depthwise when c1 == c2, a channel multiplier or gcd grouping otherwise."""
+
+    def __init__(self, c1, c2, k=1, s=1, act=True):
+        super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), act=act)
+
+
+class GhostConv(nn.Module):
+    """cat(cv1(x), cv2(cv1(x))) with cv2 a 5x5 depthwise Conv (models/common.py:2001-2011).  cv1 writes channels [0, c_) of the output,
+    cv2 reads them and writes [c_, 2c_): no torch.cat.  act=False is no activation on both convs (the reference's own class passes `act`
+    into Conv's dilation slot and cannot run with act=False)."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
+
+    def forward(self, x, out=None, residual=None):
+        """residual: an Act of 2c_ channels added to the output (GhostBottleneck's shortcut): its halves ride the two convs' output passes -
+        cv1's output then goes to a tensor of its own first (cv2 reads it without the residual)."""
+        c_ = self.cv1.conv.out_channels
+        if c_ % 4:
+            raise NotImplementedError('GhostConv hidden width must be a multiple of 4 on the MI355X path')
+        k, s = self.cv1.conv.kernel_size[0], self.cv1.conv.stride[0]
+        H, W = x.shape[1], x.shape[2]
+        Ho, Wo = ops.conv_out_size(H, k, s, k // 2), ops.conv_out_size(W, k, s, k // 2)
+        if out is None:
+            out = concat_act(x.t, Ho, Wo, 2 * c_)
+        t = self.cv1(x, out=out.slice(0, c_) if residual is None else None)
+        self.cv2(t, out=out.slice(c_, c_), residual=None if residual is None else residual.slice(c_, c_))
+        if residual is not None:
+            ops.add_(t.t, t.coff, residual.t, residual.coff, c_, out=out.t, out_coff=out.coff)
+        return Act(out.t, out.coff, 2 * c_)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True, also_add=None):
+        """The first half's gradient is dout[0, c_) plus what flows back through cv2: one dgrad pass writes their sum."""
+        c_ = self.cv1.conv.out_channels
+        dt = self.cv2.backward(dout.slice(c_, c_), also_add=dout.slice(0, c_))
+        return self.cv1.backward(dt, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=also_add)
+
+
+class GhostBottleneck(nn.Module):
+    """conv(x) + shortcut(x) (models/common.py:2014-2029): GhostConv -> [depthwise k x k, stride 2] -> GhostConv(act=False); the shortcut is
+    the identity (s = 1) or depthwise stride 2 -> 1x1 Conv (s = 2), both without activation.  The sum rides the last GhostConv's passes."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1),
+                                  DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+                                  GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+    @property
+    def stride(self):
+        return 2 if isinstance(self.conv[1], Conv) else 1
+
+    def forward(self, x, out=None):
+        g1, dw, g2 = self.conv
+        if self.stride == 2:
+            sc = self.shortcut[1](self.shortcut[0](x))
+            t = dw(g1(x))
+        else:
+            if x.c != g2.cv1.conv.out_channels * 2:
+                raise RuntimeError(f'GhostBottleneck(s=1) adds its input to its output: {x.c} and {2 * g2.cv1.conv.out_channels} channels')
+            sc, t = x, g1(x)
+        return g2(t, out=out, residual=sc)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        g1, dw, g2 = self.conv
+        d = g2.backward(dout)
+        if self.stride == 2:
+            dx = g1.backward(dw.backward(d), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+            ds = self.shortcut[1].backward(dout)
+            return self.shortcut[0].backward(ds, dx_out=dx, accumulate=True, need_dx=need_dx)
+        c1 = g1.cv1.conv.in_channels
+        fuse = pad4(c1) == c1 and dout.coff % 4 == 0             # the identity shortcut's gradient rides the dgrad epilogue
+        dx = g1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class C3Ghost(C3):
+    """C3 whose bottlenecks are GhostBottleneck(c_, c_) (models/common.py:1798-1803); `shortcut` is ignored there too."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
 
 
 class Concat(nn.Module):

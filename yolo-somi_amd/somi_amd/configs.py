@@ -126,6 +126,23 @@ def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0'):
                 backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
 
 
+def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
+    """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
+    C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""
+    import copy
+    bb = [[-1, 1, 'Focus', [64, 3]], [-1, 1, 'GhostConv', [128, 3, 2]], [-1, 3, 'C3Ghost', [128]], [-1, 1, 'GhostConv', [256, 3, 2]],
+          [-1, 9, 'C3Ghost', [256]], [-1, 1, 'GhostConv', [512, 3, 2]], [-1, 9, 'C3Ghost', [512]], [-1, 1, 'GhostConv', [1024, 3, 2]],
+          [-1, 1, 'SPP', [1024, [5, 9, 13]]], [-1, 3, 'C3Ghost', [1024, False]]]
+    up = [-1, 1, 'nn.Upsample', [None, 2, 'nearest']]
+    hd = [[-1, 1, 'GhostConv', [512, 1, 1]], up, [[-1, 6], 1, 'Concat', [1]], [-1, 3, 'C3Ghost', [512, False]],
+          [-1, 1, 'GhostConv', [256, 1, 1]], up, [[-1, 4], 1, 'Concat', [1]], [-1, 3, 'C3Ghost', [256, False]],
+          [-1, 1, 'GhostConv', [256, 3, 2]], [[-1, 14], 1, 'Concat', [1]], [-1, 3, 'C3Ghost', [512, False]],
+          [-1, 1, 'GhostConv', [512, 3, 2]], [[-1, 10], 1, 'Concat', [1]], [-1, 3, 'C3Ghost', [1024, False]],
+          [[17, 20, 23], 1, 'Detect', ['nc', 'anchors']]]
+    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors or COCO_ANCHORS),
+                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+
+
 def tiny_somi_cfg(nc=10):
     """A cut-down graph that uses every module class of the SOMI yaml once (Conv, ODConv_3rd, C2fCBAM, SPPF, nn.Upsample, BiFPN, SEAM,
     DecoupledDetect) at 32 / 64 channels, two detection levels: ~0.2 M parameters - for fixtures that carry whole pickled models."""

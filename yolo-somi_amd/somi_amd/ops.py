@@ -630,6 +630,69 @@ def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, cin=None, x_coff=0, cou
     return out
 
 
+# ---------------------------------------------------------------------------------------------- grouped / depthwise convolution
+# fp32 always: CONV_PREC (--amp bf16 / bf16x3) applies to the dense implicit GEMM only.
+def gconv2d_nhwc(x, w, bias=None, *, c1, c2, groups, k, stride=1, x_coff=0, out=None, y_coff=0, cw=None, act='none', residual=None, res_coff=0,
+                 bn_stats=None):
+    """Grouped conv of x's channel slice [x_coff, x_coff + c1) -> out's slice [y_coff, y_coff + cw); w packed [k*k][c1/groups][w_cs]
+    (pack.pack_gconv_weight), pad k // 2.  bn_stats: dict filled in place with the partial channel sums ('part' (2, rows, cw), 'rows')
+    around bn_stats['pivot'] - the dense conv2d_nhwc(bn_stats=...) format, for bn_stats_from_partials."""
+    B, H, W, x_cs = x.shape
+    Ho, Wo = conv_out_size(H, k, stride, k // 2), conv_out_size(W, k, stride, k // 2)
+    cw = (c2 + 3) // 4 * 4 if cw is None else cw
+    if out is None:
+        out = torch.empty(B, Ho, Wo, cw, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, Ho, Wo) or (residual is not None and tuple(residual.shape[:3]) != (B, Ho, Wo)):
+        raise RuntimeError(f'grouped conv: output / residual must be ({B}, {Ho}, {Wo}, .), got {tuple(out.shape)}')
+    L = _lib.lib()
+    ss = sq = piv = None
+    if bn_stats is not None:
+        rows = L.somi_gconv2d_stat_rows(B, Ho, Wo, cw)
+        part = torch.empty(2, rows, cw, device=x.device, dtype=torch.float32)
+        ss, sq, piv = part[0].data_ptr(), part[1].data_ptr(), _ptr(bn_stats.get('pivot'))
+        bn_stats['part'], bn_stats['rows'] = part, rows
+    check(L.somi_gconv2d_nhwc_f32(_ptr(_f32c(x, 'input')), x_cs, x_coff, B, H, W, c1, _ptr(_f32c(w, 'weight')), w.shape[-1], _ptr(bias), groups, k,
+                                  stride, _ptr(_f32c(out, 'output')), out.shape[3], y_coff, c2, cw, ACT[act],
+                                  _ptr(None if residual is None else _f32c(residual, 'residual')), 0 if residual is None else residual.shape[3],
+                                  res_coff, ss, sq, piv, _stream()), 'gconv2d_nhwc')
+    return out
+
+
+def gconv2d_dgrad_nhwc(dy, w, *, H, W, c1, c2, groups, k, stride=1, dy_coff=0, out=None, dx_coff=0, cx=None, accumulate=None, acc_coff=0,
+                       accumulate2=None, acc2_coff=0):
+    """Data gradient of gconv2d_nhwc into out's slice [dx_coff, dx_coff + cx) (+ accumulate's and accumulate2's slices; accumulate may be out)."""
+    B, Ho, Wo, dy_cs = dy.shape
+    cx = (c1 + 3) // 4 * 4 if cx is None else cx
+    if out is None:
+        out = torch.empty(B, H, W, cx, device=dy.device, dtype=torch.float32)
+    a1, a2 = accumulate, accumulate2
+    if any(t is not None and tuple(t.shape[:3]) != (B, H, W) for t in (out, a1, a2)):
+        raise RuntimeError(f'grouped conv dgrad: output / accumulated tensors must be ({B}, {H}, {W}, .)')
+    check(_lib.lib().somi_gconv2d_dgrad_nhwc_f32(_ptr(_f32c(dy, 'gradient')), dy_cs, dy_coff, B, Ho, Wo, c2, _ptr(_f32c(w, 'weight')), w.shape[-1],
+                                                 groups, k, stride, _ptr(_f32c(out, 'output')), out.shape[3], dx_coff, H, W, c1, cx,
+                                                 _ptr(None if a1 is None else _f32c(a1)), 0 if a1 is None else a1.shape[3], acc_coff,
+                                                 _ptr(None if a2 is None else _f32c(a2)), 0 if a2 is None else a2.shape[3], acc2_coff, _stream()),
+          'gconv2d_dgrad_nhwc')
+    return out
+
+
+def gconv2d_wgrad_nhwc(x, dy, *, c1, c2, groups, k, stride=1, x_coff=0, dy_coff=0, out=None, accumulate=False):
+    """Weight gradient (c2, c1/groups, k, k) of gconv2d_nhwc, written into `out` (or added to it when accumulate)."""
+    B, H, W, x_cs = x.shape
+    _, Ho, Wo, dy_cs = dy.shape
+    L = _lib.lib()
+    if out is None:
+        out = torch.empty(c2, c1 // groups, k, k, device=x.device, dtype=torch.float32)
+    if out.numel() != c2 * (c1 // groups) * k * k or dy.shape[0] != B:
+        raise RuntimeError('grouped conv wgrad: weight gradient or batch size does not match')
+    n = L.somi_gconv2d_wgrad_workspace_floats(B, Ho, Wo, c2, c1 // groups, k)
+    ws = torch.empty(max(n, 4), device=x.device, dtype=torch.float32)
+    check(L.somi_gconv2d_wgrad_nhwc_f32(_ptr(_f32c(x, 'input')), x_cs, x_coff, B, H, W, c1, _ptr(_f32c(dy, 'gradient')), dy_cs, dy_coff, Ho, Wo, c2,
+                                        groups, k, stride, _ptr(_f32c(out, 'weight gradient')), int(accumulate), _ptr(ws), ws.numel(), _stream()),
+          'gconv2d_wgrad_nhwc')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- training-mode helpers
 def _npix(t):
     return t.shape[0] * t.shape[1] * t.shape[2]

@@ -87,7 +87,7 @@ class FusedAdamEMA:
         # weight gradient is accumulated into the gradient buffer by the wgrad kernel itself
         from .blocks import Conv
         from .pack import pad4
-        owners = {id(m.conv.weight): m for m in model.modules() if isinstance(m, Conv)}
+        owners = {id(m.conv.weight): m for m in model.modules() if isinstance(m, Conv) and m.conv.groups == 1}   # grouped weights stay plain
         packed = {k: (pad4(m.conv.out_channels), m.conv.kernel_size[0], m.conv.kernel_size[1], pad4(m.conv.in_channels))
                   for k, m in owners.items()}
         self.param_groups, self._flat = [], []

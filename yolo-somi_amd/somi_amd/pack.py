@@ -22,6 +22,15 @@ def pack_conv_weight(w, cin_pad=None, cout_pad=None):
     return out.reshape(*lead, cout_pad, kh * kw * cin_pad).contiguous()
 
 
+def pack_gconv_weight(w, cout_pad=None):
+    """grouped (Cout,Cin/g,kh,kw) -> [kh*kw][Cin/g][Cout_pad] (operand of the grouped conv kernels, gconv.hip); pads are zero."""
+    Cout, cin_g, kh, kw = w.shape
+    cout_pad = pad4(Cout) if cout_pad is None else cout_pad
+    out = torch.zeros(kh * kw, cin_g, cout_pad, dtype=torch.float32, device=w.device)
+    out[:, :, :Cout] = w.float().permute(2, 3, 1, 0).reshape(kh * kw, cin_g, Cout)
+    return out.contiguous()
+
+
 def bn_fold(bn):
     """eval-mode BatchNorm as y = x*scale + shift (utils/torch_utils.py:212-219 uses the same two terms)."""
     scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
