@@ -532,6 +532,23 @@ int somi_gconv2d_wgrad_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int
                                 size_t workspace_floats, somi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PSA multi-head spatial self-attention (AttentionPSA, models/common.py:7203-7230; yolov10.yaml).  NHWC fp32, key_dim 32 and head_dim
+ * 64 fixed (scale 32^-0.5).  q, k and v are read in place from the qkv Conv's output: per pixel (row stride qkv_cs), head h's channels
+ * qkv_coff + h*128 + [0,32) are q, + [32,64) k and + [64,128) v.  N = H*W tokens per image, any N >= 1.  Channel offsets and row
+ * strides are multiples of 4.  The N x N matrix never reaches memory.  Deterministic: fixed-order sums, no float atomics.  fp32 only.
+ *
+ * Forward: o[.., o_coff + h*64 + d] = sum_j softmax_j(q.k_j * scale) v_j[d].  lse (optional, (B, heads, N)): the natural-log
+ * log-sum-exp of each row's scaled scores, for the backward pass.  v_out (optional): v written contiguously as (B, N, heads*64),
+ * channel h*64 + d - the input of the depthwise pe Conv. */
+int somi_psa_attention_f32(const float *qkv, int qkv_cs, int qkv_coff, int B, int N, int heads, float *o, int o_cs, int o_coff,
+                           float *lse, float *v_out, somi_stream_t stream);
+/* Backward: dq, dk, dv written into dqkv's slice (the qkv layout above; every channel of the heads' slice is written).  dv_add
+ * (optional, contiguous (B, N, heads*64)) is added to dv.  o and lse are the forward's; workspace holds B*heads*N floats. */
+int somi_psa_attention_backward_f32(const float *qkv, int qkv_cs, int qkv_coff, const float *o, int o_cs, int o_coff, const float *dout,
+                                    int do_cs, int do_coff, const float *lse, int B, int N, int heads, float *dqkv, int g_cs, int g_coff,
+                                    const float *dv_add, float *workspace, somi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stock YOLOv5 module set (north_star "CSP/Darknet backbone, PANet/FPN neck, anchor-based detection head"; BASELINE configs[0]).
  * Bottleneck / C3 / SPP (models/common.py:1494-1509,1541-1565,1806-1826) are compositions of the convolution entry points above
  * (C3's torch.cat never materialises: cv2 and the last bottleneck write the two halves of cv3's input; SPP's parallel 5/9/13

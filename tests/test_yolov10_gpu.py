@@ -1,0 +1,245 @@
+"""The YOLOv10 module set on the MI355X (C2f, SCDown, CIB, C2fCIB, AttentionPSA, PSA; models/hub/yolov10.yaml): the PSA attention kernels
+against fp64 on the CPU, the blocks against torch autograd on the CPU restatement (tests/yolov10_ref.py), the whole graph against the
+oracle Model.  Bar 1e-3 relative (BASELINE)."""
+import copy
+import io
+
+import pytest
+import torch
+
+import yolov10_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def rel_close(got, want, rel=1e-3, what='', atol=0.0):
+    got, want = got.detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert torch.isfinite(got).all(), f'{what}: not finite'
+    err = (got - want).abs().max().item()
+    scale = want.abs().max().item() + 1e-12
+    assert err <= rel * scale + atol, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _attn64(qkv, heads, dout=None, dv_add=None):
+    """fp64 reference on (B, N, 128*heads) token rows: -> o (B, N, 64*heads), lse (B, heads, N) and, given dout, the qkv gradient."""
+    qkv = qkv.double().requires_grad_(dout is not None)
+    B, N, _ = qkv.shape
+    t = qkv.view(B, N, heads, 128)
+    q, k, v = t[..., :32], t[..., 32:64], t[..., 64:]
+    s = torch.einsum('bihd,bjhd->bhij', q, k) * 32 ** -0.5
+    lse = torch.logsumexp(s, -1)
+    o = torch.einsum('bhij,bjhd->bihd', s.softmax(-1), v).reshape(B, N, 64 * heads)
+    g = None
+    if dout is not None:
+        o.backward(dout.double())
+        g = qkv.grad.clone()
+        if dv_add is not None:
+            g.view(B, N, heads, 128)[..., 64:] += dv_add.double().view(B, N, heads, 64)
+    return o.detach(), lse.detach(), g
+
+
+ACASES = [(1, 1, 1, 1), (2, 2, 5, 5), (1, 4, 13, 17), (2, 8, 20, 20), (1, 2, 40, 40), (3, 1, 7, 3)]
+
+
+@pytest.mark.parametrize('case', ACASES, ids=lambda c: 'x'.join(map(str, c)))
+def test_psa_attention_kernels(case):
+    """Forward (output, log-sum-exp, the contiguous v copy) and backward (dq, dk, dv with the dv addend) against fp64, read from and
+    written into channel slices of wider tensors; channels outside the written slices stay as they were; two launches are bit-identical."""
+    from somi_amd import ops
+    B, heads, H, W = case
+    N = H * W
+    gen = torch.Generator().manual_seed(sum(case))
+    cq, co = 128 * heads, 64 * heads
+    qkv_all = torch.randn(B, H, W, cq + 12, generator=gen)
+    dout_all = torch.randn(B, H, W, co + 8, generator=gen)
+    dv_add = torch.randn(B, H, W, co, generator=gen)
+    qkv = qkv_all[..., 4:4 + cq].reshape(B, N, cq)
+    o64, lse64, g64 = _attn64(qkv, heads, dout_all[..., 8:].reshape(B, N, co), dv_add.reshape(B, N, co))
+    dev = 'cuda'
+    qa, da, dva = qkv_all.to(dev), dout_all.to(dev), dv_add.to(dev)
+    o_fill = torch.randn(B, H, W, co + 4, generator=gen)
+    g_fill = torch.randn(B, H, W, cq + 8, generator=gen)
+
+    def run():
+        o = o_fill.clone().to(dev)
+        _, lse, v = ops.psa_attention(qa, heads, qkv_coff=4, out=o, o_coff=4, lse=True, v_out=True)
+        g = g_fill.clone().to(dev)
+        ops.psa_attention_backward(qa, o, da, lse, heads, qkv_coff=4, o_coff=4, do_coff=8, out=g, g_coff=8, dv_add=dva)
+        return o, lse, v, g
+
+    o, lse, v, g = run()
+    o2, lse2, v2, g2 = run()
+    torch.cuda.synchronize()
+    for a_, b_ in ((o, o2), (lse, lse2), (v, v2), (g, g2)):
+        assert torch.equal(a_, b_), 'two launches differ'
+    rel_close(o[..., 4:].reshape(B, N, co), o64, what='output')
+    rel_close(lse, lse64, what='log-sum-exp')
+    rel_close(v.reshape(B, N, heads, 64), qkv.view(B, N, heads, 128)[..., 64:], rel=0, what='v copy')
+    gg = g[..., 8:].reshape(B, N, heads, 128).cpu()
+    want = g64.view(B, N, heads, 128)
+    for name, sl in (('dq', slice(0, 32)), ('dk', slice(32, 64)), ('dv', slice(64, 128))):
+        rel_close(gg[..., sl], want[..., sl], what=name, atol=1e-5)   # N = 1: dq, dk are exactly 0, fp32 leaves P (dP - D) roundings
+    assert torch.equal(o[..., :4].cpu(), o_fill[..., :4]), 'output channels outside the slice changed'
+    assert torch.equal(g[..., :8].cpu(), g_fill[..., :8]), 'gradient channels outside the slice changed'
+
+
+def test_psa_attention_large_logits():
+    """q and k scaled so that exp of a raw score overflows fp32: the online max keeps everything finite and right."""
+    from somi_amd import ops
+    B, heads, H, W = 2, 2, 9, 11
+    N = H * W
+    gen = torch.Generator().manual_seed(7)
+    qkv = torch.randn(B, H, W, 128 * heads, generator=gen)
+    t = qkv.view(B, H, W, heads, 128)
+    t[..., :64] *= 12.0                                           # scores up to a few thousand: exp() of them is inf in fp32
+    dout = torch.randn(B, H, W, 64 * heads, generator=gen)
+    o64, lse64, g64 = _attn64(qkv.reshape(B, N, -1), heads, dout.reshape(B, N, -1))
+    assert lse64.abs().max() > 200                                # a naive exp(score) overflows
+    o, lse, _ = ops.psa_attention(qkv.cuda(), heads, lse=True)
+    g = ops.psa_attention_backward(qkv.cuda(), o, dout.cuda(), lse, heads)
+    rel_close(o.reshape(B, N, -1), o64, what='output')
+    rel_close(lse, lse64, what='log-sum-exp')
+    rel_close(g.reshape(B, N, -1), g64, rel=2e-3, what='qkv gradient')
+
+
+def _bn_hyper(mod):
+    for m in mod.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.eps, m.momentum = 1e-3, 0.03
+    return mod
+
+
+BLOCKS = {'c2f_n1_sc': (lambda M: M.C2f(32, 32, 1, True), (2, 32, 9, 11)),
+          'c2f_n2_sc': (lambda M: M.C2f(32, 32, 2, True), (2, 32, 10, 10)),
+          'c2f_n1_nosc': (lambda M: M.C2f(24, 32, 1, False), (2, 24, 7, 9)),
+          'c2f_n2_nosc': (lambda M: M.C2f(16, 48, 2, False), (3, 16, 8, 11)),
+          'scdown_k3s2': (lambda M: M.SCDown(16, 32, 3, 2), (2, 16, 13, 17)),
+          'cib': (lambda M: M.CIB(32, 32, True, e=1.0), (2, 32, 9, 7)),
+          'cib_noadd': (lambda M: M.CIB(16, 32, True, e=1.0), (2, 16, 9, 7)),
+          'c2fcib': (lambda M: M.C2fCIB(32, 32, 1, True), (2, 32, 9, 11)),
+          'c2fcib_n2_nosc': (lambda M: M.C2fCIB(24, 32, 2, False), (2, 24, 8, 8)),
+          'attnpsa': (lambda M: M.AttentionPSA(128, 2), (2, 128, 5, 7)),
+          'psa': (lambda M: M.PSA(256, 256), (1, 256, 5, 7)),
+          'psa_n156': (lambda M: M.PSA(128, 128), (2, 128, 12, 13))}
+
+
+@pytest.mark.parametrize('tag', list(BLOCKS))
+def test_yolov10_blocks_eval_train_backward(tag):
+    """Eval forward (BatchNorm folded), training forward, hand-written backward against torch autograd on the CPU restatement: output,
+    dx, every parameter gradient (BatchNorm's included) and the updated running statistics."""
+    from oracle.somi_ref import blocks as OB
+    from oracle.somi_ref.testing import fill_state
+    from somi_amd import blocks as MB
+    mk, shape = BLOCKS[tag]
+    ref, mine = mk(R), mk(MB)
+    fill_state(ref, 5)
+    OB.initialize_weights(ref)
+    mine.load_state_dict(ref.state_dict())
+    mine = _bn_hyper(mine).cuda()
+    gen = torch.Generator().manual_seed(len(tag))
+    x = torch.randn(*shape, generator=gen, requires_grad=True)
+    ref.eval(), mine.eval()
+    with torch.no_grad():
+        want = ref(x)
+        out = mine(MB.Act(nhwc(x.detach()).cuda()))
+    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(want), what=f'{tag} eval')
+    ref.train(), mine.train()
+    y = ref(x)
+    dy = torch.randn(y.shape, generator=gen)
+    y.backward(dy)
+    out = mine(MB.Act(nhwc(x.detach()).cuda()))
+    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(y), what=f'{tag} train forward')
+    dx = mine.backward(MB.Act(nhwc(dy).cuda()))
+    rel_close(dx.t[..., dx.coff:dx.coff + shape[1]], nhwc(x.grad), what=f'{tag} dx')
+    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
+        assert q.grad is not None and p.grad is not None, n
+        rel_close(p.grad, q.grad, what=f'{tag}: d{n}', atol=2e-5)
+    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
+        if 'running' in n:
+            rel_close(p, q, what=f'{tag}: {n}')
+
+
+def test_yolov10_graph_training_step_eval_and_checkpoint(monkeypatch):
+    """yolov10 at width 0.25 / depth 0.33, batch 2, 160x160 (PSA sees N = 25) against the oracle Model: one training forward, ComputeLoss
+    and backward (outputs, loss, every parameter gradient, BatchNorm statistics), the eval forward; two fresh TrainStep.step runs
+    bit-identical; attempt_load of a pickled oracle model reproduces the eval forward."""
+    from oracle.somi_ref import Model as OModel
+    from oracle.somi_ref.loss import ComputeLoss as OLoss
+    from oracle.somi_ref.testing import HYP_VISDRONE, fill_state, synthetic_batch
+    from somi_amd.checkpoint import attempt_load
+    from somi_amd.configs import yolov10_cfg
+    from somi_amd.loss import ComputeLoss
+    from somi_amd.model import Model
+    from somi_amd.train import TrainStep
+    R.register(monkeypatch)
+    cfg = yolov10_cfg(0.25, 0.33)
+    ref = fill_state(OModel(cfg), 3)
+    state = copy.deepcopy(ref.state_dict())
+    mine = Model(cfg)
+    mine.load_state_dict(state)
+    ref.hyp = mine.hyp = dict(HYP_VISDRONE)
+    imgs, targets = synthetic_batch(2, 160, nc=10, seed=2)
+    ref.train()
+    pr = ref(imgs.float() / 255)
+    lr, ir = OLoss(ref)(pr, targets)
+    lr.backward()
+    mine = mine.cuda().train()
+    pm = mine(imgs.cuda())
+    for a, b in zip(pm, pr):
+        rel_close(a, b, what='train outputs')
+    lm, im = ComputeLoss(mine)(pm, targets.cuda())
+    rel_close(lm, lr, rel=1e-4, what='loss')
+    rel_close(im, ir, rel=1e-4, what='loss items')
+    lm.backward()
+    bad = []
+    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
+        assert q.grad is not None and p.grad is not None, n
+        err = (p.grad.cpu().double() - q.grad.double()).abs().max().item()
+        scale = q.grad.double().abs().max().item() + 1e-9
+        if err > 2e-3 * scale + 2e-6:
+            bad.append((n, err, scale))
+    assert not bad, bad[:8]
+    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
+        if 'running' in n:
+            rel_close(p, q, what=n)
+    ref.eval(), mine.eval()
+    with torch.no_grad():
+        zr, _ = ref(imgs.float() / 255)
+        z, _ = mine(imgs.cuda())
+    rel_close(z, zr, what='z')
+
+    runs = []
+    for _ in range(2):
+        m = Model(cfg)
+        m.load_state_dict(state)
+        tr = TrainStep(m.cuda(), dict(HYP_VISDRONE), 2)
+        grads, real = [], tr.optimizer.step
+
+        def spy(real=real, grads=grads):
+            grads.extend(g_.clone() for g_ in tr.optimizer.flat_grads)
+            real()
+        tr.optimizer.step = spy
+        loss, _ = tr.step(imgs.cuda(), targets.cuda())
+        torch.cuda.synchronize()
+        runs.append((loss.detach().clone(), grads, {k: v.detach().clone() for k, v in m.state_dict().items()}))
+    (l0, g0, s0), (l1, g1, s1) = runs
+    assert torch.equal(l0, l1)
+    assert all(torch.equal(a, b) for a, b in zip(g0, g1)), 'gradients differ between two identical steps'
+    assert all(torch.equal(s0[k], s1[k]) for k in s0), [k for k in s0 if not torch.equal(s0[k], s1[k])][:5]
+
+    buf = io.BytesIO()
+    torch.save({'epoch': 1, 'model': copy.deepcopy(ref).half(), 'ema': None}, buf)
+    loaded, info = attempt_load(buf.getvalue(), foreign_prefixes=('oracle', 'yolov10_ref'))
+    assert info['used'] == 'model' and not loaded.training
+    want_model = copy.deepcopy(ref).half().float().eval()
+    with torch.no_grad():
+        rel_close(loaded(imgs.cuda())[0], want_model(imgs.float() / 255)[0], what='z from the loaded checkpoint')

@@ -155,6 +155,8 @@ SIGNATURES = {
     'somi_gconv2d_dgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, P, I, I, I, I, I, I, P, I, I, P, I, I, S]),
     'somi_gconv2d_wgrad_workspace_floats': (Z, [I, I, I, I, I, I]),
     'somi_gconv2d_wgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, P, Z, S]),
+    'somi_psa_attention_f32': (I, [P, I, I, I, I, I, P, I, I, P, P, S]),
+    'somi_psa_attention_backward_f32': (I, [P, I, I, P, I, I, P, I, I, P, I, I, I, P, I, I, P, P, S]),
     'somi_axpby_f32': (I, [P, P, C.c_long, F, F, S]),
     'somi_nms_workspace_bytes': (Z, [I, I, I, I]),
     'somi_nms_f32': (I, [P, I, I, I, F, F, I, I, P, I, P, P, P, Z, S]),

@@ -1298,6 +1298,163 @@ class C3Ghost(C3):
         self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
 
 
+class C2f(nn.Module):
+    """cv2(cat(cv1(x).chunk(2), m_1, ..., m_n)) (models/common.py:2638-2658), laid out like C2fCBAM: all (2+n) pieces live in one buffer,
+    block i reads piece i+1 and writes piece i+2.  In backward a block's data gradient is added into the piece that already holds cv2's."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__()
+        self.c = int(c2 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv((2 + n) * self.c, c2, 1)
+        self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
+
+    def forward(self, x):
+        c, n = self.c, len(self.m)
+        if c % 4:
+            raise NotImplementedError(f'{type(self).__name__} hidden width must be a multiple of 4 on the MI355X path')
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, (2 + n) * c)
+        self.cv1(x, out=cat.slice(0, 2 * c))
+        for i, blk in enumerate(self.m):
+            blk(cat.slice((1 + i) * c, c), out=cat.slice((2 + i) * c, c))
+        return self.cv2(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        c, n = self.c, len(self.m)
+        dcat = self.cv2.backward(dout)
+        for i in reversed(range(n)):
+            self.m[i].backward(dcat.slice((2 + i) * c, c), dx_out=dcat.slice((1 + i) * c, c), accumulate=True)
+        return self.cv1.backward(dcat.slice(0, 2 * c), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
+class SCDown(nn.Module):
+    """1x1 Conv -> k x k depthwise Conv, stride s, BatchNorm, no activation (models/common.py:7192-7200)."""
+
+    def __init__(self, c1, c2, k, s):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.cv2 = Conv(c2, c2, k=k, s=s, g=c2, act=False)
+
+    def forward(self, x, out=None):
+        return self.cv2(self.cv1(x), out=out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        return self.cv1.backward(self.cv2.backward(dout), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
+class CIB(nn.Module):
+    """dw3x3 -> 1x1 -> dw3x3 -> 1x1 -> dw3x3, all Conv+BN+SiLU, (+x) (models/common.py:8981-9002).  The shortcut rides the last depthwise
+    conv's output pass in forward and the first one's data-gradient pass in backward."""
+
+    def __init__(self, c1, c2, shortcut=True, e=0.5, lk=False):
+        super().__init__()
+        if lk:
+            raise NotImplementedError("CIB(lk=True): RepVGGDW's 7x7 depthwise conv is outside the grouped conv kernels (k 1/3/5)")
+        c_ = int(c2 * e)
+        self.cv1 = nn.Sequential(Conv(c1, c1, 3, g=c1), Conv(c1, 2 * c_, 1), Conv(2 * c_, 2 * c_, 3, g=2 * c_), Conv(2 * c_, c2, 1),
+                                 Conv(c2, c2, 3, g=c2))
+        self.add = shortcut and c1 == c2
+
+    def forward(self, x, out=None):
+        t = x
+        for m in self.cv1[:-1]:
+            t = m(t)
+        return self.cv1[-1](t, out=out, residual=x if self.add else None)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = dout
+        for m in reversed(self.cv1[1:]):
+            d = m.backward(d)
+        return self.cv1[0].backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if self.add else None)
+
+
+class C2fCIB(C2f):
+    """C2f whose blocks are CIB(c, c, shortcut, e=1.0, lk) (models/common.py:9005-9013)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, lk=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(CIB(self.c, self.c, shortcut, e=1.0, lk=lk) for _ in range(n))
+
+
+class AttentionPSA(nn.Module):
+    """proj(attention(q, k, v) + pe(v)) over the H*W tokens of each image (models/common.py:7203-7230).  The attention kernels
+    (attention.hip) read q, k and v in place from qkv's output; the forward also leaves v as a contiguous tensor, which is pe's input, and pe
+    takes the attention output as its residual, so o + pe(v) is one pass.  In backward, pe's data gradient is the attention's dv addend."""
+
+    def __init__(self, dim, num_heads=8, attn_ratio=0.5):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.key_dim = int(self.head_dim * attn_ratio)
+        self.scale = self.key_dim ** -0.5
+        if self.head_dim != 64 or self.key_dim != 32 or dim != 64 * num_heads:
+            raise NotImplementedError(f'AttentionPSA({dim}, {num_heads}, {attn_ratio}): the attention kernels need head_dim 64 and key_dim 32 '
+                                      f'(dim = 64 * num_heads, attn_ratio 0.5), got {self.head_dim} / {self.key_dim}')
+        self.qkv = Conv(dim, dim + 2 * self.key_dim * num_heads, 1, act=False)
+        self.proj = Conv(dim, dim, 1, act=False)
+        self.pe = Conv(dim, dim, 3, 1, g=dim, act=False)
+
+    def forward(self, x, out=None, residual=None):
+        """residual: an Act added to the output in proj's pass (PSA's b + attn(b))."""
+        dim, nh = self.proj.conv.out_channels, self.num_heads
+        qkv = self.qkv(x)
+        o, lse, v = ops.psa_attention(qkv.t, nh, qkv_coff=qkv.coff, lse=self.training, v_out=True)
+        t = self.pe(Act(v, 0, dim), residual=Act(o, 0, dim))
+        if self.training:
+            self.__dict__['_ctx'] = (qkv, o, lse)
+        return self.proj(t, out=out, residual=residual)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True, also_add=None):
+        qkv, o, lse = self.__dict__.pop('_ctx')
+        nh = self.num_heads
+        dt = self.proj.backward(dout)                             # the gradient of o + pe(v): dO of the attention and pe's output gradient
+        dv = self.pe.backward(dt)
+        B, H, W, _ = dt.shape
+        dqkv = torch.empty(B, H, W, 128 * nh, device=dt.t.device, dtype=torch.float32)
+        ops.psa_attention_backward(qkv.t, o, dt.t, lse, nh, qkv_coff=qkv.coff, do_coff=dt.coff, out=dqkv, dv_add=dv.t)
+        return self.qkv.backward(Act(dqkv, 0, 128 * nh), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=also_add)
+
+
+class PSA(nn.Module):
+    """cv2(cat(a, b2)) with a, b = cv1(x).split, b1 = b + attn(b), b2 = b1 + ffn(b1) (models/common.py:7233-7255).  cv1 writes [a | b] into
+    cv2's input buffer; b is copied out once (attn.qkv's weight gradient still needs it after b2 has taken its place).  Both residual sums
+    ride the output passes of attn.proj and ffn[1]; in backward they ride the data-gradient passes of ffn[0] and attn.qkv, and qkv's writes
+    b's gradient next to a's, so cv1 reads one buffer."""
+
+    def __init__(self, c1, c2, e=0.5):
+        super().__init__()
+        if c1 != c2:
+            raise ValueError(f'PSA needs c1 == c2, got {c1} and {c2}')
+        self.c = int(c1 * e)
+        if self.c % 64 or self.c == 0:
+            raise NotImplementedError(f'PSA with {self.c} channels per branch: the attention kernels need head_dim 64 / key_dim 32, i.e. '
+                                      f'channels per branch a multiple of 64')
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.attn = AttentionPSA(self.c, attn_ratio=0.5, num_heads=self.c // 64)
+        self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
+
+    def forward(self, x):
+        c = self.c
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, 2 * c)
+        self.cv1(x, out=cat)
+        b = new_act(x.t, H, W, c)
+        ops.resample_slice(cat.t, c, b.t, 0, c)
+        b1 = self.attn(b, residual=b)
+        self.ffn[1](self.ffn[0](b1), out=cat.slice(c, c), residual=b1)
+        return self.cv2(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        c = self.c
+        dcat = self.cv2.backward(dout)
+        db2 = dcat.slice(c, c)
+        db1 = self.ffn[0].backward(self.ffn[1].backward(db2), also_add=db2)
+        self.attn.backward(db1, dx_out=db2, also_add=db1)         # db2's slice is free again: it takes b's gradient
+        return self.cv1.backward(dcat, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
 class Concat(nn.Module):
     """torch.cat(x, 1) (models/common.py:2085-2097) of NHWC channel slices; an input that is a 2x nearest-upsampled view
     (`Upsample` only sets a flag) is expanded by the same copy.  Backward hands out slices of the incoming gradient (no copy) and

@@ -143,6 +143,25 @@ def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
                 backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
 
 
+def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None):
+    """The layer table of models/hub/yolov10.yaml as a dict: Conv / C2f / SCDown backbone, C2fCIB at P5, SPPF, PSA, a C2f / C2fCIB PAN head
+    and the plain Detect.  Defaults are the yaml's (depth 1.0, width 1.0, 10 classes).  anchors=None gives the COCO anchors: the yaml's
+    `anchors: 3` is a placeholder (list(range(6)) per level) that only makes sense after autoanchor; anchors=3 reproduces the yaml exactly."""
+    import copy
+    bb = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'C2f', [128, True]], [-1, 1, 'Conv', [256, 3, 2]],
+          [-1, 6, 'C2f', [256, True]], [-1, 1, 'SCDown', [512, 3, 2]], [-1, 6, 'C2f', [512, True]], [-1, 1, 'SCDown', [1024, 3, 2]],
+          [-1, 3, 'C2fCIB', [1024, True]], [-1, 1, 'SPPF', [1024, 5]], [-1, 1, 'PSA', [1024]]]
+    up = [-1, 1, 'nn.Upsample', [None, 2, 'nearest']]
+    hd = [up, [[-1, 6], 1, 'Concat', [1]], [-1, 3, 'C2fCIB', [512, True]],
+          up, [[-1, 4], 1, 'Concat', [1]], [-1, 3, 'C2f', [256]],
+          [-1, 1, 'Conv', [256, 3, 2]], [[-1, 13], 1, 'Concat', [1]], [-1, 3, 'C2fCIB', [512, True]],
+          [-1, 1, 'SCDown', [512, 3, 2]], [[-1, 10], 1, 'Concat', [1]], [-1, 3, 'C2fCIB', [1024, True]],
+          [[16, 19, 22], 1, 'Detect', ['nc', 'anchors']]]
+    anchors = COCO_ANCHORS if anchors is None else anchors
+    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors),
+                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+
+
 def tiny_somi_cfg(nc=10):
     """A cut-down graph that uses every module class of the SOMI yaml once (Conv, ODConv_3rd, C2fCBAM, SPPF, nn.Upsample, BiFPN, SEAM,
     DecoupledDetect) at 32 / 64 channels, two detection levels: ~0.2 M parameters - for fixtures that carry whole pickled models."""

@@ -5,7 +5,8 @@ Same constructor (`Model(cfg, ch=3, nc=None, anchors=None)`), same attributes ca
 raw_l = (B,na,ny,nx,no).  Input is the reference's `(B,3,H,W)` NCHW batch, either float32 already divided by 255
 (train.py:249) or uint8 (the /255 then happens in the ingest kernel).  Accepted module names: the SOMI set of SURVEY.md
 section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, Concat, Detect - BASELINE configs[0]) and the Ghost set
-of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv).
+of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv) and the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
+C2fCIB, PSA).
 """
 import math
 from copy import deepcopy
@@ -24,8 +25,8 @@ def make_divisible(x, divisor):
 
 _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bottleneck': B.Bottleneck, 'C3': B.C3, 'SPP': B.SPP,
        'Focus': B.Focus, 'GhostConv': B.GhostConv, 'GhostBottleneck': B.GhostBottleneck, 'DWConv': B.DWConv,
-       'C3Ghost': B.C3Ghost}                                    # models/yolo.py:1472-1479
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost')                   # models/yolo.py:1487-1492
+       'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA}   # models/yolo.py:1472-1479
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB')  # models/yolo.py:1487-1492
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
 
 
@@ -140,6 +141,8 @@ class Model(nn.Module):
                 r *= m.cv1.conv.stride[0]
             elif isinstance(m, B.GhostBottleneck):
                 r *= m.stride
+            elif isinstance(m, B.SCDown):
+                r *= m.cv2.conv.stride[0]
             elif isinstance(m, B.Focus):
                 r *= 2 * m.conv.conv.stride[0]
             elif isinstance(m, B.ODConv_3rd):
@@ -273,7 +276,8 @@ class Model(nn.Module):
             else:
                 have = grads.get(srcs[0])
                 kw = {'pooled': pend} if pend is not None else {}
-                if (have is not None and isinstance(m, (B.Conv, B.C2fCBAM, B.C3, B.SPPF, B.SPP, B.ODConv_3rd, B.GhostConv, B.GhostBottleneck)) and
+                if (have is not None and isinstance(m, (B.Conv, B.C2fCBAM, B.C3, B.SPPF, B.SPP, B.ODConv_3rd, B.GhostConv, B.GhostBottleneck,
+                                                                B.C2f, B.SCDown, B.PSA)) and
                         have.coff == 0 and
                         have.t.shape[3] == B.pad4(have.c) and have.t.is_contiguous() and have.pooled is None and
                         (not isinstance(m, B.ODConv_3rd) or have.t.shape[3] == have.c)):

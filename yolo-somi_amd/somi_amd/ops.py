@@ -693,6 +693,45 @@ def gconv2d_wgrad_nhwc(x, dy, *, c1, c2, groups, k, stride=1, x_coff=0, dy_coff=
     return out
 
 
+# ---------------------------------------------------------------------------------------------- PSA attention
+# fp32 always, key_dim 32 / head_dim 64 (attention.hip).
+def psa_attention(qkv, heads, *, qkv_coff=0, out=None, o_coff=0, lse=False, v_out=False):
+    """Multi-head attention of AttentionPSA over the NHWC qkv Conv output's slice [qkv_coff, qkv_coff + 128*heads) (per head q 32 | k 32 |
+    v 64) -> out's slice [o_coff, o_coff + 64*heads).  lse: also return the log-sum-exp (B, heads, H*W) the backward needs; v_out: also
+    return v as a contiguous (B, H, W, 64*heads) tensor.  -> (out, lse or None, v or None)"""
+    B, H, W, cs = qkv.shape
+    N = H * W
+    if out is None:
+        out = torch.empty(B, H, W, 64 * heads, device=qkv.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'psa attention: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    lt = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32) if lse else None
+    vt = torch.empty(B, H, W, 64 * heads, device=qkv.device, dtype=torch.float32) if v_out else None
+    check(_lib.lib().somi_psa_attention_f32(_ptr(_f32c(qkv, 'qkv')), cs, qkv_coff, B, N, heads, _ptr(_f32c(out, 'output')), out.shape[3],
+                                            o_coff, _ptr(lt), _ptr(vt), _stream()), 'psa_attention')
+    return out, lt, vt
+
+
+def psa_attention_backward(qkv, o, dout, lse, heads, *, qkv_coff=0, o_coff=0, do_coff=0, out=None, g_coff=0, dv_add=None):
+    """Gradient of psa_attention w.r.t. q, k and v, written into out's slice [g_coff, g_coff + 128*heads) in the qkv layout.  dv_add: a
+    contiguous (B, H, W, 64*heads) tensor added to dv (the gradient that reached v through pe)."""
+    B, H, W, cs = qkv.shape
+    N = H * W
+    if out is None:
+        out = torch.empty(B, H, W, 128 * heads, device=qkv.device, dtype=torch.float32)
+    if any(t is not None and tuple(t.shape[:3]) != (B, H, W) for t in (o, dout, out, dv_add)) or tuple(lse.shape) != (B, heads, N):
+        raise RuntimeError(f'psa attention backward: tensors must be ({B}, {H}, {W}, .) and lse ({B}, {heads}, {N})')
+    if dv_add is not None and (dv_add.shape[3] != 64 * heads or not dv_add.is_contiguous()):
+        raise RuntimeError('psa attention backward: dv_add must be a contiguous (B, H, W, 64*heads) tensor')
+    ws = torch.empty(B * heads * N, device=qkv.device, dtype=torch.float32)
+    check(_lib.lib().somi_psa_attention_backward_f32(_ptr(_f32c(qkv, 'qkv')), cs, qkv_coff, _ptr(_f32c(o, 'output')), o.shape[3], o_coff,
+                                                     _ptr(_f32c(dout, 'gradient')), dout.shape[3], do_coff, _ptr(_f32c(lse, 'lse')), B, N,
+                                                     heads, _ptr(_f32c(out, 'qkv gradient')), out.shape[3], g_coff,
+                                                     _ptr(None if dv_add is None else _f32c(dv_add)), _ptr(ws), _stream()),
+          'psa_attention_backward')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- training-mode helpers
 def _npix(t):
     return t.shape[0] * t.shape[1] * t.shape[2]
