@@ -250,6 +250,28 @@ int somi_sppf_pool_nhwc_f32(float *buf, int B, int H, int W, int C, int cs, int 
  * (row-major) in its 5x5 window of the previous slice: `codes` = 3*B*H*W*C bytes, handed to somi_sppf_pool_bwd_nhwc_f32 as its workspace with buf = NULL. */
 int somi_sppf_pool_codes_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, somi_stream_t stream);
 
+/* Max-pooling outside SPPF's chained 5x5 (pool.hip).  NHWC fp32 channel slices; C, strides and offsets are multiples of 4.
+ * Routing rule of every entry: a pooled value's gradient goes to the FIRST maximum of its full window in row-major order (torch's max_pool2d
+ * autograd on the CPU); the forward leaves that position as one byte r * k + q per pooled element (`codes`, NULL in eval), the backward gathers by
+ * it: owner-computes, a fixed order of terms, no float atomics.
+ *
+ * maxpool2: nn.MaxPool2d(2, stride, 0), stride 1 or 2, floor mode, over x zero-padded by (pad_l, pad_r, pad_t, pad_b), each 0 or 1 - with
+ *   (0, 1, 0, 1) and stride 1 it is yolov3-tiny's nn.ZeroPad2d([0, 1, 0, 1]) + nn.MaxPool2d(2, 1, 0) in one pass.  The pad VALUE is 0 (not -inf): it wins
+ *   over negative activations, and the gradient of an output it won is dropped.  x (B,H,W,x_cs) -> y (B,Ho,Wo,y_cs), Ho = (H + pad_t + pad_b - 2) / stride + 1;
+ *   codes: B*Ho*Wo*C bytes.  The backward WRITES dx (B,H,W,dx_cs) - elements no window covers get 0; at stride 2 windows do not overlap and no sums form.
+ * spp_pool: the nk (1..3) PARALLEL stride-1 windows k0 < k1 < k2 of SPP (models/common.py:1806-1826), each odd and 3 <= k <= 13, implicit -inf pad of k / 2:
+ *   from x = slice [x_coff, x_coff + C) of buf (B,H,W,cs) the slices at x_coff + (i + 1) * C = pool_k[i](x), in place, in one walk over the largest window.
+ *   codes: nk*B*H*W*C bytes, window-major.  The backward ADDS the routed gradients of dbuf's slices 1..nk into its slice 0 (which holds x's direct
+ *   gradient from the concat's consumer). */
+int somi_maxpool2_nhwc_f32(const float *x, float *y, void *codes, int B, int H, int W, int C, int x_cs, int x_coff, int y_cs, int y_coff, int stride,
+                           int pad_l, int pad_r, int pad_t, int pad_b, somi_stream_t stream);
+int somi_maxpool2_bwd_nhwc_f32(const float *dy, const void *codes, float *dx, int B, int H, int W, int C, int dy_cs, int dy_coff, int dx_cs, int dx_coff,
+                               int stride, int pad_l, int pad_r, int pad_t, int pad_b, somi_stream_t stream);
+int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
+                           somi_stream_t stream);
+int somi_spp_pool_bwd_nhwc_f32(const void *codes, float *dbuf, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
+                               somi_stream_t stream);
+
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed
  * inside the kernel from the raw parameter w_dev (n_in floats on the device; no host copy of it is needed).
@@ -625,6 +647,17 @@ size_t somi_loss_workspace_bytes(const somi_loss_desc *d);
  * ComputeLoss(autobalance=True) updates its balance with after the call (utils/loss.py:197-201; host state, the kernel only reports). */
 int somi_yolo_loss_f32(const somi_loss_desc *d, float *out8, void *workspace, size_t workspace_bytes,
                        somi_stream_t stream);
+/* Five detection levels (models/hub/yolov5-p7.yaml, Detect over P3..P7): d->nl = 5, levels 0..3 in the descriptor (whose layout stays as it is) and the
+ * fifth in `l5`.  out9 = out8 + obji[4].  Same kernels and the same order of sums as somi_yolo_loss_f32, which keeps serving 1 to 4 levels. */
+typedef struct somi_loss_level {
+    const float *p;
+    float *grad;
+    int32_t ny, nx;
+    float balance;
+} somi_loss_level;
+size_t somi_loss5_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5);
+int somi_yolo_loss5_f32(const somi_loss_desc *d, const somi_loss_level *l5, float *out9, void *workspace, size_t workspace_bytes,
+                        somi_stream_t stream);
 
 /* Repulsion loss, RepGT + RepBox (utils/RepulsionLoss.py:47-95; imported by utils/loss.py:8 but never called by ComputeLoss,
  * so it is an optional term and off by default).  pbox, gtbox: (B,A,4) xyxy; fg_mask: (B,A) bytes (non-zero = foreground).

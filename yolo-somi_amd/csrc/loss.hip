@@ -32,17 +32,32 @@ constexpr int SLOT = 3;
 constexpr float NWD_EPS = 1e-7f, FOCAL_ALPHA = 0.25f;
 
 constexpr int LOSS_FOLD = 64;   // slot segments per level: one workgroup each, so that the finish kernel does not walk ~34000 slots per level alone
+constexpr int MAXL = 5;       // detection levels: the public descriptor carries four, somi_yolo_loss5_f32 hands in a fifth (yolov5-p7, P3..P7)
+// somi_loss_desc with room for MAXL levels (same field names): what the kernels read
+struct LossDescN {
+    const float *p[MAXL];
+    float *grad[MAXL];
+    int32_t ny[MAXL], nx[MAXL];
+    int32_t nl, na, nc, B, nt;
+    const float *targets;
+    const float *anchors;
+    float balance[MAXL];
+    float box_gain, obj_gain, cls_gain, cls_pw, obj_pw, anchor_t, cp, cn, gr;
+    float fl_gamma;
+    int32_t slide;
+    float nwd_ratio, nwd_constant;
+};
 struct LossArgs {
-    somi_loss_desc d;
+    LossDescN d;
     int no;
-    long cells[4];          // B*na*ny*nx per level
-    long cell_off[4];       // prefix of cells (offset into the tobj workspace)
-    int nblk[4];            // dense workgroups per level
-    int blk_off[4];
+    long cells[MAXL];       // B*na*ny*nx per level
+    long cell_off[MAXL];    // prefix of cells (offset into the tobj workspace)
+    int nblk[MAXL];         // dense workgroups per level
+    int blk_off[MAXL];
     unsigned *tobj;         // [sum cells] float bits (>= 0), zeroed
     float *slots;           // [nl][na*nt*NOFF][SLOT] = {box loss or -1 (invalid), cls bce sum, clamp(iou,0,1)}
-    float *auto_iou;        // [4] per level: mean of the entries' clamped IoU (SlideLoss), 0.5 when the level has none
-    int *nent;              // [4] entries per level, zeroed
+    float *auto_iou;        // [MAXL] per level: mean of the entries' clamped IoU (SlideLoss), 0.5 when the level has none
+    int *nent;              // [MAXL] entries per level, zeroed
     int *head;              // [sum cells] last entry pushed onto the cell's list, -1 = none (only with gradients)
     int *next;              // [nl][na*nt*NOFF] list links
     float *partial;         // [sum nblk] obj-BCE partial sums
@@ -149,7 +164,7 @@ struct Triple {
     float gx, gy, gw, gh, aw, ah;
     bool use[NOFF];
 };
-__device__ __forceinline__ Triple load_triple(const somi_loss_desc &d, int l, int an, int t) {
+__device__ __forceinline__ Triple load_triple(const LossDescN &d, int l, int an, int t) {
     Triple r;
     r.nx = d.nx[l];
     r.ny = d.ny[l];
@@ -177,7 +192,7 @@ struct Entry {
     float iou01;            // what goes to the objectness target / SlideLoss mean: clamp(c.v, 0, 1)
     float s0, s1, s2, s3;
 };
-__device__ __forceinline__ Entry eval_entry(const somi_loss_desc &d, int no, const float *pl, const Triple &r, int an, int k) {
+__device__ __forceinline__ Entry eval_entry(const LossDescN &d, int no, const float *pl, const Triple &r, int an, int k) {
     const float offx[NOFF] = {0.f, 0.5f, 0.f, -0.5f, 0.f}, offy[NOFF] = {0.f, 0.f, 0.5f, 0.f, -0.5f};
     int gi = (int)(r.gx - offx[k]), gj = (int)(r.gy - offy[k]);                           // .long(): truncation
     gi = min(max(gi, 0), r.nx - 1);                                                       // clamp_ (also feeds tbox)
@@ -200,7 +215,7 @@ __device__ __forceinline__ Entry eval_entry(const somi_loss_desc &d, int no, con
 }
 
 __global__ __launch_bounds__(256) void loss_match_kernel(const LossArgs a) {
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     const int l = blockIdx.y;
     const int per_level = d.na * d.nt;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(256) void loss_match_kernel(const LossArgs a) {
 // auto_iou = iou.mean() over the level's entries (utils/loss.py:180); 0.5 - SlideLoss's default - for a level without entries (:191-194)
 __global__ __launch_bounds__(256) void loss_level_mean_kernel(const LossArgs a) {
     __shared__ double red[256];
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     const int l = blockIdx.x;
     const int per_level = d.na * d.nt * NOFF;
     const float *sl = a.slots + (size_t)l * per_level * SLOT;
@@ -250,7 +265,7 @@ __global__ __launch_bounds__(256) void loss_level_mean_kernel(const LossArgs a) 
 
 // ------------------------------------------------------------------------------------------------ 1b. gradient of the matched entries
 __global__ __launch_bounds__(256) void loss_scatter_kernel(const LossArgs a) {
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     const int l = blockIdx.y;
     const int per_level = d.na * d.nt;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -313,7 +328,7 @@ __global__ __launch_bounds__(256) void loss_scatter_kernel(const LossArgs a) {
 // ------------------------------------------------------------------------------------------------ 3. dense pass
 __global__ __launch_bounds__(256) void loss_dense_kernel(const LossArgs a, int l) {
     __shared__ float red[4];
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     const float *pl = d.p[l];
     float *gl = d.grad[l];
     const long cells = a.cells[l];
@@ -357,7 +372,7 @@ __global__ __launch_bounds__(256) void loss_dense_kernel(const LossArgs a, int l
 // (fixed order).  Round 4: the finish kernel did this walk alone, one workgroup for every level: 227 us per step.
 __global__ __launch_bounds__(256) void loss_slots_fold_kernel(const LossArgs a) {
     __shared__ double red[2][256];
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     const int l = blockIdx.y, per_level = d.na * d.nt * NOFF;
     const int per = (per_level + LOSS_FOLD - 1) / LOSS_FOLD, i0 = blockIdx.x * per, i1 = min(i0 + per, per_level);
     const float *sl = a.slots + (size_t)l * per_level * SLOT;
@@ -388,7 +403,7 @@ __global__ __launch_bounds__(256) void loss_slots_fold_kernel(const LossArgs a) 
 }
 __global__ __launch_bounds__(256) void loss_finish_kernel(const LossArgs a, float *out4) {
     __shared__ double red[256];
-    const somi_loss_desc &d = a.d;
+    const LossDescN &d = a.d;
     double lbox = 0.0, lobj = 0.0, lcls = 0.0;
     for (int l = 0; l < d.nl; ++l) {
         double so = 0.0;
@@ -425,13 +440,27 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const LossArgs a, floa
 
 static size_t align_up(size_t v, size_t al) { return (v + al - 1) / al * al; }
 
-static int plan(const somi_loss_desc &d, LossArgs &a) {
-    SOMI_REQUIRE(d.nl >= 1 && d.nl <= 4 && d.na >= 1 && d.nc >= 1 && d.B >= 1 && d.nt >= 0, SOMI_EINVAL, "loss: bad sizes");
-    a.d = d;
+static int plan(const somi_loss_desc &pd, const somi_loss_level *l5, LossArgs &a) {
+    SOMI_REQUIRE(pd.nl >= 1 && pd.nl <= (l5 ? MAXL : 4) && (!l5 || pd.nl == MAXL) && pd.na >= 1 && pd.nc >= 1 && pd.B >= 1 && pd.nt >= 0, SOMI_EINVAL,
+                 "loss: bad sizes (1 to 4 levels in the descriptor; a fifth through somi_yolo_loss5_f32 with nl = 5)");
+    LossDescN &d = a.d;
+    for (int l = 0; l < MAXL; ++l) {
+        const bool in = l < 4;
+        d.p[l] = in ? pd.p[l] : (l5 ? l5->p : nullptr);
+        d.grad[l] = in ? pd.grad[l] : (l5 ? l5->grad : nullptr);
+        d.ny[l] = in ? pd.ny[l] : (l5 ? l5->ny : 0);
+        d.nx[l] = in ? pd.nx[l] : (l5 ? l5->nx : 0);
+        d.balance[l] = in ? pd.balance[l] : (l5 ? l5->balance : 0.f);
+    }
+    d.nl = pd.nl; d.na = pd.na; d.nc = pd.nc; d.B = pd.B; d.nt = pd.nt;
+    d.targets = pd.targets; d.anchors = pd.anchors;
+    d.box_gain = pd.box_gain; d.obj_gain = pd.obj_gain; d.cls_gain = pd.cls_gain; d.cls_pw = pd.cls_pw; d.obj_pw = pd.obj_pw;
+    d.anchor_t = pd.anchor_t; d.cp = pd.cp; d.cn = pd.cn; d.gr = pd.gr;
+    d.fl_gamma = pd.fl_gamma; d.slide = pd.slide; d.nwd_ratio = pd.nwd_ratio; d.nwd_constant = pd.nwd_constant;
     a.no = d.nc + 5;
     long off = 0;
     int boff = 0;
-    for (int l = 0; l < 4; ++l) {
+    for (int l = 0; l < MAXL; ++l) {
         a.cells[l] = a.cell_off[l] = 0;
         a.nblk[l] = a.blk_off[l] = 0;
         if (l >= d.nl) continue;
@@ -448,29 +477,20 @@ static int plan(const somi_loss_desc &d, LossArgs &a) {
     return 0;
 }
 
-}  // namespace somi
-
-using namespace somi;
-
-extern "C" size_t somi_loss_workspace_bytes(const somi_loss_desc *d) {
-    LossArgs a;
-    if (!d || plan(*d, a)) return 0;
-    const size_t tobj = align_up((size_t)(a.cell_off[d->nl - 1] + a.cells[d->nl - 1]) * 4, 256);
-    const size_t slots = align_up((size_t)d->nl * d->na * (d->nt > 0 ? d->nt : 1) * NOFF * SLOT * 4, 256);
-    const size_t part = align_up((size_t)(a.blk_off[d->nl - 1] + a.nblk[d->nl - 1]) * 4, 256);
-    const size_t next = align_up((size_t)d->nl * d->na * (d->nt > 0 ? d->nt : 1) * NOFF * 4, 256);
-    return tobj + 256 + slots + part + tobj + next + 4 * LOSS_FOLD * 2 * sizeof(double);      // + the per-cell list heads, the entry links of the gradient pass, the slot-segment sums
+static size_t workspace_bytes_of(const LossArgs &a) {
+    const LossDescN &d = a.d;
+    const size_t tobj = align_up((size_t)(a.cell_off[d.nl - 1] + a.cells[d.nl - 1]) * 4, 256);
+    const size_t slots = align_up((size_t)d.nl * d.na * (d.nt > 0 ? d.nt : 1) * NOFF * SLOT * 4, 256);
+    const size_t part = align_up((size_t)(a.blk_off[d.nl - 1] + a.nblk[d.nl - 1]) * 4, 256);
+    const size_t next = align_up((size_t)d.nl * d.na * (d.nt > 0 ? d.nt : 1) * NOFF * 4, 256);
+    return tobj + 256 + slots + part + tobj + next + MAXL * LOSS_FOLD * 2 * sizeof(double);   // + the per-cell list heads, the entry links of the gradient pass, the slot-segment sums
 }
 
-extern "C" int somi_yolo_loss_f32(const somi_loss_desc *dp, float *out4, void *workspace, size_t workspace_bytes,
-                                  somi_stream_t stream) {
-    SOMI_REQUIRE(dp && out4 && workspace, SOMI_EINVAL, "loss: null argument");
-    LossArgs a;
-    int rc = plan(*dp, a);
-    if (rc) return rc;
-    const somi_loss_desc &d = *dp;
+static int run_loss(const LossArgs &planned, float *out, void *workspace, size_t workspace_bytes, somi_stream_t stream, const char *what) {
+    LossArgs a = planned;
+    const LossDescN &d = a.d;
     SOMI_REQUIRE(d.nt == 0 || (d.targets && d.anchors), SOMI_EINVAL, "loss: targets / anchors missing");
-    SOMI_REQUIRE(workspace_bytes >= somi_loss_workspace_bytes(dp), SOMI_EWORKSPACE, "loss: workspace too small");
+    SOMI_REQUIRE(workspace_bytes >= workspace_bytes_of(a), SOMI_EWORKSPACE, "loss: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     char *w = static_cast<char *>(workspace);
     const size_t tobj_b = align_up((size_t)(a.cell_off[d.nl - 1] + a.cells[d.nl - 1]) * 4, 256);
@@ -499,6 +519,39 @@ extern "C" int somi_yolo_loss_f32(const somi_loss_desc *dp, float *out4, void *w
     }
     for (int l = 0; l < d.nl; ++l) hipLaunchKernelGGL(loss_dense_kernel, dim3(a.nblk[l]), dim3(256), 0, s, a, l);
     if (d.nt > 0) hipLaunchKernelGGL(loss_slots_fold_kernel, dim3(LOSS_FOLD, d.nl), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, a, out4);
-    return launch_status("somi_yolo_loss_f32");
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, a, out);
+    return launch_status(what);
+}
+
+}  // namespace somi
+
+using namespace somi;
+
+extern "C" size_t somi_loss_workspace_bytes(const somi_loss_desc *d) {
+    LossArgs a;
+    if (!d || plan(*d, nullptr, a)) return 0;
+    return workspace_bytes_of(a);
+}
+
+extern "C" int somi_yolo_loss_f32(const somi_loss_desc *dp, float *out8, void *workspace, size_t workspace_bytes, somi_stream_t stream) {
+    SOMI_REQUIRE(dp && out8 && workspace, SOMI_EINVAL, "loss: null argument");
+    LossArgs a;
+    int rc = plan(*dp, nullptr, a);
+    if (rc) return rc;
+    return run_loss(a, out8, workspace, workspace_bytes, stream, "somi_yolo_loss_f32");
+}
+
+extern "C" size_t somi_loss5_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5) {
+    LossArgs a;
+    if (!d || !l5 || plan(*d, l5, a)) return 0;
+    return workspace_bytes_of(a);
+}
+
+extern "C" int somi_yolo_loss5_f32(const somi_loss_desc *dp, const somi_loss_level *l5, float *out9, void *workspace, size_t workspace_bytes,
+                                   somi_stream_t stream) {
+    SOMI_REQUIRE(dp && l5 && out9 && workspace, SOMI_EINVAL, "loss: null argument");
+    LossArgs a;
+    int rc = plan(*dp, l5, a);
+    if (rc) return rc;
+    return run_loss(a, out9, workspace, workspace_bytes, stream, "somi_yolo_loss5_f32");
 }

@@ -36,6 +36,11 @@ class LossDesc(C.Structure):
                 ('fl_gamma', C.c_float), ('slide', C.c_int32), ('nwd_ratio', C.c_float), ('nwd_constant', C.c_float)]
 
 
+class LossLevel(C.Structure):
+    """struct somi_loss_level (include/somi_hip.h): the fifth detection level of somi_yolo_loss5_f32."""
+    _fields_ = [('p', C.c_void_p), ('grad', C.c_void_p), ('ny', C.c_int32), ('nx', C.c_int32), ('balance', C.c_float)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -162,6 +167,12 @@ SIGNATURES = {
     'somi_nms_f32': (I, [P, I, I, I, F, F, I, I, P, I, P, P, P, Z, S]),
     'somi_loss_workspace_bytes': (Z, [C.POINTER(LossDesc)]),
     'somi_yolo_loss_f32': (I, [C.POINTER(LossDesc), P, P, Z, S]),
+    'somi_loss5_workspace_bytes': (Z, [C.POINTER(LossDesc), C.POINTER(LossLevel)]),
+    'somi_yolo_loss5_f32': (I, [C.POINTER(LossDesc), C.POINTER(LossLevel), P, P, Z, S]),
+    'somi_maxpool2_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_maxpool2_bwd_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_val_match_f32': (I, [P, P, P, P, P, I, I, I, I, P, S]),
     'somi_confusion_matrix_f32': (I, [P, P, P, P, I, I, I, I, F, F, P, S]),
     'somi_ap_per_class_workspace_bytes': (Z, [C.c_long, I, I]),

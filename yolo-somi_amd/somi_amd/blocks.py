@@ -1163,21 +1163,255 @@ class C3(nn.Module):
 
 
 class SPP(nn.Module):
-    """models/common.py:1806-1826 with the stock kernel sizes (5, 9, 13): a stride-1 max-pool of window 9 (13) is exactly two (three)
-    chained 5x5 pools, so the three parallel pools are the same single kernel SPPF uses, writing the concat slices; likewise the
-    gradient (every pooled value's gradient ends at the arg-max pixel of its window whichever way it is routed)."""
+    """models/common.py:1806-1826: cv1 -> parallel stride-1 max-pools -> concat -> cv2, the pools writing the concat slices in place.
+
+    Two kernel sets, which differ in how a pooled value's gradient is routed at exact ties:
+    * the stock sizes (5, 9, 13) run on the kernel SPPF uses: a window of 9 (13) is exactly two (three) chained 5x5 pools, so the VALUES are those of
+      the parallel pools, but the gradient walks back through the chain and lands on the first maximum of each 5x5 stage - the same pixel as autograd's
+      for distinct values, not always the same one among equal values;
+    * every other set (1 to 3 ascending odd sizes, each 3 <= k <= 13: yolov5-p6's (3, 5, 7), yolov5-p7's (3, 5)) runs on the parallel-window kernels of
+      pool.hip, which route to the first row-major maximum of the FULL window, as torch's max_pool2d autograd does."""
 
     def __init__(self, c1, c2, k=(5, 9, 13)):
         super().__init__()
-        if tuple(k) != (5, 9, 13):
-            raise NotImplementedError('SPP kernel sizes (5, 9, 13) only')
+        k = tuple(int(v) for v in k)
+        if k != (5, 9, 13) and not (1 <= len(k) <= 3 and all(v % 2 == 1 and 3 <= v <= 13 for v in k) and all(a < b for a, b in zip(k, k[1:]))):
+            raise NotImplementedError(f'SPP kernel sizes {k} are not on the SOMI path: 1 to 3 ascending odd window sizes, each 3 <= k <= 13')
+        self.k = k
         c_ = c1 // 2
         self.cv1 = Conv(c1, c_, 1, 1)
-        self.cv2 = Conv(c_ * 4, c2, 1, 1)
+        self.cv2 = Conv(c_ * (len(k) + 1), c2, 1, 1)
         self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])    # parameter-free; kept for state_dict / repr parity
 
-    forward = SPPF.forward
-    backward = SPPF.backward
+    def forward(self, x):
+        if self.k == (5, 9, 13):
+            return SPPF.forward(self, x)
+        c_ = self.cv1.conv.out_channels
+        if c_ % 4:
+            raise NotImplementedError('SPP hidden width must be a multiple of 4 on the MI355X path')
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, (len(self.k) + 1) * c_)
+        self.cv1(x, out=cat.slice(0, c_))
+        if self.training:
+            self.__dict__['_ctx'] = ops.spp_pool_(cat.t, c_, self.k, 0, codes=True)[1]
+        else:
+            ops.spp_pool_(cat.t, c_, self.k, 0)
+        return self.cv2(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False):
+        if self.k == (5, 9, 13):
+            return SPPF.backward(self, dout, dx_out=dx_out, accumulate=accumulate)
+        codes = self.__dict__.pop('_ctx')
+        c_ = self.cv1.conv.out_channels
+        dcat = self.cv2.backward(dout)
+        ops.spp_pool_backward_(dcat.t, codes, c_, self.k, dcat.coff)
+        return self.cv1.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate)
+
+
+class MaxPool2d(nn.Module):
+    """nn.MaxPool2d(2, s, 0), s 1 or 2 (models/hub/yolov3-tiny.yaml; the reference's generic branch, models/yolo.py:1647-1648: channels pass through).
+    `pad` = (left, right, top, bottom) of a ZeroPad2d in front of it that parse_model folded in: the kernel reads the zero border, no padded copy."""
+
+    def __init__(self, kernel_size, stride=None, padding=0):
+        super().__init__()
+        stride = kernel_size if stride is None else stride
+        if kernel_size != 2 or stride not in (1, 2) or padding != 0:
+            raise NotImplementedError(f'nn.MaxPool2d({kernel_size}, {stride}, {padding}) is not on the SOMI path (kernel 2, stride 1 or 2, padding 0)')
+        self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
+        self.pad = (0, 0, 0, 0)
+
+    def extra_repr(self):
+        return f'kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, zero_pad={self.pad}'
+
+    def forward(self, x):
+        if x.c % 4:
+            raise NotImplementedError('MaxPool2d needs a channel count that is a multiple of 4')
+        B, H, W, _ = x.shape
+        pl, pr, pt, pb = self.pad
+        Ho, Wo = ops.maxpool2_out_size(H, self.stride, pt, pb), ops.maxpool2_out_size(W, self.stride, pl, pr)
+        out = concat_act(x.t, Ho, Wo, x.c)                        # pad channels (if any) zero, like every activation
+        r = ops.maxpool2(x.t, x.c, x.coff, stride=self.stride, pad=self.pad, out=out.t, codes=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (r[1], H, W, x.c)
+        return out
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        codes, H, W, c = self.__dict__.pop('_ctx')
+        if not need_dx:
+            return None
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('MaxPool2d writes its own input gradient')
+        dx = concat_act(dout.t, H, W, c)
+        ops.maxpool2_backward(dout.t, codes, c, H, W, dout.coff, stride=self.stride, pad=self.pad, out=dx.t)
+        return dx
+
+
+class ZeroPad2d(nn.Module):
+    """nn.ZeroPad2d([left, right, top, bottom]) (yolov3-tiny layer 11).  Runs only folded into the MaxPool2d that follows it (parse_model sets that
+    pool's `pad` and marks this layer `folded`): then it hands its input through."""
+
+    def __init__(self, padding):
+        super().__init__()
+        p = (padding,) * 4 if isinstance(padding, int) else tuple(int(v) for v in padding)
+        if len(p) != 4 or any(v not in (0, 1) for v in p):
+            raise NotImplementedError(f'nn.ZeroPad2d({padding}) is not on the SOMI path (four pads of 0 or 1)')
+        self.padding = p
+        self.folded = False
+
+    def extra_repr(self):
+        return f'padding={self.padding}'
+
+    def forward(self, x):
+        if not self.folded:
+            raise NotImplementedError(ZeroPad2d.STRAY)
+        return x
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('ZeroPad2d hands its gradient through')
+        return dout if need_dx else None
+
+    STRAY = 'nn.ZeroPad2d runs only directly in front of an nn.MaxPool2d that is its only reader (folded into the pool kernel)'
+
+
+class Repeat(nn.Sequential):
+    """n > 1 repeats of a module the yaml does not repeat inside itself (models/yolo.py:1650: an nn.Sequential, so the names stay model.<i>.<j>...):
+    forward and backward walk the children."""
+
+    def forward(self, x):
+        for m in self:
+            x = m(x)
+        return x
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        mods = list(self)
+        for j in range(len(mods) - 1, 0, -1):
+            dout = mods[j].backward(dout)
+        kw = {}
+        if dx_out is not None:
+            kw.update(dx_out=dx_out, accumulate=accumulate)
+        if not need_dx:
+            kw['need_dx'] = False
+        return mods[0].backward(dout, **kw)
+
+
+class BottleneckCSP(_Packed):
+    """cv4(silu(bn(cat(cv3(m(cv1(x))), cv2(x))))) (models/common.py:1512-1538); cv2 / cv3 are plain bias-free 1x1 nn.Conv2d, m's bottlenecks 3x3 -> 3x3
+    with e = 1.  No torch.cat: cv3 and cv2 write the two halves of one buffer, and since BatchNorm is per channel, `bn` over the concat is two
+    slices of one BatchNorm.  Eval: each slice folds into its conv, SiLU in the epilogue - two launches for cv3 / cv2 / bn / act.  Training: each conv
+    leaves its BatchNorm partial sums from the conv epilogue, bn_stats_from_partials + the affine/SiLU sweep run per half on slices of bn's
+    parameters and running statistics (in place); backward mirrors it with the BatchNorm/SiLU backward per half and the dense wgrad / dgrad kernels."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = nn.Conv2d(c1, c_, 1, 1, bias=False)
+        self.cv3 = nn.Conv2d(c_, c_, 1, 1, bias=False)
+        self.cv4 = Conv(2 * c_, c2, 1, 1)
+        self.bn = nn.BatchNorm2d(2 * c_)
+        self.act = nn.SiLU()
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
+
+    def _packed(self, dev):
+        own = (self.cv2.weight, self.cv3.weight, self.bn.weight, self.bn.bias)      # the children pack themselves
+        key = (dev, self.training, tuple(p._version for p in own))
+        cache = self.__dict__.get('_pk')
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                cache = (key, self._pack(dev))
+            self.__dict__['_pk'] = cache
+        return cache[1]
+
+    def invalidate(self):
+        self.__dict__.pop('_pk', None)
+
+    def _pack(self, dev):
+        c_ = self.cv3.out_channels
+        if c_ % 4 or pad4(c_) != c_:
+            raise NotImplementedError('BottleneckCSP hidden width must be a multiple of 4 (of 32 from 64 up) on the MI355X path')
+        if not self.training:                                    # the two slices of bn fold into cv3 / cv2
+            s, t = bn_fold(self.bn)
+            return [_pack_wb(conv.weight.detach().float() * s[o:o + c_].view(-1, 1, 1, 1), t[o:o + c_], dev)
+                    for conv, o in ((self.cv3, 0), (self.cv2, c_))]
+        pk = {}
+        for name, conv in (('3', self.cv3), ('2', self.cv2)):
+            w = conv.weight
+            c1p = pad4(conv.in_channels)
+            if c1p == conv.in_channels and w.device == dev and w.dtype == torch.float32 and w.is_contiguous():
+                wp = w.detach().view(c_, c1p)                    # a 1x1 weight without pads IS its forward packing [cout][cin]
+            else:
+                wp = pack_conv_weight(w.detach().float(), cout_pad=c_).to(dev)
+            pk['w' + name], pk['t' + name] = wp, ops.pack_dgrad_weights(wp, c_, 1, c1p)
+        bn = self.bn
+        if bn.weight.device != dev:
+            raise RuntimeError('BottleneckCSP: move the module to the device before a training forward')
+        pk.update(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var)
+        return pk
+
+    def forward(self, x):
+        pk = self._packed(x.t.device)
+        c_ = self.cv3.out_channels
+        B, H, W, _ = x.shape
+        t = self.cv1(x)
+        for blk in self.m:
+            t = blk(t)
+        z = concat_act(x.t, H, W, 2 * c_)
+        if not self.training:
+            for (wp, bp), src, o in ((pk[0], t, 0), (pk[1], x, c_)):
+                ops.conv2d_nhwc(src.t, wp, bp, kh=1, kw=1, stride=1, pad=0, act='silu', cin=pad4(src.c), x_coff=src.coff, out=z.t, cout=c_, y_coff=o,
+                                alg_cin=src.c, alg_cout=c_)
+            return self.cv4(z)
+        y = torch.empty(B, H, W, 2 * c_, device=x.t.device, dtype=torch.float32)     # raw cv3 | cv2 outputs: what bn normalises
+        stats = []
+        for name, src, o in (('3', t, 0), ('2', x, c_)):
+            st = {'pivot': pk['rm'][o:o + c_]}
+            ops.conv2d_nhwc(src.t, pk['w' + name], None, kh=1, kw=1, stride=1, pad=0, act='none', cin=pad4(src.c), x_coff=src.coff, out=y, cout=c_,
+                            y_coff=o, alg_cin=src.c, alg_cout=c_, bn_stats=st)
+            s4 = ops.bn_stats_from_partials(st['part'], st['rows'], B * H * W, c_, pk['gamma'][o:o + c_], pk['beta'][o:o + c_], self.bn.eps,
+                                            self.bn.momentum, pk['rm'][o:o + c_], pk['rv'][o:o + c_])
+            ops.chan_affine_act(y, c_, o, s4[2], s4[3], 'silu', 0, z.t, o)
+            stats.append(s4)
+        with torch.no_grad():
+            _bump_batches_tracked(self.bn)
+        self.__dict__['_ctx'] = (x, t, y, stats, pk)
+        return self.cv4(z)
+
+    def _plain_backward(self, conv, wt, src, dy, o, dx_out, accumulate, need_dx):
+        """Weight gradient of the plain 1x1 `conv` (input src, output gradient dy's slice at o) into .grad; -> its data gradient."""
+        c1, c_ = conv.in_channels, conv.out_channels
+        c1p = pad4(c1)
+        g = conv.weight.grad
+        if c1p == c1 and g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == dy.device:
+            gv = g.view(c_, c1)                                   # the kernel accumulates straight into the gradient (the optimizer's flat view)
+            ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=c_, dy_coff=o, out=gv, accumulate=gv)
+        else:
+            dw = ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=c_, dy_coff=o)
+            _acc_grad(conv.weight, dw.view(c_, 1, 1, c1p)[:, :, :, :c1].permute(0, 3, 1, 2))
+        if not need_dx:
+            return None
+        B, H, W, _ = src.shape
+        if dx_out is None:
+            dx_out = Act(torch.empty(B, H, W, c1p, device=dy.device, dtype=torch.float32), 0, c1)
+        ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1p, kh=1, kw=1, cout=c_, dy_coff=o, out=dx_out.t, dx_coff=dx_out.coff,
+                              accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff)
+        return dx_out
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        x, t, y, stats, pk = self.__dict__.pop('_ctx')
+        c_ = self.cv3.out_channels
+        dz = self.cv4.backward(dout)
+        dy = torch.empty_like(y)
+        (gw, gb), fin = _grad_targets(self.bn.weight, self.bn.bias)
+        for (mean, rstd, scale, shift), o in zip(stats, (0, c_)):
+            ops.bn_act_backward(dz.t, dz.coff + o, y, o, c_, mean, rstd, scale, shift, 'silu', 0, True, dy, o, gw[o:o + c_], gb[o:o + c_])
+        fin()
+        dx = self._plain_backward(self.cv2, pk['t2'], x, dy, c_, dx_out, accumulate, need_dx)
+        d = self._plain_backward(self.cv3, pk['t3'], t, dy, 0, None, False, True)
+        for blk in reversed(self.m):
+            d = blk.backward(d)
+        self.cv1.backward(d, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return dx
 
 
 class Focus(nn.Module):

@@ -162,6 +162,92 @@ def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None):
                 backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
 
 
+YOLOV3_TINY_ANCHORS = [[10, 14, 23, 27, 37, 58], [81, 82, 135, 169, 344, 319]]
+"""The P4 / P5 anchors of models/hub/yolov3-tiny.yaml."""
+
+
+def yolov3_cfg(variant='', width=1.0, depth=1.0, nc=80, anchors=None):
+    """The layer tables of models/hub/yolov3.yaml (variant ''), yolov3-spp.yaml ('spp': SPP(5, 9, 13) in place of the head's first 1x1 Conv) and
+    yolov3-tiny.yaml ('tiny': Conv / nn.MaxPool2d backbone, nn.ZeroPad2d + stride-1 pool, two Detect levels) as dicts.  Defaults are the yamls'
+    (depth 1.0, width 1.0, 80 classes, their own anchors).  The Darknet-53 stages repeat Bottleneck 2 / 8 / 8 / 4 times as nn.Sequentials."""
+    import copy
+    up = [-1, 1, 'nn.Upsample', [None, 2, 'nearest']]
+    if variant == 'tiny':
+        mp = [-1, 1, 'nn.MaxPool2d', [2, 2, 0]]
+        bb = [[-1, 1, 'Conv', [16, 3, 1]], mp, [-1, 1, 'Conv', [32, 3, 1]], mp, [-1, 1, 'Conv', [64, 3, 1]], mp, [-1, 1, 'Conv', [128, 3, 1]], mp,
+              [-1, 1, 'Conv', [256, 3, 1]], mp, [-1, 1, 'Conv', [512, 3, 1]], [-1, 1, 'nn.ZeroPad2d', [[0, 1, 0, 1]]],
+              [-1, 1, 'nn.MaxPool2d', [2, 1, 0]]]
+        hd = [[-1, 1, 'Conv', [1024, 3, 1]], [-1, 1, 'Conv', [256, 1, 1]], [-1, 1, 'Conv', [512, 3, 1]], [-2, 1, 'Conv', [128, 1, 1]], up,
+              [[-1, 8], 1, 'Concat', [1]], [-1, 1, 'Conv', [256, 3, 1]], [[19, 15], 1, 'Detect', ['nc', 'anchors']]]
+        default = YOLOV3_TINY_ANCHORS
+    elif variant in ('', 'spp'):
+        bb = [[-1, 1, 'Conv', [32, 3, 1]], [-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Bottleneck', [64]], [-1, 1, 'Conv', [128, 3, 2]],
+              [-1, 2, 'Bottleneck', [128]], [-1, 1, 'Conv', [256, 3, 2]], [-1, 8, 'Bottleneck', [256]], [-1, 1, 'Conv', [512, 3, 2]],
+              [-1, 8, 'Bottleneck', [512]], [-1, 1, 'Conv', [1024, 3, 2]], [-1, 4, 'Bottleneck', [1024]]]
+        second = [-1, 1, 'SPP', [512, [5, 9, 13]]] if variant == 'spp' else [-1, 1, 'Conv', [512, [1, 1]]]
+        hd = [[-1, 1, 'Bottleneck', [1024, False]], second, [-1, 1, 'Conv', [1024, 3, 1]], [-1, 1, 'Conv', [512, 1, 1]],
+              [-1, 1, 'Conv', [1024, 3, 1]], [-2, 1, 'Conv', [256, 1, 1]], up, [[-1, 8], 1, 'Concat', [1]],
+              [-1, 1, 'Bottleneck', [512, False]], [-1, 1, 'Bottleneck', [512, False]], [-1, 1, 'Conv', [256, 1, 1]],
+              [-1, 1, 'Conv', [512, 3, 1]], [-2, 1, 'Conv', [128, 1, 1]], up, [[-1, 6], 1, 'Concat', [1]],
+              [-1, 1, 'Bottleneck', [256, False]], [-1, 2, 'Bottleneck', [256, False]], [[27, 22, 15], 1, 'Detect', ['nc', 'anchors']]]
+        default = COCO_ANCHORS
+    else:
+        raise ValueError(f"yolov3_cfg: variant {variant!r} (one of '', 'spp', 'tiny')")
+    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(default if anchors is None else anchors),
+                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+
+
+def yolov5_hub_cfg(name, width=1.0, depth=1.0, nc=80, anchors=None):
+    """The layer tables of models/hub/yolov5-fpn.yaml ('fpn': Bottleneck x3 as an nn.Sequential, BottleneckCSP, top-down head only),
+    yolov5-panet.yaml ('panet': BottleneckCSP everywhere), yolov5-p6.yaml ('p6': C3, SPP(3, 5, 7), Detect over P3..P6) and yolov5-p7.yaml ('p7': C3,
+    SPP(3, 5), Detect over P3..P7) as dicts.  Defaults are the yamls' (depth 1.0, width 1.0, 80 classes; the COCO anchors for fpn / panet, and for
+    p6 / p7 the yamls' `anchors: 3`, a placeholder of list(range(6)) per level that only makes sense after autoanchor - pass real ones)."""
+    import copy
+    up = [-1, 1, 'nn.Upsample', [None, 2, 'nearest']]
+
+    def cat(j):
+        return [[-1, j], 1, 'Concat', [1]]
+    if name == 'fpn':
+        bb = [[-1, 1, 'Focus', [64, 3]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'Bottleneck', [128]], [-1, 1, 'Conv', [256, 3, 2]],
+              [-1, 9, 'BottleneckCSP', [256]], [-1, 1, 'Conv', [512, 3, 2]], [-1, 9, 'BottleneckCSP', [512]], [-1, 1, 'Conv', [1024, 3, 2]],
+              [-1, 1, 'SPP', [1024, [5, 9, 13]]], [-1, 6, 'BottleneckCSP', [1024]]]
+        hd = [[-1, 3, 'BottleneckCSP', [1024, False]], up, cat(6), [-1, 1, 'Conv', [512, 1, 1]], [-1, 3, 'BottleneckCSP', [512, False]],
+              up, cat(4), [-1, 1, 'Conv', [256, 1, 1]], [-1, 3, 'BottleneckCSP', [256, False]], [[18, 14, 10], 1, 'Detect', ['nc', 'anchors']]]
+        default = COCO_ANCHORS
+    elif name == 'panet':
+        bb = [[-1, 1, 'Focus', [64, 3]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'BottleneckCSP', [128]], [-1, 1, 'Conv', [256, 3, 2]],
+              [-1, 9, 'BottleneckCSP', [256]], [-1, 1, 'Conv', [512, 3, 2]], [-1, 9, 'BottleneckCSP', [512]], [-1, 1, 'Conv', [1024, 3, 2]],
+              [-1, 1, 'SPP', [1024, [5, 9, 13]]], [-1, 3, 'BottleneckCSP', [1024, False]]]
+        hd = [[-1, 1, 'Conv', [512, 1, 1]], up, cat(6), [-1, 3, 'BottleneckCSP', [512, False]],
+              [-1, 1, 'Conv', [256, 1, 1]], up, cat(4), [-1, 3, 'BottleneckCSP', [256, False]],
+              [-1, 1, 'Conv', [256, 3, 2]], cat(14), [-1, 3, 'BottleneckCSP', [512, False]],
+              [-1, 1, 'Conv', [512, 3, 2]], cat(10), [-1, 3, 'BottleneckCSP', [1024, False]], [[17, 20, 23], 1, 'Detect', ['nc', 'anchors']]]
+        default = COCO_ANCHORS
+    elif name in ('p6', 'p7'):
+        wide = [128, 256, 512, 768, 1024] + ([1280] if name == 'p7' else [])       # P2 .. P6 / P7
+        reps = [3, 9, 9, 3] + ([3] if name == 'p7' else [])
+        bb = [[-1, 1, 'Focus', [64, 3]]]
+        for c, n in zip(wide[:-1], reps):
+            bb += [[-1, 1, 'Conv', [c, 3, 2]], [-1, n, 'C3', [c]]]
+        bb += [[-1, 1, 'Conv', [wide[-1], 3, 2]], [-1, 1, 'SPP', [wide[-1], [3, 5, 7] if name == 'p6' else [3, 5]]],
+               [-1, 3, 'C3', [wide[-1], False]]]
+        nb, hd = len(bb), []
+        lateral = []                                              # indices of the top-down 1x1 Convs, coarsest first
+        for j, c in enumerate(reversed(wide[1:-1])):              # top-down: 1x1, upsample, cat the backbone level below, C3
+            lateral.append(nb + len(hd))
+            hd += [[-1, 1, 'Conv', [c, 1, 1]], up, cat(nb - 3 - 2 * j - 1), [-1, 3, 'C3', [c, False]]]
+        outs = [nb + len(hd) - 1]
+        for c, nxt, lat in zip(wide[1:-1], wide[2:], reversed(lateral)):            # bottom-up: 3x3 / 2, cat the lateral, C3
+            hd += [[-1, 1, 'Conv', [c, 3, 2]], cat(lat), [-1, 3, 'C3', [nxt, False]]]
+            outs.append(nb + len(hd) - 1)
+        hd.append([outs, 1, 'Detect', ['nc', 'anchors']])
+        default = 3
+    else:
+        raise ValueError(f"yolov5_hub_cfg: name {name!r} (one of 'fpn', 'panet', 'p6', 'p7')")
+    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(default if anchors is None else anchors),
+                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+
+
 def tiny_somi_cfg(nc=10):
     """A cut-down graph that uses every module class of the SOMI yaml once (Conv, ODConv_3rd, C2fCBAM, SPPF, nn.Upsample, BiFPN, SEAM,
     DecoupledDetect) at 32 / 64 channels, two detection levels: ~0.2 M parameters - for fixtures that carry whole pickled models."""

@@ -12,7 +12,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import LossDesc, check
+from ._lib import LossDesc, LossLevel, check
 from .ops import _ptr, _stream
 
 
@@ -44,8 +44,8 @@ class ComputeLoss:
         self.gr, self.hyp, self.autobalance = 1.0, h, autobalance
         self.ssi = list(det.stride).index(16) if autobalance else 0                           # stride 16 index (:137)
         self.na, self.nc, self.nl, self.anchors = det.na, det.nc, det.nl, det.anchors
-        if self.nl > 4:
-            raise NotImplementedError('at most 4 detection levels')
+        if self.nl > 5:
+            raise NotImplementedError(f'at most 5 detection levels, got {self.nl}')
         self._anc = None
 
     def _anchors(self, dev):
@@ -54,21 +54,24 @@ class ComputeLoss:
         return self._anc
 
     def _launch(self, p, targets, need_grad):
-        d = LossDesc()
+        d, l5 = LossDesc(), LossLevel()                           # the descriptor holds four levels; a fifth (yolov5-p7) travels beside it
         grads = []
         for i, t in enumerate(p):
             if t.dtype != torch.float32 or not t.is_cuda:
                 raise RuntimeError('prediction tensors have to be float32 on the GPU (no CPU fallback)')
-            d.p[i] = _ptr(t)
             g = torch.empty_like(t) if need_grad else None
             grads.append(g)
+            if i == 4:
+                l5.p, l5.grad, l5.ny, l5.nx, l5.balance = _ptr(t), _ptr(g), t.shape[2], t.shape[3], self.balance[4]
+                continue
+            d.p[i] = _ptr(t)
             d.grad[i] = _ptr(g)
             d.ny[i], d.nx[i] = t.shape[2], t.shape[3]
         dev = p[0].device
         tg = targets.detach().to(dev).float().contiguous()
         d.nl, d.na, d.nc, d.B, d.nt = len(p), self.na, self.nc, p[0].shape[0], tg.shape[0]
         d.targets, d.anchors = (_ptr(tg) if tg.numel() else None), _ptr(self._anchors(dev))
-        for i in range(len(p)):
+        for i in range(min(len(p), 4)):
             d.balance[i] = self.balance[i]
         h = self.hyp
         d.box_gain, d.obj_gain, d.cls_gain = float(h['box']), float(h['obj']), float(h['cls'])
@@ -78,10 +81,14 @@ class ComputeLoss:
         d.nwd_ratio = 0.5 if h['nwdloss'] > 0 else 0.0           # iou_ratio, utils/loss.py:148
         d.nwd_constant = 2.5 if h.get('shapeloss', 0) > 0 else 12.8   # wasserstein (utils/metrics.py:373) / wasserstein_loss (:341), :163-166
         L = _lib.lib()
-        nbytes = L.somi_loss_workspace_bytes(C.byref(d))
+        five = len(p) == 5
+        nbytes = L.somi_loss5_workspace_bytes(C.byref(d), C.byref(l5)) if five else L.somi_loss_workspace_bytes(C.byref(d))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        out = torch.empty(8, dtype=torch.float32, device=dev)
-        check(L.somi_yolo_loss_f32(C.byref(d), _ptr(out), _ptr(ws), nbytes, _stream()), 'ComputeLoss')
+        out = torch.empty(9 if five else 8, dtype=torch.float32, device=dev)
+        if five:
+            check(L.somi_yolo_loss5_f32(C.byref(d), C.byref(l5), _ptr(out), _ptr(ws), nbytes, _stream()), 'ComputeLoss')
+        else:
+            check(L.somi_yolo_loss_f32(C.byref(d), _ptr(out), _ptr(ws), nbytes, _stream()), 'ComputeLoss')
         if self.autobalance:                                      # utils/loss.py:197-201 (a host sync per call, like the reference's .item())
             obji = out[4:4 + len(p)].tolist()
             bal = [self.balance[i] * 0.9999 + 0.0001 / obji[i] for i in range(len(p))] + list(self.balance[len(p):])

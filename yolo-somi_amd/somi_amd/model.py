@@ -5,8 +5,9 @@ Same constructor (`Model(cfg, ch=3, nc=None, anchors=None)`), same attributes ca
 raw_l = (B,na,ny,nx,no).  Input is the reference's `(B,3,H,W)` NCHW batch, either float32 already divided by 255
 (train.py:249) or uint8 (the /255 then happens in the ingest kernel).  Accepted module names: the SOMI set of SURVEY.md
 section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, Concat, Detect - BASELINE configs[0]) and the Ghost set
-of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv) and the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
-C2fCIB, PSA).
+of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv), the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
+C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny, yolov5-fpn / -panet / -p6 / -p7): BottleneckCSP,
+nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels.
 """
 import math
 from copy import deepcopy
@@ -25,8 +26,10 @@ def make_divisible(x, divisor):
 
 _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bottleneck': B.Bottleneck, 'C3': B.C3, 'SPP': B.SPP,
        'Focus': B.Focus, 'GhostConv': B.GhostConv, 'GhostBottleneck': B.GhostBottleneck, 'DWConv': B.DWConv,
-       'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA}   # models/yolo.py:1472-1479
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB')  # models/yolo.py:1487-1492
+       'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA,
+       'BottleneckCSP': B.BottleneckCSP}                          # models/yolo.py:1472-1479
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP')  # models/yolo.py:1487-1492
+_PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
 
 
@@ -62,6 +65,9 @@ def parse_model(d, ch):
         elif name == 'nn.Upsample':
             m = B.Upsample
             c2 = ch[f]
+        elif name in _PASS_THROUGH:                               # parameter-free, channels pass through
+            m = _PASS_THROUGH[name]
+            c2 = ch[f]
         elif name == 'DCNv3_YOLO':                                # the reference's generic branch (models/yolo.py:1647-1648): channels pass through
             m = B.DCNv3_YOLO
             c2 = ch[f]
@@ -76,9 +82,11 @@ def parse_model(d, ch):
                 args[1] = [list(range(args[1] * 2))] * len(f)
         else:
             raise NotImplementedError(f'module {name!r} is outside the SOMI hot path (SURVEY.md section 8a)')
-        if n > 1:
-            raise NotImplementedError(f'{n} repeats of {name!r} as an nn.Sequential are not on the path (no shipped or stock graph has them)')
-        m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        if n > 1 and (name not in _CH or isinstance(f, (list, tuple))):
+            raise NotImplementedError(f'{n} repeats of {name!r} as an nn.Sequential are not on the path (single-input (c1, c2, ...) modules only)')
+        if name in ('DecoupledDetect', 'Detect') and len(f) > 5:
+            raise NotImplementedError(f'at most 5 detection levels, got {len(f)}')
+        m_ = B.Repeat(*(m(*args) for _ in range(n))) if n > 1 else m(*args)                 # models/yolo.py:1650
         m_.i, m_.f, m_.type = i, f, name
         m_.np = sum(p.numel() for p in m_.parameters())
         save.extend(x % i for x in ([f] if isinstance(f, int) else f) if x != -1)
@@ -86,6 +94,12 @@ def parse_model(d, ch):
         if i == 0:
             ch = []
         ch.append(c2)
+    for i, m_ in enumerate(layers):                               # a ZeroPad2d runs folded into the MaxPool2d behind it, or not at all
+        if isinstance(m_, B.ZeroPad2d):
+            nxt = layers[i + 1] if i + 1 < len(layers) else None
+            if not isinstance(nxt, B.MaxPool2d) or nxt.f != -1 or i in save:
+                raise NotImplementedError(f'layer {i}: {B.ZeroPad2d.STRAY}')
+            nxt.pad, m_.folded = m_.padding, True
     return nn.Sequential(*layers), sorted(save)
 
 
@@ -135,22 +149,32 @@ class Model(nn.Module):
         for m in self.model:
             src = m.f if isinstance(m.f, int) else m.f[0]
             r = 1.0 if m.i == 0 else (red[m.i - 1] if src == -1 else red[src])
-            if isinstance(m, B.Conv):                             # DWConv too
-                r *= m.conv.stride[0]
-            elif isinstance(m, B.GhostConv):
-                r *= m.cv1.conv.stride[0]
-            elif isinstance(m, B.GhostBottleneck):
-                r *= m.stride
-            elif isinstance(m, B.SCDown):
-                r *= m.cv2.conv.stride[0]
-            elif isinstance(m, B.Focus):
-                r *= 2 * m.conv.conv.stride[0]
-            elif isinstance(m, B.ODConv_3rd):
-                r *= m.conv.stride
-            elif isinstance(m, B.Upsample):
-                r /= 2
+            r *= self._reduction(m)
             red.append(r)
         return [float(red[j]) for j in self.model[-1].f]
+
+    @staticmethod
+    def _reduction(m):
+        """Factor by which a layer shrinks its input map (1 / 2 for the upsample)."""
+        if isinstance(m, B.Conv):                                 # DWConv too
+            return m.conv.stride[0]
+        if isinstance(m, B.GhostConv):
+            return m.cv1.conv.stride[0]
+        if isinstance(m, B.GhostBottleneck):
+            return m.stride
+        if isinstance(m, B.SCDown):
+            return m.cv2.conv.stride[0]
+        if isinstance(m, B.Focus):
+            return 2 * m.conv.conv.stride[0]
+        if isinstance(m, B.ODConv_3rd):
+            return m.conv.stride
+        if isinstance(m, B.Upsample):
+            return 0.5
+        if isinstance(m, B.MaxPool2d):                            # stride 2 halves the map; yolov3-tiny's padded stride-1 pool keeps it
+            return m.stride
+        if isinstance(m, B.Repeat):
+            return math.prod(Model._reduction(sub) for sub in m)
+        return 1
 
     @staticmethod
     def _check_anchor_order(m):
@@ -232,7 +256,7 @@ class Model(nn.Module):
     # ---------------------------------------------------------------------------------------------- training
     def _sources(self, m):
         f = m.f if isinstance(m.f, (list, tuple)) else [m.f]
-        return [m.i - 1 if j == -1 else j for j in f]
+        return [m.i + j if j < 0 else j for j in f]                 # -1 the previous layer, -2 the one before (yolov3's heads)
 
     def _backward_walk(self, draws):
         """Reverse walk of the layer graph (the autograd of models/yolo.py:1269-1290 done by hand): `draws` are the gradients
@@ -277,7 +301,7 @@ class Model(nn.Module):
                 have = grads.get(srcs[0])
                 kw = {'pooled': pend} if pend is not None else {}
                 if (have is not None and isinstance(m, (B.Conv, B.C2fCBAM, B.C3, B.SPPF, B.SPP, B.ODConv_3rd, B.GhostConv, B.GhostBottleneck,
-                                                                B.C2f, B.SCDown, B.PSA)) and
+                                                                B.C2f, B.SCDown, B.PSA, B.BottleneckCSP)) and
                         have.coff == 0 and
                         have.t.shape[3] == B.pad4(have.c) and have.t.is_contiguous() and have.pooled is None and
                         (not isinstance(m, B.ODConv_3rd) or have.t.shape[3] == have.c)):

@@ -326,6 +326,65 @@ def sppf_pool_(buf, c, x_coff=0, codes=False):
     return buf
 
 
+def maxpool2_out_size(size, stride, pad0, pad1):
+    """Floor-mode output size of a 2-wide window over a map padded by (pad0, pad1)."""
+    return (size + pad0 + pad1 - 2) // stride + 1
+
+
+def maxpool2(x, c, x_coff=0, *, stride=2, pad=(0, 0, 0, 0), out=None, y_coff=0, codes=False):
+    """nn.MaxPool2d(2, stride, 0) of slice [x_coff, x_coff + c) of x (B,H,W,cs) over a ZERO pad (left, right, top, bottom) folded into the read
+    -> out (B,Ho,Wo,*) slice at y_coff.  codes=True (training): -> (out, codes), one byte per pooled element for maxpool2_backward."""
+    B, H, W, _ = x.shape
+    pl, pr, pt, pb = (int(v) for v in pad)
+    Ho, Wo = maxpool2_out_size(H, stride, pt, pb), maxpool2_out_size(W, stride, pl, pr)
+    if out is None:
+        out = torch.empty(B, max(Ho, 0), max(Wo, 0), c, device=x.device, dtype=torch.float32)
+    if Ho < 1 or Wo < 1 or tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise RuntimeError(f'maxpool2: output must be ({B}, {Ho}, {Wo}, .) with both sizes >= 1, got {tuple(out.shape)}')
+    arg = torch.empty(B * Ho * Wo * c, device=x.device, dtype=torch.uint8) if codes else None
+    check(_lib.lib().somi_maxpool2_nhwc_f32(_ptr(_f32c(x)), _ptr(_f32c(out)), _ptr(arg), B, H, W, c, x.shape[3], x_coff, out.shape[3], y_coff,
+                                            int(stride), pl, pr, pt, pb, _stream()), 'maxpool2')
+    return (out, arg) if codes else out
+
+
+def maxpool2_backward(dy, codes, c, H, W, dy_coff=0, *, stride=2, pad=(0, 0, 0, 0), out=None, dx_coff=0):
+    """dx (B,H,W,*) slice at dx_coff = the gradient of maxpool2's input, written (not added): every element gathers the outputs whose code points at it."""
+    B = dy.shape[0]
+    pl, pr, pt, pb = (int(v) for v in pad)
+    if out is None:
+        out = torch.empty(B, H, W, c, device=dy.device, dtype=torch.float32)
+    Ho, Wo = maxpool2_out_size(H, stride, pt, pb), maxpool2_out_size(W, stride, pl, pr)
+    if tuple(dy.shape[:3]) != (B, Ho, Wo) or tuple(out.shape[:3]) != (B, H, W) or codes.dtype != torch.uint8 or codes.numel() != B * Ho * Wo * c:
+        raise RuntimeError(f'maxpool2_backward: dy must be ({B}, {Ho}, {Wo}, .), dx ({B}, {H}, {W}, .), codes {B * Ho * Wo * c} bytes')
+    check(_lib.lib().somi_maxpool2_bwd_nhwc_f32(_ptr(_f32c(dy)), _ptr(codes), _ptr(_f32c(out)), B, H, W, c, dy.shape[3], dy_coff, out.shape[3], dx_coff,
+                                                int(stride), pl, pr, pt, pb, _stream()), 'maxpool2_backward')
+    return out
+
+
+def _spp_k(k):
+    k = [int(v) for v in k]
+    return [len(k)] + (k + [0, 0, 0])[:3]
+
+
+def spp_pool_(buf, c, k, x_coff=0, codes=False):
+    """The parallel stride-1 max-pools of slice [x_coff, x_coff + c), one per window size in `k` (ascending odd sizes 3..13, at most 3), into the next
+    len(k) slices of `buf`, in one pass.  codes=True (training): -> (buf, codes) with the first row-major maximum of every full window, for
+    spp_pool_backward_."""
+    B, H, W, cs = buf.shape
+    arg = torch.empty(len(k) * B * H * W * c, device=buf.device, dtype=torch.uint8) if codes else None
+    check(_lib.lib().somi_spp_pool_nhwc_f32(_ptr(_f32c(buf)), _ptr(arg), B, H, W, c, cs, x_coff, *_spp_k(k), _stream()), 'spp_pool')
+    return (buf, arg) if codes else buf
+
+
+def spp_pool_backward_(dbuf, codes, c, k, x_coff=0):
+    """Slice [x_coff, x_coff + c) of dbuf += the gradients of the len(k) pooled slices behind it, routed by spp_pool_'s codes."""
+    B, H, W, cs = dbuf.shape
+    if codes.dtype != torch.uint8 or codes.numel() != len(k) * B * H * W * c:
+        raise RuntimeError(f'spp_pool_backward_: codes must be the {len(k) * B * H * W * c} bytes spp_pool_(codes=True) returned')
+    check(_lib.lib().somi_spp_pool_bwd_nhwc_f32(_ptr(codes), _ptr(_f32c(dbuf)), B, H, W, c, cs, x_coff, *_spp_k(k), _stream()), 'spp_pool_backward')
+    return dbuf
+
+
 def bifpn(srcs, ups, w_dev, eps=1e-4, out=None):
     """y = sum_i w_i / (sum_j swish(w_j) + eps) * src_i; `w_dev` is the raw fusion parameter on the device."""
     n = len(srcs)
