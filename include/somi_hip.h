@@ -754,6 +754,34 @@ typedef struct somi_aug_sample {
 
 int somi_augment_u8(const somi_aug_sample *samples, int B, int H, int W, int fill, uint8_t *out, somi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AutoAnchor (utils/autoanchor.py): anchor metric, genetic evolution and the Lloyd step of scipy.cluster.vq.kmeans.
+ * wh: (n, 2) fp32 label sizes in pixels; anchors: (na, 2) fp32, na <= 64; thr is the reference's 1 / anchor_t.
+ * metric: x = min(w/kw, kw/w, h/kh, kh/h) in fp32 with IEEE division, best = max over the anchors (written to `best`
+ *   when it is not NULL); out[0] = labels with best > thr, out[1] = (label, anchor) pairs with x > thr, out[2] = sum of
+ *   best over the labels with best > thr.  The sums are fp64 and EXACT for thr >= 1/8 and n < 2^27 (every term is a
+ *   multiple of 2^-26), hence independent of the launch shape.
+ * evolve: generations 0..gen-1 one after the other, all enqueued by one call and with no host round trip: candidate
+ *   kg = max(k * v[g], 2.0) in fp64 (v: (gen, na, 2) fp64 mutation factors), rounded to fp32 for the metric; if its
+ *   fitness sum (out[2] above) is > *fitness then k <- kg, *fitness <- that sum and g is appended to `accepted`
+ *   (int32, gen + 1 entries: [0] = count - zero it before the first call - then the generations).  *fitness holds the sum
+ *   of the start k on entry.
+ * kmeans lloyd step: one iteration of _kmeans for `restarts` independent code books at once, fp64.  book (restarts, k, 2),
+ *   alive (restarts, k) int32 (1 = the code is still in the book; codes that end an iteration without members leave it),
+ *   dist (restarts) = mean Euclidean distance of the assignment before the move (set it to +inf before the first step),
+ *   done (restarts) int32 is raised when |previous dist - dist| <= thresh and freezes that restart, iters counts the
+ *   steps a restart took.  k <= 32.  The caller reads `done` between steps; nothing else leaves the device.
+ * Workspaces hold per-block partial sums; every fold has a fixed order, no float atomics. */
+size_t somi_anchor_metric_workspace_bytes(long n);
+int somi_anchor_metric_f32(const float *wh, long n, const float *anchors, int na, float thr, float *best, double *out,
+                           void *workspace, size_t workspace_bytes, somi_stream_t stream);
+int somi_anchor_evolve_f32(const float *wh, long n, double *k, int na, const double *v, int gen, float thr, double *fitness,
+                           int32_t *accepted, void *workspace, size_t workspace_bytes, somi_stream_t stream);
+size_t somi_kmeans_workspace_bytes(long n, int k, int restarts);
+int somi_kmeans_lloyd_step_f64(const double *obs, long n, double *book, int32_t *alive, int k, int restarts, double thresh,
+                               double *dist, int32_t *done, int32_t *iters, void *workspace, size_t workspace_bytes,
+                               somi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

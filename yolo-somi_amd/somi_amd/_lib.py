@@ -184,6 +184,11 @@ SIGNATURES = {
     'somi_wbf_f32': (I, [P, P, P, P, I, I, C.POINTER(C.c_float), F, F, P, P, P, P, P, Z, S]),
     'somi_wbf_batch_workspace_bytes': (Z, [I, I, I]),
     'somi_wbf_batch_f32': (I, [C.POINTER(P), C.POINTER(P), I, I, I, C.POINTER(C.c_float), F, F, F, F, P, P, P, P, P, Z, S]),
+    'somi_anchor_metric_workspace_bytes': (Z, [C.c_long]),
+    'somi_anchor_metric_f32': (I, [P, C.c_long, P, I, F, P, P, P, Z, S]),
+    'somi_anchor_evolve_f32': (I, [P, C.c_long, P, I, P, I, F, P, P, P, Z, S]),
+    'somi_kmeans_workspace_bytes': (Z, [C.c_long, I, I]),
+    'somi_kmeans_lloyd_step_f64': (I, [P, C.c_long, P, P, I, I, C.c_double, P, P, P, P, Z, S]),
 }
 
 _lib = None

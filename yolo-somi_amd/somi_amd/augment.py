@@ -137,12 +137,15 @@ class DeviceImageCache:
         self.batch_index = np.floor(np.arange(self.n) / batch_size).astype(int)                # datasets.py:477-479
         self.order = np.arange(self.n)                                                    # position -> index into `imgs` as given
         self.img_files = list(img_files) if img_files is not None else list(range(self.n))
+        # original (width, height) per image like `LoadImagesAndLabels.shapes` (datasets.py:455): what autoanchor scales the labels by
+        self.shapes = np.array([(im.shape[1], im.shape[0]) for im in imgs] if shapes is None else shapes, dtype=np.float64).reshape(-1, 2)
         if self.rect:
             wh = np.array([(im.shape[1], im.shape[0]) for im in imgs] if shapes is None else shapes,
                           dtype=np.float64)
             self.order, self.batch_shapes = rect_batch_shapes(wh, self.batch_index, self.img_size, stride, pad)
             imgs = [imgs[i] for i in self.order]
             self.labels = [self.labels[i] for i in self.order]
+            self.shapes = self.shapes[self.order]
             self.img_files = [self.img_files[i] for i in self.order]
         self.img_hw, offsets, total = [], [], 0
         arrs = []

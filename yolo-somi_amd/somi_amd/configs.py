@@ -146,7 +146,8 @@ def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
 def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None):
     """The layer table of models/hub/yolov10.yaml as a dict: Conv / C2f / SCDown backbone, C2fCIB at P5, SPPF, PSA, a C2f / C2fCIB PAN head
     and the plain Detect.  Defaults are the yaml's (depth 1.0, width 1.0, 10 classes).  anchors=None gives the COCO anchors: the yaml's
-    `anchors: 3` is a placeholder (list(range(6)) per level) that only makes sense after autoanchor; anchors=3 reproduces the yaml exactly."""
+    `anchors: 3` is a placeholder (list(range(6)) per level) that only makes sense after autoanchor; anchors=3 reproduces the yaml exactly -
+    `somi_amd.autoanchor.check_anchors(dataset, model)` then replaces the placeholder from the data set's labels."""
     import copy
     bb = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'C2f', [128, True]], [-1, 1, 'Conv', [256, 3, 2]],
           [-1, 6, 'C2f', [256, True]], [-1, 1, 'SCDown', [512, 3, 2]], [-1, 6, 'C2f', [512, True]], [-1, 1, 'SCDown', [1024, 3, 2]],
@@ -201,7 +202,8 @@ def yolov5_hub_cfg(name, width=1.0, depth=1.0, nc=80, anchors=None):
     """The layer tables of models/hub/yolov5-fpn.yaml ('fpn': Bottleneck x3 as an nn.Sequential, BottleneckCSP, top-down head only),
     yolov5-panet.yaml ('panet': BottleneckCSP everywhere), yolov5-p6.yaml ('p6': C3, SPP(3, 5, 7), Detect over P3..P6) and yolov5-p7.yaml ('p7': C3,
     SPP(3, 5), Detect over P3..P7) as dicts.  Defaults are the yamls' (depth 1.0, width 1.0, 80 classes; the COCO anchors for fpn / panet, and for
-    p6 / p7 the yamls' `anchors: 3`, a placeholder of list(range(6)) per level that only makes sense after autoanchor - pass real ones)."""
+    p6 / p7 the yamls' `anchors: 3`, a placeholder of list(range(6)) per level that only makes sense after autoanchor - pass real ones, or run
+    `somi_amd.autoanchor.check_anchors(dataset, model)` on the built model)."""
     import copy
     up = [-1, 1, 'nn.Upsample', [None, 2, 'nearest']]
 
