@@ -5,9 +5,10 @@ oracle block, the fp32 CPU oracle block (`oracle_alone`) and the HIP block (`hip
 bit-identical inputs, output gradients and weights for all three - so whatever a block shows there is error it generates itself."""
 import torch
 
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
+try:
+    from parity import nhwc                                       # the tests import this module with tests/ on sys.path
+except ImportError:
+    from tests.parity import nhwc                                 # tools/ import it as tests.isolate
 
 
 def capture(model64, run, layers=None):

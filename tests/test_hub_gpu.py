@@ -3,7 +3,6 @@ against torch's max_pool2d and its autograd on the CPU in fp64, the new blocks a
 (tests/hub_ref.py), the five-level loss against the oracle loss, whole graphs against the oracle Model.  Bars: selection (values, arg-max
 codes) exact; pool gradients n roundings of the sum of their terms' magnitudes, n the number of terms; blocks and graphs 1e-3 relative (BASELINE)."""
 import copy
-import io
 
 import pytest
 import torch
@@ -11,33 +10,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import hub_ref as R
+from parity import (check_block, check_checkpoint_roundtrip, check_eval, check_train_step, check_two_steps_bit_identical, nchw, nhwc,
+                    rel_close)
 
 pytestmark = pytest.mark.gpu
-
-
-def rel_close(got, want, rel=1e-3, what='', atol=0.0):
-    got, want = got.detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert torch.isfinite(got).all(), f'{what}: not finite'
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    print(f'{what}: max err {err:.3e}, scale {scale:.3e}')
-    assert err <= rel * scale + atol, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def _bn_hyper(mod):
-    for m in mod.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    return mod
 
 
 def _tie_map(B, H, W, C, gen, kind):
@@ -229,38 +205,8 @@ BLOCKS = {'csp_sc': (lambda M: M.BottleneckCSP(32, 32, 1, True), (2, 32, 9, 11),
 def test_hub_blocks_eval_train_backward(tag):
     """Eval forward (BatchNorm folded), training forward, hand-written backward against torch autograd on the CPU restatement: output,
     dx, every parameter gradient (BatchNorm's included) and the updated running statistics."""
-    from oracle.somi_ref import blocks as OB
-    from oracle.somi_ref.testing import fill_state
-    from somi_amd import blocks as MB
     mk, shape, shift = BLOCKS[tag]
-    ref, mine = mk(R), mk(MB)
-    fill_state(ref, 5)
-    OB.initialize_weights(ref)
-    mine.load_state_dict(ref.state_dict())
-    mine = _bn_hyper(mine).cuda()
-    gen = torch.Generator().manual_seed(len(tag))
-    x = (torch.randn(*shape, generator=gen) + shift).requires_grad_(True)
-    ref.eval(), mine.eval()
-    with torch.no_grad():
-        want = ref(x)
-        out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(want), what=f'{tag} eval')
-    ref.train(), mine.train()
-    y = ref(x)
-    dy = torch.randn(y.shape, generator=gen)
-    y.backward(dy)
-    out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(y), what=f'{tag} train forward')
-    dx = mine.backward(MB.Act(nhwc(dy).cuda()))
-    rel_close(dx.t[..., dx.coff:dx.coff + shape[1]], nhwc(x.grad), what=f'{tag} dx')
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        assert q.grad is not None and p.grad is not None, n
-        rel_close(p.grad, q.grad, what=f'{tag}: d{n}', atol=2e-5)
-    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-        if 'running' in n:
-            rel_close(p, q, what=f'{tag}: {n}')
-        elif 'num_batches_tracked' in n:
-            assert int(p) == int(q), n
+    check_block(mk, R, shape, tag, shift=shift)
 
 
 def hub_batch(batch, size, nc, seed):
@@ -308,10 +254,7 @@ def test_hub_graph_training_step_eval_and_checkpoint(name, kw, batch, size, seed
     from oracle.somi_ref.loss import ComputeLoss as OLoss
     from oracle.somi_ref.testing import HYP_VISDRONE, fill_state
     from somi_amd import blocks as MB
-    from somi_amd.checkpoint import attempt_load
-    from somi_amd.loss import ComputeLoss
     from somi_amd.model import Model
-    from somi_amd.train import TrainStep
     R.register(monkeypatch)
     cfg = R.hub_cfg(name, **kw)
     ref = fill_state(OModel(cfg), 3)
@@ -323,13 +266,10 @@ def test_hub_graph_training_step_eval_and_checkpoint(name, kw, batch, size, seed
     if name == 'yolov3-spp':
         assert [len(m) for m in mine.model if isinstance(m, MB.Repeat)] == [3, 3]       # the 3-long Sequentials are in the graph under test
     if full:
-        ref.train()
-        pr = ref(imgs.float() / 255)
+        pr = check_train_step(ref, mine, imgs, targets, name)
         hit = entries_per_level(ref, pr, targets)
         print(f'{name}: entries per level {hit}, maps {[tuple(p.shape[2:4]) for p in pr]}')
         assert len(hit) == len(cfg['head'][-1][0]) and all(h > 0 for h in hit), f'a detection level has no target: {hit}'
-        lr, ir = OLoss(ref)(pr, targets)
-        lr.backward()
         if name == 'yolov5-p7':                                   # the fp32 oracle has to be a witness at this bar (see the docstring)
             ref64 = copy.deepcopy(ref).double()
             ref64.zero_grad()
@@ -338,63 +278,11 @@ def test_hub_graph_training_step_eval_and_checkpoint(name, kw, batch, size, seed
                       for p, q in zip(ref.parameters(), ref64.parameters()))
             print(f'{name}: the fp32 oracle is {own:.3f} x the bar from its fp64 copy')
             assert own <= 0.5, f'the fp32 oracle is {own:.2f} x the bar from fp64: no witness at this batch'
-        mine = mine.cuda().train()
-        pm = mine(imgs.cuda())
-        for a, b in zip(pm, pr):
-            rel_close(a, b, what=f'{name} train outputs')
-        lm, im = ComputeLoss(mine)(pm, targets.cuda())
-        rel_close(lm, lr, rel=1e-4, what=f'{name} loss')
-        rel_close(im, ir, rel=1e-4, what=f'{name} loss items')
-        lm.backward()
-        bad, worst = [], 0.0
-        for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-            assert q.grad is not None and p.grad is not None, n
-            err = (p.grad.cpu().double() - q.grad.double()).abs().max().item()
-            scale = q.grad.double().abs().max().item() + 1e-9
-            worst = max(worst, err / (2e-3 * scale + 2e-6))
-            if err > 2e-3 * scale + 2e-6:
-                bad.append((n, err, scale))
-        print(f'{name}: worst parameter gradient at {worst:.3f} x the bar')
-        assert not bad, bad[:8]
-        for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-            if 'running' in n:
-                rel_close(p, q, what=f'{name} {n}')
-    mine = mine.cuda()
-    ref.eval(), mine.eval()
-    with torch.no_grad():
-        zr, _ = ref(imgs.float() / 255)
-        z, _ = mine(imgs.cuda())
-    rel_close(z, zr, what=f'{name} z')
+    check_eval(ref, mine, imgs, name)
     if not full:
         return
-
-    runs = []
-    for _ in range(2):
-        m = Model(cfg)
-        m.load_state_dict(state)
-        tr = TrainStep(m.cuda(), dict(HYP_VISDRONE), batch)
-        grads, real = [], tr.optimizer.step
-
-        def spy(real=real, grads=grads, tr=tr):
-            grads.extend(g_.clone() for g_ in tr.optimizer.flat_grads)
-            real()
-        tr.optimizer.step = spy
-        loss, _ = tr.step(imgs.cuda(), targets.cuda())
-        torch.cuda.synchronize()
-        runs.append((loss.detach().clone(), grads, {k: v.detach().clone() for k, v in m.state_dict().items()}))
-    (l0, g0, s0), (l1, g1, s1) = runs
-    assert torch.isfinite(l0).all() and torch.equal(l0, l1)
-    assert all(torch.equal(a, b) for a, b in zip(g0, g1)), 'gradients differ between two identical steps'
-    assert all(torch.equal(s0[k], s1[k]) for k in s0), [k for k in s0 if not torch.equal(s0[k], s1[k])][:5]
-    assert any(not torch.equal(s0[k].cpu(), state[k]) for k in state if k.endswith('cv2.weight') or k.endswith('conv.weight')), 'the step changed no weight'
-
-    buf = io.BytesIO()
-    torch.save({'epoch': 1, 'model': copy.deepcopy(ref).half(), 'ema': None}, buf)
-    loaded, info = attempt_load(buf.getvalue(), foreign_prefixes=('oracle', 'hub_ref'))
-    assert info['used'] == 'model' and not loaded.training
-    want_model = copy.deepcopy(ref).half().float().eval()
-    with torch.no_grad():
-        rel_close(loaded(imgs.cuda())[0], want_model(imgs.float() / 255)[0], what=f'{name} z from the loaded checkpoint')
+    check_two_steps_bit_identical(cfg, state, imgs, targets, batch)
+    check_checkpoint_roundtrip(ref, imgs, ('oracle', 'hub_ref'), name)
 
 
 @pytest.mark.parametrize('nl', [5, 2])

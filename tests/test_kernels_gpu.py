@@ -6,24 +6,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from parity import nhwc, rel_close
+
 pytestmark = pytest.mark.gpu
 
 
 def dev():
     assert torch.cuda.is_available(), 'GPU tests need an MI355X'
     return torch.device('cuda:0')
-
-
-def rel_close(got, want, rel=1e-3, what=''):
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    assert err <= rel * scale, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
 
 
 ACTS = {'none': lambda v: v, 'silu': F.silu, 'gelu': F.gelu, 'relu': F.relu, 'sigmoid': torch.sigmoid}

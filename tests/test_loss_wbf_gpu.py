@@ -3,16 +3,10 @@ import numpy as np
 import pytest
 import torch
 
+from parity import rel_close
+
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-
-
-def rel_close(got, want, rel=1e-3, what=''):
-    got, want = torch.as_tensor(got).detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    assert err <= rel * scale, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
 
 
 class _M:

@@ -6,37 +6,22 @@ import pytest
 import torch
 import torch.nn as nn
 
+from parity import bn_hyper, check_block, check_eval, check_train_step, grads_close, nhwc, rel_close
+
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 
 
-def rel_close(got, want, rel=1e-3, what='', atol=0.0):
-    got, want = got.detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    assert err <= rel * scale + atol, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
+_MAKE = {'bottleneck_sc': lambda M: M.Bottleneck(16, 16, True, 1, k=((1, 1), (3, 3)), e=1.0),
+         'bottleneck_nosc': lambda M: M.Bottleneck(16, 24, True), 'c3_sc': lambda M: M.C3(32, 32, 2, True),
+         'c3_nosc': lambda M: M.C3(48, 32, 1, False), 'spp': lambda M: M.SPP(32, 32, (5, 9, 13)), 'focus': lambda M: M.Focus(3, 16, 3),
+         'conv6x6_s2': lambda M: M.Conv(3, 16, 6, 2, 2)}
 
 
 def _pair(tag):
     from oracle.somi_ref import blocks as OB
     from somi_amd import blocks as MB
-    mk = {'bottleneck_sc': lambda M: M.Bottleneck(16, 16, True, 1, k=((1, 1), (3, 3)), e=1.0),
-          'bottleneck_nosc': lambda M: M.Bottleneck(16, 24, True), 'c3_sc': lambda M: M.C3(32, 32, 2, True),
-          'c3_nosc': lambda M: M.C3(48, 32, 1, False), 'spp': lambda M: M.SPP(32, 32, (5, 9, 13)), 'focus': lambda M: M.Focus(3, 16, 3),
-          'conv6x6_s2': lambda M: M.Conv(3, 16, 6, 2, 2)}[tag]
-    return mk(OB), mk(MB)
-
-
-def _bn_hyper(mod):
-    for m in mod.modules():
-        if isinstance(m, nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    return mod
+    return _MAKE[tag](OB), _MAKE[tag](MB)
 
 
 BLOCKS = ['bottleneck_sc', 'bottleneck_nosc', 'c3_sc', 'c3_nosc', 'spp', 'focus', 'conv6x6_s2']
@@ -51,7 +36,7 @@ def test_stock_blocks_match_reference_vectors(golden, tag):
     ref, mine = _pair(tag)
     fill_state(ref, 0)
     mine.load_state_dict(ref.state_dict())
-    mine = _bn_hyper(mine).cuda()
+    mine = bn_hyper(mine).cuda()
     x = MB.Act(nhwc(T(g['in0'])).cuda())
     if x.t.shape[3] % 4:                                             # the 3-channel image: padded to 4 like the ingest kernel does
         x = MB.Act(torch.nn.functional.pad(x.t, (0, 4 - x.t.shape[3] % 4)).contiguous(), 0, x.t.shape[3])
@@ -66,32 +51,11 @@ def test_stock_blocks_match_reference_vectors(golden, tag):
 @pytest.mark.parametrize('tag,cin,shape', [('bottleneck_sc', 16, (3, 16, 9, 11)), ('bottleneck_nosc', 16, (2, 16, 8, 8)),
                                            ('c3_sc', 32, (2, 32, 10, 10)), ('c3_nosc', 48, (2, 48, 7, 9)), ('spp', 32, (2, 32, 11, 11))])
 def test_stock_blocks_train_forward_backward(tag, cin, shape):
-    """Training forward + hand-written backward against torch autograd on the oracle block: output, dx, every parameter gradient."""
+    """Training forward + hand-written backward against torch autograd on the oracle block: output, dx, every parameter gradient, the
+    running statistics."""
     from oracle.somi_ref import blocks as OB
-    from oracle.somi_ref.testing import fill_state
-    from somi_amd import blocks as MB
-    ref, mine = _pair(tag)
-    fill_state(ref, 5)
-    OB.initialize_weights(ref)
-    mine.load_state_dict(ref.state_dict())
-    mine = _bn_hyper(mine).cuda().train()
-    ref.train()
-    g = torch.Generator().manual_seed(len(tag))
-    x = torch.randn(*shape, generator=g, requires_grad=True)
-    y = ref(x)
-    dy = torch.randn(y.shape, generator=g)
-    y.backward(dy)
-    out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(y), what=f'{tag} forward')
-    dx = mine.backward(MB.Act(nhwc(dy).cuda()))
-    rel_close(dx.t[..., dx.coff:dx.coff + cin], nhwc(x.grad), what=f'{tag} dx')
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        if q.grad is not None:
-            assert p.grad is not None, n
-            rel_close(p.grad, q.grad, what=f'{tag}: d{n}', atol=2e-5)
-    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-        if 'running' in n:
-            rel_close(p, q, what=f'{tag}: {n}')
+    assert cin == shape[1]
+    check_block(_MAKE[tag], OB, shape, tag, eval_too=False)
 
 
 def test_focus_and_6x6_stem_backward_inside_a_graph():
@@ -106,7 +70,7 @@ def test_focus_and_6x6_stem_backward_inside_a_graph():
         fill_state(ref, 6)
         OB.initialize_weights(ref)
         mine.load_state_dict(ref.state_dict())
-        mine = _bn_hyper(mine).cuda().train()
+        mine = bn_hyper(mine).cuda().train()
         ref.train()
         g = torch.Generator().manual_seed(3)
         x = torch.randn(2, 8, 12, 16, generator=g, requires_grad=True)
@@ -121,8 +85,7 @@ def test_focus_and_6x6_stem_backward_inside_a_graph():
         for m in reversed(list(mine)):
             d = m.backward(d)
         rel_close(d.t[..., :8], nhwc(x.grad), what=f'{name} dx')
-        for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-            rel_close(p.grad, q.grad, what=f'{name}: d{n}', atol=2e-5)
+        grads_close(mine, ref, name)
 
 
 def test_concat_with_upsampled_input_forward_backward(golden):
@@ -182,8 +145,7 @@ def test_plain_detect_matches_reference_vectors_and_autograd(golden):
     dxs = mine.backward([d.cuda() for d in dys])
     for d, x in zip(dxs, xs):
         rel_close(d.t[..., :x.shape[1]], nhwc(x.grad), what='detect dx')
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        rel_close(p.grad, q.grad, what=f'Detect: d{n}', atol=2e-5)
+    grads_close(mine, ref, 'Detect')
 
 
 @pytest.mark.parametrize('tag,version', [('yolov5_v6', '6.0'), ('yolov5_v5', '5.0')])
@@ -229,10 +191,8 @@ def test_yolov5s_coco_training_step_and_nms():
     """BASELINE configs[0]: yolov5s (7,235,389 parameters, 80 classes) at 640x640, batch 2 - one whole training step (loss, every
     parameter gradient, BN statistics) against the CPU oracle, then eval predictions and NMS (selection bit-exact)."""
     from oracle.somi_ref import Model as OModel
-    from oracle.somi_ref.loss import ComputeLoss as OLoss
     from oracle.somi_ref.nms import non_max_suppression as oracle_nms
     from oracle.somi_ref.testing import HYP_VISDRONE, fill_state, synthetic_batch, yolov5_cfg
-    from somi_amd.loss import ComputeLoss
     from somi_amd.model import Model
     from somi_amd.nms import non_max_suppression
     cfg = yolov5_cfg()
@@ -242,39 +202,10 @@ def test_yolov5s_coco_training_step_and_nms():
     mine.load_state_dict(ref.state_dict())
     ref.hyp = mine.hyp = dict(HYP_VISDRONE)
     imgs, targets = synthetic_batch(2, 640, nc=80, seed=2)
-    ref.train()
-    pr = ref(imgs.float() / 255)
-    lr, ir = OLoss(ref)(pr, targets)
-    lr.backward()
-    mine = mine.cuda().train()
-    pm = mine(imgs.cuda())
-    for a, b in zip(pm, pr):
-        rel_close(a, b, what='train outputs')
-    lm, im = ComputeLoss(mine)(pm, targets.cuda())
-    rel_close(lm, lr, rel=1e-4, what='loss')
-    rel_close(im, ir, rel=1e-4, what='loss items')
-    lm.backward()
-    bad = []
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        if q.grad is None:
-            continue
-        assert p.grad is not None, n
-        err = (p.grad.cpu().double() - q.grad.double()).abs().max().item()
-        scale = q.grad.double().abs().max().item() + 1e-9
-        if err > 2e-3 * scale + 2e-6:
-            bad.append((n, err, scale))
-    assert not bad, bad[:8]
-    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-        if 'running' in n:
-            rel_close(p, q, what=n)
-    ref.eval(), mine.eval()
-    with torch.no_grad():
-        zr, _ = ref(imgs.float() / 255)
-        z, _ = mine(imgs.cuda())
+    check_train_step(ref, mine, imgs, targets, 'yolov5s')
+    z = check_eval(ref, mine, imgs, 'yolov5s')
     assert z.shape == (2, 25200, 85)
-    rel_close(z, zr, what='z')
     det = non_max_suppression(z, 0.001, 0.6, multi_label=True)
     want = oracle_nms(z.cpu(), 0.001, 0.6, multi_label=True)
     for a, b in zip(det, want):
         assert a.shape == b.shape and torch.equal(a.cpu(), b)
-

@@ -7,20 +7,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from parity import bn_hyper, buffers_close, check_built_block, grads_close, nhwc, rel_close
+
 pytestmark = pytest.mark.gpu
 ACTS = {'none': lambda v: v, 'silu': F.silu, 'gelu': F.gelu, 'relu': F.relu}
-
-
-def rel_close(got, want, rel=1e-3, what='', atol=0.0):
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    assert err <= rel * scale + atol, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
 
 
 @pytest.mark.parametrize('order,act,batch_stats', [(0, 'silu', True), (1, 'gelu', True), (0, 'silu', False), (0, 'none', True)])
@@ -109,15 +99,6 @@ def test_elementwise_sweeps_cover_every_pixel_and_channel(npix, C):
     rel_close(dgam, (dact * (x.double() - mean.double()) * rstd.double()).sum((0, 1, 2)).float(), rel=1e-4, what='dgamma')
 
 
-def _grads_close(mine, ref, what):
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        if q.grad is None:
-            continue
-        assert p.grad is not None, f'{what}: {n} has no gradient'
-        # atol: gradients that are analytically zero (e.g. a bias in front of a batch-norm) are rounding noise on both sides
-        rel_close(p.grad, q.grad, what=f'{what}: d{n}', atol=2e-5)
-
-
 def test_conv_block_train_forward_backward():
     """Conv (conv -> BN batch stats -> SiLU) chain in training mode: outputs, running stats, dx and all parameter gradients."""
     from oracle.somi_ref import blocks as OB
@@ -130,10 +111,7 @@ def test_conv_block_train_forward_backward():
     OB.initialize_weights(ref)
     mine = nn.Sequential(*[MB.Conv(*c) for c in cfgs])
     mine.load_state_dict(ref.state_dict())
-    for m in mine.modules():
-        if isinstance(m, nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    mine = mine.cuda().train()
+    mine = bn_hyper(mine).cuda().train()
     ref.train()
     x = torch.randn(3, 16, 14, 10, generator=g, requires_grad=True)
     y = ref(x)
@@ -143,33 +121,12 @@ def test_conv_block_train_forward_backward():
     for m in mine:
         a = m(a)
     rel_close(a.t[..., :20], nhwc(y), what='train forward')
-    for m, r in zip(mine, ref):
-        rel_close(m.bn.running_mean, r.bn.running_mean, what='running_mean')
-        rel_close(m.bn.running_var, r.bn.running_var, what='running_var')
+    buffers_close(mine, ref, 'conv chain')
     d = MB.Act(nhwc(dy).cuda())
     for m in reversed(list(mine)):
         d = m.backward(d)
     rel_close(d.t, nhwc(x.grad), what='dx')
-    _grads_close(mine, ref, 'conv chain')
-
-
-def _run_block_train(mine, ref, x, seed, what, cin):
-    from somi_amd import blocks as MB
-    g = torch.Generator().manual_seed(seed)
-    for m in mine.modules():
-        if isinstance(m, nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    mine = mine.cuda().train()
-    ref.train()
-    x = x.clone().requires_grad_(True)
-    y = ref(x)
-    dy = torch.randn(y.shape, generator=g)
-    y.backward(dy)
-    out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(y), what=f'{what} forward')
-    dx = mine.backward(MB.Act(nhwc(dy).cuda()))
-    rel_close(dx.t[..., :cin], nhwc(x.grad), what=f'{what} dx')
-    _grads_close(mine, ref, what)
+    grads_close(mine, ref, 'conv chain')
 
 
 @pytest.mark.parametrize('c1,c2,n,shortcut', [(32, 32, 2, True), (48, 32, 1, False), (32, 32, 3, False), (64, 32, 3, True)])
@@ -182,7 +139,7 @@ def test_c2fcbam_train_forward_backward(c1, c2, n, shortcut):
     mine = MB.C2fCBAM(c1, c2, n, shortcut)
     mine.load_state_dict(ref.state_dict())
     x = torch.randn(2, c1, 12, 10, generator=torch.Generator().manual_seed(c1))
-    _run_block_train(mine, ref, x, 21, 'C2fCBAM', c1)
+    check_built_block(ref, mine, x, torch.Generator().manual_seed(21), 'C2fCBAM', eval_too=False)
 
 
 @pytest.mark.parametrize('c,n,B,H,W', [(64, 2, 3, 37, 29), (256, 1, 2, 20, 20), (32, 1, 5, 45, 31)])
@@ -231,7 +188,7 @@ def test_sppf_seam_train_forward_backward():
         mine = ctor_m()
         mine.load_state_dict(ref.state_dict())
         x = torch.randn(2, cin, 11, 9, generator=torch.Generator().manual_seed(3))
-        _run_block_train(mine, ref, x, 31, name, cin)
+        check_built_block(ref, mine, x, torch.Generator().manual_seed(31), name, eval_too=False)
 
 
 def test_bifpn_train_backward():
@@ -269,10 +226,7 @@ def test_decoupled_detect_train_backward():
     OB.initialize_weights(ref)
     mine = MB.DecoupledDetect(10, anchors, (64, 96))
     mine.load_state_dict(ref.state_dict())
-    for m in mine.modules():
-        if isinstance(m, nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    mine = mine.cuda().train()
+    mine = bn_hyper(mine).cuda().train()
     ref.train()
     ref.stride = mine.stride = torch.tensor([8., 16.])
     xs = [torch.randn(2, 64, 8, 8, generator=g, requires_grad=True), torch.randn(2, 96, 4, 4, generator=g, requires_grad=True)]
@@ -285,7 +239,7 @@ def test_decoupled_detect_train_backward():
     dxs = mine.backward([d.cuda() for d in dys])
     for d, x in zip(dxs, xs):
         rel_close(d.t[..., :x.shape[1]], nhwc(x.grad), what='detect dx')
-    _grads_close(mine, ref, 'DecoupledDetect')
+    grads_close(mine, ref, 'DecoupledDetect')
 
 
 def _train_cfg(odconv):
@@ -439,7 +393,9 @@ def test_odconv_train_forward_backward(B):
     mine = MB.ODConv_3rd(16, 32, 3, 2, 4)
     mine.load_state_dict(ref.state_dict())
     x = torch.randn(B, 16, 12, 12, generator=torch.Generator().manual_seed(B))
-    _run_block_train(mine, ref, x, 41 + B, f'ODConv B={B}', 16)
+    # conv.reduction is unused in the reference (and here); one sample skips the squeeze BatchNorm, so its parameters get nothing either
+    no_grad = ('conv.reduction.weight', 'conv.reduction.bias') + (('conv.bn.weight', 'conv.bn.bias') if B == 1 else ())
+    check_built_block(ref, mine, x, torch.Generator().manual_seed(41 + B), f'ODConv B={B}', eval_too=False, no_grad=no_grad)
 
 
 def test_fused_sgd_nesterov_ema_matches_torch():

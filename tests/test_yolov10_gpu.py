@@ -2,31 +2,14 @@
 against fp64 on the CPU, the blocks against torch autograd on the CPU restatement (tests/yolov10_ref.py), the whole graph against the
 oracle Model.  Bar 1e-3 relative (BASELINE)."""
 import copy
-import io
 
 import pytest
 import torch
 
 import yolov10_ref as R
+from parity import check_block, check_checkpoint_roundtrip, check_eval, check_train_step, check_two_steps_bit_identical, rel_close
 
 pytestmark = pytest.mark.gpu
-
-
-def rel_close(got, want, rel=1e-3, what='', atol=0.0):
-    got, want = got.detach().cpu().double(), torch.as_tensor(want).detach().cpu().double()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert torch.isfinite(got).all(), f'{what}: not finite'
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item() + 1e-12
-    assert err <= rel * scale + atol, f'{what}: max err {err:.3e} vs scale {scale:.3e}'
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2)
 
 
 def _attn64(qkv, heads, dout=None, dv_add=None):
@@ -111,13 +94,6 @@ def test_psa_attention_large_logits():
     rel_close(g.reshape(B, N, -1), g64, rel=2e-3, what='qkv gradient')
 
 
-def _bn_hyper(mod):
-    for m in mod.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eps, m.momentum = 1e-3, 0.03
-    return mod
-
-
 BLOCKS = {'c2f_n1_sc': (lambda M: M.C2f(32, 32, 1, True), (2, 32, 9, 11)),
           'c2f_n2_sc': (lambda M: M.C2f(32, 32, 2, True), (2, 32, 10, 10)),
           'c2f_n1_nosc': (lambda M: M.C2f(24, 32, 1, False), (2, 24, 7, 9)),
@@ -136,36 +112,8 @@ BLOCKS = {'c2f_n1_sc': (lambda M: M.C2f(32, 32, 1, True), (2, 32, 9, 11)),
 def test_yolov10_blocks_eval_train_backward(tag):
     """Eval forward (BatchNorm folded), training forward, hand-written backward against torch autograd on the CPU restatement: output,
     dx, every parameter gradient (BatchNorm's included) and the updated running statistics."""
-    from oracle.somi_ref import blocks as OB
-    from oracle.somi_ref.testing import fill_state
-    from somi_amd import blocks as MB
     mk, shape = BLOCKS[tag]
-    ref, mine = mk(R), mk(MB)
-    fill_state(ref, 5)
-    OB.initialize_weights(ref)
-    mine.load_state_dict(ref.state_dict())
-    mine = _bn_hyper(mine).cuda()
-    gen = torch.Generator().manual_seed(len(tag))
-    x = torch.randn(*shape, generator=gen, requires_grad=True)
-    ref.eval(), mine.eval()
-    with torch.no_grad():
-        want = ref(x)
-        out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(want), what=f'{tag} eval')
-    ref.train(), mine.train()
-    y = ref(x)
-    dy = torch.randn(y.shape, generator=gen)
-    y.backward(dy)
-    out = mine(MB.Act(nhwc(x.detach()).cuda()))
-    rel_close(out.t[..., out.coff:out.coff + out.c], nhwc(y), what=f'{tag} train forward')
-    dx = mine.backward(MB.Act(nhwc(dy).cuda()))
-    rel_close(dx.t[..., dx.coff:dx.coff + shape[1]], nhwc(x.grad), what=f'{tag} dx')
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        assert q.grad is not None and p.grad is not None, n
-        rel_close(p.grad, q.grad, what=f'{tag}: d{n}', atol=2e-5)
-    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-        if 'running' in n:
-            rel_close(p, q, what=f'{tag}: {n}')
+    check_block(mk, R, shape, tag)
 
 
 def test_yolov10_graph_training_step_eval_and_checkpoint(monkeypatch):
@@ -173,13 +121,9 @@ def test_yolov10_graph_training_step_eval_and_checkpoint(monkeypatch):
     and backward (outputs, loss, every parameter gradient, BatchNorm statistics), the eval forward; two fresh TrainStep.step runs
     bit-identical; attempt_load of a pickled oracle model reproduces the eval forward."""
     from oracle.somi_ref import Model as OModel
-    from oracle.somi_ref.loss import ComputeLoss as OLoss
     from oracle.somi_ref.testing import HYP_VISDRONE, fill_state, synthetic_batch
-    from somi_amd.checkpoint import attempt_load
     from somi_amd.configs import yolov10_cfg
-    from somi_amd.loss import ComputeLoss
     from somi_amd.model import Model
-    from somi_amd.train import TrainStep
     R.register(monkeypatch)
     cfg = yolov10_cfg(0.25, 0.33)
     ref = fill_state(OModel(cfg), 3)
@@ -188,58 +132,7 @@ def test_yolov10_graph_training_step_eval_and_checkpoint(monkeypatch):
     mine.load_state_dict(state)
     ref.hyp = mine.hyp = dict(HYP_VISDRONE)
     imgs, targets = synthetic_batch(2, 160, nc=10, seed=2)
-    ref.train()
-    pr = ref(imgs.float() / 255)
-    lr, ir = OLoss(ref)(pr, targets)
-    lr.backward()
-    mine = mine.cuda().train()
-    pm = mine(imgs.cuda())
-    for a, b in zip(pm, pr):
-        rel_close(a, b, what='train outputs')
-    lm, im = ComputeLoss(mine)(pm, targets.cuda())
-    rel_close(lm, lr, rel=1e-4, what='loss')
-    rel_close(im, ir, rel=1e-4, what='loss items')
-    lm.backward()
-    bad = []
-    for (n, p), (_, q) in zip(mine.named_parameters(), ref.named_parameters()):
-        assert q.grad is not None and p.grad is not None, n
-        err = (p.grad.cpu().double() - q.grad.double()).abs().max().item()
-        scale = q.grad.double().abs().max().item() + 1e-9
-        if err > 2e-3 * scale + 2e-6:
-            bad.append((n, err, scale))
-    assert not bad, bad[:8]
-    for (n, p), (_, q) in zip(mine.named_buffers(), ref.named_buffers()):
-        if 'running' in n:
-            rel_close(p, q, what=n)
-    ref.eval(), mine.eval()
-    with torch.no_grad():
-        zr, _ = ref(imgs.float() / 255)
-        z, _ = mine(imgs.cuda())
-    rel_close(z, zr, what='z')
-
-    runs = []
-    for _ in range(2):
-        m = Model(cfg)
-        m.load_state_dict(state)
-        tr = TrainStep(m.cuda(), dict(HYP_VISDRONE), 2)
-        grads, real = [], tr.optimizer.step
-
-        def spy(real=real, grads=grads):
-            grads.extend(g_.clone() for g_ in tr.optimizer.flat_grads)
-            real()
-        tr.optimizer.step = spy
-        loss, _ = tr.step(imgs.cuda(), targets.cuda())
-        torch.cuda.synchronize()
-        runs.append((loss.detach().clone(), grads, {k: v.detach().clone() for k, v in m.state_dict().items()}))
-    (l0, g0, s0), (l1, g1, s1) = runs
-    assert torch.equal(l0, l1)
-    assert all(torch.equal(a, b) for a, b in zip(g0, g1)), 'gradients differ between two identical steps'
-    assert all(torch.equal(s0[k], s1[k]) for k in s0), [k for k in s0 if not torch.equal(s0[k], s1[k])][:5]
-
-    buf = io.BytesIO()
-    torch.save({'epoch': 1, 'model': copy.deepcopy(ref).half(), 'ema': None}, buf)
-    loaded, info = attempt_load(buf.getvalue(), foreign_prefixes=('oracle', 'yolov10_ref'))
-    assert info['used'] == 'model' and not loaded.training
-    want_model = copy.deepcopy(ref).half().float().eval()
-    with torch.no_grad():
-        rel_close(loaded(imgs.cuda())[0], want_model(imgs.float() / 255)[0], what='z from the loaded checkpoint')
+    check_train_step(ref, mine, imgs, targets, 'yolov10')
+    check_eval(ref, mine, imgs, 'yolov10')
+    check_two_steps_bit_identical(cfg, state, imgs, targets, 2)
+    check_checkpoint_roundtrip(ref, imgs, ('oracle', 'yolov10_ref'), 'yolov10')
