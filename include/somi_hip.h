@@ -618,6 +618,35 @@ int somi_nms_f32(const float *pred, int B, int n, int nc, float conf_thres, floa
                  int agnostic, const uint64_t *classes_mask, int max_det, float *det, int32_t *count, void *workspace,
                  size_t workspace_bytes, somi_stream_t stream);
 
+/* The reference's other selection rules (utils/general.py).  Candidate generation, the top-30000 cut and the stable descending sort are
+ * those of somi_nms_f32; `mode` picks what runs on the sorted candidates:
+ *   SOMI_NMS_IOU                   the torchvision rule; with merge = 0 the call is somi_nms_f32, bit for bit.
+ *   SOMI_NMS_GIOU .. SOMI_NMS_SIOU `NMS(boxes, scores, iou_thres, class_nms)` (:925-951): greedy, candidate j is suppressed by an earlier
+ *                                  kept box i iff !(bbox_iou(box_i, box_j, <mode>=True) <= iou_thres) (utils/metrics.py:490-579, alpha = 1,
+ *                                  eps = 1e-7; a NaN suppresses).  GIoU / DIoU / EIoU reproduce the CPU's fp32 bits; CIoU / SIoU go
+ *                                  through atan / asin / cos / exp and agree to a few roundings of the metric.
+ *   SOMI_NMS_SOFT                  `soft_nms` (:834-862, the alternative at :695) on the sorted candidates: keep the current box with its
+ *                                  score as it stands, multiply every live score whose box_iou_for_nms(cur, j, CIoU=True) (:868-892)
+ *                                  exceeds iou_thres by exp(-m*m/sigma), drop what is not > score_threshold, go on with the highest live
+ *                                  score (an exact tie: the lowest index), at most max_det picks.  det rows carry the decayed scores.
+ *                                  Unlike the reference, whose loop leaves with one candidate in hand, the last candidate is kept.
+ *   merge != 0                     merge-NMS (:698-704) after the max_det cut, for images with 1 < candidates < 3000: each kept box
+ *                                  becomes the score-weighted mean of the candidates whose plain IoU with it exceeds iou_thres (summed in
+ *                                  a fixed order), and rows whose cluster is the box alone are dropped (`redundant`).  Not with SOFT.
+ * sigma and score_threshold are read by SOMI_NMS_SOFT only (the reference's defaults: 0.5, 0.25).
+ * somi_nms_boxes_f32 is the standalone form, `NMS()` / `soft_nms()` on boxes (n,4) xyxy (16-byte aligned) and scores (n), n <= 30000:
+ * keep (n) int64 receives the kept indices (greedy modes: descending score, ties in index order; SOFT: pick order, candidates taken in
+ * the given order with index 0 first, scores decayed in place), count (1) int32 how many.
+ * workspace bytes: somi_nms_ex_workspace_bytes(B, n, nc, multi_label, mode, merge), somi_nms_boxes_workspace_bytes(n). */
+enum { SOMI_NMS_IOU = 0, SOMI_NMS_GIOU = 1, SOMI_NMS_DIOU = 2, SOMI_NMS_CIOU = 3, SOMI_NMS_EIOU = 4, SOMI_NMS_SIOU = 5, SOMI_NMS_SOFT = 6 };
+size_t somi_nms_ex_workspace_bytes(int B, int n, int nc, int multi_label, int mode, int merge);
+int somi_nms_ex_f32(const float *pred, int B, int n, int nc, float conf_thres, float iou_thres, int multi_label, int agnostic,
+                    const uint64_t *classes_mask, int max_det, int mode, int merge, float sigma, float score_threshold, float *det,
+                    int32_t *count, void *workspace, size_t workspace_bytes, somi_stream_t stream);
+size_t somi_nms_boxes_workspace_bytes(int n);
+int somi_nms_boxes_f32(const float *boxes, float *scores, int n, int mode, float iou_thres, float sigma, float score_threshold,
+                       int64_t *keep, int32_t *count, void *workspace, size_t workspace_bytes, somi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Loss: ComputeLoss.__call__ + build_targets (utils/loss.py:142-262) with CIoU (utils/metrics.py:476-518).
  * p[l] (B,na,ny_l,nx_l,no) for l < nl<=4; targets (nt,6) [img,cls,x,y,w,h]; anchors (nl,na,2) in grid units.

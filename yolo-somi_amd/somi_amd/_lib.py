@@ -165,6 +165,10 @@ SIGNATURES = {
     'somi_axpby_f32': (I, [P, P, C.c_long, F, F, S]),
     'somi_nms_workspace_bytes': (Z, [I, I, I, I]),
     'somi_nms_f32': (I, [P, I, I, I, F, F, I, I, P, I, P, P, P, Z, S]),
+    'somi_nms_ex_workspace_bytes': (Z, [I, I, I, I, I, I]),
+    'somi_nms_ex_f32': (I, [P, I, I, I, F, F, I, I, P, I, I, I, F, F, P, P, P, Z, S]),
+    'somi_nms_boxes_workspace_bytes': (Z, [I]),
+    'somi_nms_boxes_f32': (I, [P, P, I, I, F, F, F, P, P, P, Z, S]),
     'somi_loss_workspace_bytes': (Z, [C.POINTER(LossDesc)]),
     'somi_yolo_loss_f32': (I, [C.POINTER(LossDesc), P, P, Z, S]),
     'somi_loss5_workspace_bytes': (Z, [C.POINTER(LossDesc), C.POINTER(LossLevel)]),

@@ -43,7 +43,7 @@ def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None):
 
 
 @torch.no_grad()
-def run(model, batches, conf_thres=0.001, iou_thres=0.6, single_cls=False, device=None, confusion_matrix=None):
+def run(model, batches, conf_thres=0.001, iou_thres=0.6, single_cls=False, device=None, confusion_matrix=None, nms='iou', merge=False):
     """-> (mp, mr, map50, map, dict(p, r, ap50, ap, ap_class, seen, nt)); val.py:148-212 with plots / saving off.
     confusion_matrix: a `somi_amd.metrics.ConfusionMatrix` to fill as val.py:141,186 does when `plots` is on."""
     device = device or next(model.parameters()).device
@@ -61,7 +61,7 @@ def run(model, batches, conf_thres=0.001, iou_thres=0.6, single_cls=False, devic
         nb, _, height, width = imgs.shape
         out, _ = model(imgs)
         targets[:, 2:] *= torch.tensor([width, height, width, height], device=device, dtype=torch.float32)     # val.py:166
-        out = non_max_suppression(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)            # val.py:169
+        out = non_max_suppression(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls, nms=nms, merge=merge)   # val.py:169
         labs, predn = [], []
         for si in range(nb):
             labels = targets[targets[:, 0] == si, 1:]
