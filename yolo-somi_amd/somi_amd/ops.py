@@ -514,21 +514,23 @@ def resample_slice(src, src_coff, dst, dst_coff, c, up=0, reduce=False, accumula
     return dst
 
 
-def space_to_depth(x, x_coff, c, out=None, inverse=False):
+def space_to_depth(x, x_coff, c, out=None, inverse=False, y_coff=0):
     """Focus (models/common.py:1996): (B,2Ho,2Wo,.) slice of c channels -> (B,Ho,Wo,4c); inverse=True maps a gradient in the deep
-    layout back to the image layout (out must then be given or is allocated with pad4(c) channels)."""
+    layout back to the image layout (allocated with pad4(c) channels unless `out` is given).  A given `out` is written at channels
+    [y_coff, y_coff + 4c) (inverse: + c) and nowhere else; an allocated one has its padding channels zeroed."""
     if not inverse:
         B, H, W, _ = x.shape
-        out = torch.empty(B, H // 2, W // 2, (4 * c + 3) // 4 * 4, device=x.device, dtype=torch.float32) if out is None else out
-        if 4 * c < out.shape[3]:
-            out[..., 4 * c:].zero_()
-        check(_lib.lib().somi_space_to_depth_nhwc_f32(_ptr(_f32c(x)), x.shape[3], x_coff, _ptr(_f32c(out)), out.shape[3], 0, B, H // 2, W // 2, c, 0,
-                                                      _stream()), 'space_to_depth')
+        if out is None:
+            out = torch.empty(B, H // 2, W // 2, (4 * c + 3) // 4 * 4, device=x.device, dtype=torch.float32)
+            if 4 * c < out.shape[3]:
+                out[..., 4 * c:].zero_()
+        check(_lib.lib().somi_space_to_depth_nhwc_f32(_ptr(_f32c(x)), x.shape[3], x_coff, _ptr(_f32c(out)), out.shape[3], y_coff, B, H // 2, W // 2,
+                                                      c, 0, _stream()), 'space_to_depth')
         return out
     B, Ho, Wo, _ = x.shape
     out = torch.zeros(B, 2 * Ho, 2 * Wo, (c + 3) // 4 * 4, device=x.device, dtype=torch.float32) if out is None else out
-    check(_lib.lib().somi_space_to_depth_nhwc_f32(_ptr(_f32c(x)), x.shape[3], x_coff, _ptr(_f32c(out)), out.shape[3], 0, B, Ho, Wo, c, 1, _stream()),
-          'space_to_depth (inverse)')
+    check(_lib.lib().somi_space_to_depth_nhwc_f32(_ptr(_f32c(x)), x.shape[3], x_coff, _ptr(_f32c(out)), out.shape[3], y_coff, B, Ho, Wo, c, 1,
+                                                  _stream()), 'space_to_depth (inverse)')
     return out
 
 
