@@ -272,6 +272,30 @@ int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, 
 int somi_spp_pool_bwd_nhwc_f32(const void *codes, float *dbuf, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
                                somi_stream_t stream);
 
+/* The learned 2x upsamplers of the neck (upsample.hip).  NHWC fp32 channel slices; C, strides and offsets are multiples of 4.  New symbols only: the ABI
+ * version does not move.
+ *
+ * carafe: out[c, 2h+dy, 2w+dx] = sum_{a,b} softmax_t(logits[t*4 + dy*2 + dx, h, w])[a*k+b] * x[c, h+a-r, w+b-r], k = k_up (3 or 5), r = k / 2, x zero outside
+ *   the map (models/common.py:4476-4490 without the unfolded tensor).  x (B,H,W,x_cs), logits (B,H,W,l_cs) = the 4*k*k channels of the encoder conv,
+ *   out (B,2H,2W,o_cs).  weights: NULL (eval) or B*2H*2W*k*k floats that receive the softmax weights per OUTPUT pixel - the only tensor backward needs.
+ *   No workspace.  The backward WRITES dx (B,H,W,dx_cs) - owner-computes, a fixed order of terms - and dlogits (B,H,W,dl_cs) in the logits' channel
+ *   layout: p * (dp - sum p * dp), dp[a*k+b] = sum_c dout * x.  No float atomics.
+ * dysample (style 'lp', no dyscope): offset (B,H,W,f_cs) is the raw output of the 1x1 offset conv, 8 * groups channels (x in the first half, y in the
+ *   second), init_pos 8 * groups floats.  For j = g*4 + dy*2 + dx: sx = w + 0.25 * offset[j] + init_pos[j], sy = h + 0.25 * offset[4*groups + j] +
+ *   init_pos[4*groups + j], clamped to the map; out[2h+dy, 2w+dx] = the bilinear sample of x's channels of group g there.  C % groups == 0 and
+ *   (C / groups) % 4 == 0.  The backward WRITES dx (owner-computes over the output pixels whose source pixel lies within 2 pixels; a bilinear corner
+ *   farther than that from its source pixel is added with an fp32 atomic and counted into *far_count, a device uint32 the caller zeroes: 0 <=> the launch
+ *   was bit-reproducible) and doffset (B,H,W,df_cs) in offset's layout, the 0.25 included, 0 where the coordinate was clamped. */
+int somi_carafe_nhwc_f32(const float *x, const float *logits, float *out, float *weights, int B, int H, int W, int C, int k_up, int x_cs, int x_coff,
+                         int l_cs, int l_coff, int o_cs, int o_coff, somi_stream_t stream);
+int somi_carafe_bwd_nhwc_f32(const float *dout, const float *x, const float *weights, float *dx, float *dlogits, int B, int H, int W, int C, int k_up,
+                             int d_cs, int d_coff, int x_cs, int x_coff, int dx_cs, int dx_coff, int dl_cs, int dl_coff, somi_stream_t stream);
+int somi_dysample_nhwc_f32(const float *x, const float *offset, const float *init_pos, float *out, int B, int H, int W, int C, int groups, int x_cs,
+                           int x_coff, int f_cs, int f_coff, int o_cs, int o_coff, somi_stream_t stream);
+int somi_dysample_bwd_nhwc_f32(const float *dout, const float *x, const float *offset, const float *init_pos, float *dx, float *doffset, void *far_count,
+                               int B, int H, int W, int C, int groups, int d_cs, int d_coff, int x_cs, int x_coff, int f_cs, int f_coff, int dx_cs,
+                               int dx_coff, int df_cs, int df_coff, somi_stream_t stream);
+
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed
  * inside the kernel from the raw parameter w_dev (n_in floats on the device; no host copy of it is needed).

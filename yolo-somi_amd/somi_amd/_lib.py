@@ -177,6 +177,10 @@ SIGNATURES = {
     'somi_maxpool2_bwd_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
+    'somi_carafe_bwd_nhwc_f32': (I, [P, P, P, P, P] + [I] * 13 + [S]),
+    'somi_dysample_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
+    'somi_dysample_bwd_nhwc_f32': (I, [P, P, P, P, P, P, P] + [I] * 15 + [S]),
     'somi_val_match_f32': (I, [P, P, P, P, P, I, I, I, I, P, S]),
     'somi_confusion_matrix_f32': (I, [P, P, P, P, I, I, I, I, F, F, P, S]),
     'somi_ap_per_class_workspace_bytes': (Z, [C.c_long, I, I]),

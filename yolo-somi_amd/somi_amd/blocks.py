@@ -427,8 +427,8 @@ class PlainConv(_Packed):
             self.__dict__['_ctx'] = x
         return out
 
-    def backward(self, dy):
-        """dy: whole padded gradient tensor (pad channels zero).  Returns dx (Act)."""
+    def backward(self, dy, dx_out=None, accumulate=False):
+        """dy: whole padded gradient tensor (pad channels zero).  Returns dx (Act): written into dx_out if given, added to it if accumulate."""
         x = self.__dict__.pop('_ctx')
         k = self.conv.kernel_size[0]
         c1, c2 = self.conv.in_channels, self.conv.out_channels
@@ -440,8 +440,9 @@ class PlainConv(_Packed):
         ops.chan_sum_(dy, cp, 0, db)
         _acc_grad(self.conv.bias, db[:c2])
         wt = pack_dgrad_weight(self.conv.weight.detach().float()).to(dy.device)
-        dx = Act(torch.empty(B, H, W, pad4(c1), device=dy.device, dtype=torch.float32), 0, c1)
-        ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=pad4(c1), kh=k, kw=k, stride=1, pad=k // 2, cout=cp, out=dx.t)
+        dx = Act(torch.empty(B, H, W, pad4(c1), device=dy.device, dtype=torch.float32), 0, c1) if dx_out is None else dx_out
+        ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=pad4(c1), kh=k, kw=k, stride=1, pad=k // 2, cout=cp, out=dx.t, dx_coff=dx.coff,
+                              accumulate=dx.t if accumulate else None, acc_coff=dx.coff)
         return dx
 
 
@@ -693,6 +694,124 @@ class Upsample(nn.Module):
 
     def backward(self, dout):
         return dout                                              # the consumer (BiFPN) already produced the low-resolution gradient
+
+
+def _up_backward_target(dout, x, dx_out, accumulate):
+    """Where a learned upsampler's backward kernel WRITES its input gradient: the caller's slice when it is only to be written, else a tensor of its own."""
+    B, H, W, _ = x.shape
+    if dout.up or tuple(dout.shape[:3]) != (B, 2 * H, 2 * W):
+        raise RuntimeError(f'gradient of a 2x upsampler must be ({B}, {2 * H}, {2 * W}, .), got {tuple(dout.shape)}')
+    if dx_out is not None and not accumulate:
+        return dx_out
+    return Act(torch.empty(B, H, W, x.c, device=dout.t.device, dtype=torch.float32), 0, x.c)
+
+
+def _up_backward_result(dx, dx_out, accumulate, need_dx):
+    if not need_dx:
+        return None
+    if dx_out is not None and accumulate:
+        ops.add_(dx_out.t, dx_out.coff, dx.t, dx.coff, dx.c)
+        return dx_out
+    return dx
+
+
+class CARAFE(nn.Module):
+    """Content-aware reassembly, 2x (models/common.py:4450-4490): comp (1x1 Conv) -> enc (Conv, no activation) gives (2 * k_up)^2 logits per source
+    pixel; every output pixel is the softmax-weighted sum of the k_up x k_up source window around its source pixel.  The reference unfolds the
+    upsampled map to (B, C, k_up^2, 2H, 2W); here one kernel does softmax + reassembly from x and the logits (ops.carafe), and training keeps only the
+    softmax weights.  A real 2H x 2W tensor comes out (up = 0): BiFPN and Concat take it as it is."""
+
+    def __init__(self, c, k_enc=3, k_up=5, c_mid=64, scale=2):
+        super().__init__()
+        if scale != 2:
+            raise NotImplementedError(f'CARAFE with scale={scale} is not on the SOMI path (scale 2 only)')
+        if k_up not in (3, 5):
+            raise NotImplementedError(f'CARAFE with k_up={k_up} is not on the SOMI path (k_up 3 or 5)')
+        if k_enc not in (1, 3):
+            raise NotImplementedError(f'CARAFE with k_enc={k_enc} is not on the SOMI path (k_enc 1 or 3)')
+        if c % 4:
+            raise NotImplementedError(f'CARAFE needs a channel count that is a multiple of 4 (c % 4 == 0), got {c}')
+        self.scale, self.k_up = scale, k_up
+        self.comp = Conv(c, c_mid)
+        self.enc = Conv(c_mid, (scale * k_up) ** 2, k=k_enc, act=False)
+
+    def forward(self, x):
+        if x.up:
+            raise NotImplementedError('CARAFE reads a real tensor, not an nn.Upsample view')
+        B, H, W, _ = x.shape
+        logits = self.enc(self.comp(x))
+        out = new_act(x.t, 2 * H, 2 * W, x.c)
+        r = ops.carafe(x.t, logits.t, x.c, self.k_up, x.coff, logits.coff, out=out.t, weights=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (x, r[1])
+        return out
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """The kernel writes dx's reassembly part and the logits' gradient; enc and comp then run their own backward, comp adding into that dx."""
+        x, wts = self.__dict__.pop('_ctx')
+        dx = _up_backward_target(dout, x, dx_out, accumulate)
+        _, dl = ops.carafe_backward(dout.t, x.t, wts, x.c, self.k_up, dout.coff, x.coff, out=dx.t, dx_coff=dx.coff)
+        dmid = self.enc.backward(Act(dl, 0, dl.shape[3]))
+        self.comp.backward(dmid, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return _up_backward_result(dx, dx_out, accumulate, need_dx)
+
+
+class DySample(nn.Module):
+    """Dynamic point-sampling upsampler, 2x, style 'lp' without dyscope (models/common.py:4246-4309): a 1x1 conv with bias gives 2 * 4 offsets per
+    group and source pixel; every output pixel is the bilinear sample of its group's channels at source pixel + 0.25 * offset + init_pos, clamped to
+    the map.  The reference goes through pixel_shuffle, permute and grid_sample; here one kernel reads x and the raw conv output (ops.dysample).
+    init_pos stays the reference's registered buffer.  A real 2H x 2W tensor comes out (up = 0)."""
+
+    def __init__(self, in_channels, scale=2, style='lp', groups=4, dyscope=False):
+        super().__init__()
+        if scale != 2:
+            raise NotImplementedError(f'DySample with scale={scale} is not on the SOMI path (scale 2 only)')
+        if style != 'lp':
+            raise NotImplementedError(f"DySample with style={style!r} is not on the SOMI path (style 'lp' only)")
+        if dyscope:
+            raise NotImplementedError('DySample with dyscope=True is not on the SOMI path')
+        if in_channels % 4:
+            raise NotImplementedError(f'DySample needs a channel count that is a multiple of 4 (c % 4 == 0), got {in_channels}')
+        if groups < 1 or in_channels % groups or (in_channels // groups) % 4:
+            raise NotImplementedError(f'DySample needs channels per group that are a multiple of 4 ((c / groups) % 4 == 0), got c={in_channels}, '
+                                      f'groups={groups}')
+        self.scale, self.style, self.groups = scale, style, groups
+        self.offset = nn.Conv2d(in_channels, 2 * groups * scale ** 2, 1)
+        nn.init.normal_(self.offset.weight, 0, 0.001)            # normal_init(self.offset, std=0.001), models/common.py:4265
+        nn.init.constant_(self.offset.bias, 0)
+        h = torch.arange((-scale + 1) / 2, (scale - 1) / 2 + 1) / scale
+        self.register_buffer('init_pos', torch.stack(torch.meshgrid(h, h, indexing='ij')).transpose(1, 2).repeat(1, groups, 1).reshape(1, -1, 1, 1))
+        self.__dict__['_offset'] = PlainConv(self.offset)       # the runner shares the parameters, stays out of state_dict
+
+    def invalidate(self):
+        self._offset.invalidate()
+
+    def _init_pos(self, dev):
+        ip = self.init_pos.detach().reshape(-1)
+        if ip.device != dev:
+            raise RuntimeError('somi_amd DySample runs on the MI355X only (no CPU fallback): move the module to the GPU')
+        return ip if ip.dtype == torch.float32 else ip.float()
+
+    def forward(self, x):
+        if x.up:
+            raise NotImplementedError('DySample reads a real tensor, not an nn.Upsample view')
+        self._offset.train(self.training)
+        B, H, W, _ = x.shape
+        o = self._offset(x)
+        out = new_act(x.t, 2 * H, 2 * W, x.c)
+        ops.dysample(x.t, o.t, self._init_pos(x.t.device), x.c, self.groups, x.coff, o.coff, out=out.t)
+        if self.training:
+            self.__dict__['_ctx'] = (x, o)
+        return out
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """The kernels write dx's sampling part and the raw offsets' gradient; the offset conv's backward then adds into that dx."""
+        x, o = self.__dict__.pop('_ctx')
+        dx = _up_backward_target(dout, x, dx_out, accumulate)
+        _, do = ops.dysample_backward(dout.t, x.t, o.t, self._init_pos(x.t.device), x.c, self.groups, dout.coff, x.coff, o.coff, out=dx.t,
+                                      dx_coff=dx.coff)
+        self._offset.backward(do, dx_out=dx, accumulate=True)
+        return _up_backward_result(dx, dx_out, accumulate, need_dx)
 
 
 class ODConv2d_3rd(_Packed):

@@ -63,13 +63,30 @@ HYP_VISDRONE = dict(lr0=0.0032, lrf=0.12, momentum=0.843, weight_decay=0.00036, 
 """Loss-relevant keys of data/hyps/hyp.VisDrone.yaml (values are configuration data)."""
 
 
-def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8):
+UPSAMPLE_ROWS = {'nearest': None, 'carafe': ['CARAFE', [3, 5]], 'dysample': ['DySample', []]}
+"""upsample= of somi_cfg / yolov5_cfg / yolov10_cfg -> what stands in the tables' nn.Upsample rows: the reference's two learned 2x drop-ins
+(models/common.py:4450 CARAFE with its docstring's [3, 5] = k_enc, k_up; :4246 DySample with its defaults) or the rows as they are."""
+
+
+def _swap_upsample(rows, upsample):
+    """Rewrites every nn.Upsample row of a layer table in place (same `from`, same output size and channels: nothing else moves)."""
+    if upsample not in UPSAMPLE_ROWS:
+        raise ValueError(f'upsample={upsample!r} (one of {sorted(UPSAMPLE_ROWS)})')
+    swap = UPSAMPLE_ROWS[upsample]
+    if swap is None:
+        return rows
+    import copy
+    return [[r[0], r[1], *copy.deepcopy(swap)] if r[2] == 'nn.Upsample' else r for r in rows]
+
+
+def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8, upsample='nearest'):
     """The layer table of models/modules/YOLO-SOMI.yaml as a dict (C2fEACBAM -> C2fCBAM).
 
     dcn=True: "yolov5l-SOMI (DCNv3 blocks)" of BASELINE configs[1].  The reference vendors DCNv3 but wires it into no yaml (SURVEY
     fact 3), so the sites are the build's choice: one DCNv3_YOLO block (DCNv3 -> BN -> SiLU, 3x3, `dcn_group` groups) behind each of
     the two high-resolution lateral convs of the neck - P2 (160x160 at 640) and P3 (80x80), 256 channels: the representative
-    shapes of SURVEY section 8a row F10.  Later layers shift by one / two; their `from` indices are rewritten accordingly."""
+    shapes of SURVEY section 8a row F10.  Later layers shift by one / two; their `from` indices are rewritten accordingly.
+    upsample='carafe' | 'dysample': the neck's three nn.Upsample rows become the learned upsampler (UPSAMPLE_ROWS)."""
     bb = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'ODConv_3rd', [128, 3, 2, 4]], [-1, 3, 'C2fCBAM', [128, True]],
           [-1, 1, 'Conv', [256, 3, 2]], [-1, 6, 'C2fCBAM', [256, True]], [-1, 1, 'Conv', [512, 3, 2]],
           [-1, 6, 'C2fCBAM', [512, True]], [-1, 1, 'Conv', [1024, 3, 2]], [-1, 3, 'C2fCBAM', [1024, True]],
@@ -96,17 +113,18 @@ def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8):
             if l[2] != 'DCNv3_YOLO':
                 l[0] = [{10: 11, 12: 13}.get(j, j) for j in l[0]] if isinstance(l[0], list) else {10: 11, 12: 13}.get(l[0], l[0])
         bb, hd = layers[:len(bb)], layers[len(bb):]
-    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors), backbone=bb, head=hd)
+    return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors), backbone=bb, head=_swap_upsample(hd, upsample))
 
 
 COCO_ANCHORS = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
 """The stock YOLOv5 P3-P5 anchors (upstream yolov5s.yaml; the reference ships no yolov5s.yaml, SURVEY section 2 #21)."""
 
 
-def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0'):
+def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0', upsample='nearest'):
     """Stock YOLOv5 layer tables authored here (BASELINE configs[0]; the reference ships none): version '6.0' = Conv 6x6 stem + SPPF
     (upstream yolov5s.yaml of the release this fork is based on); '5.0' = Focus stem + SPP(5,9,13), which exercises the remaining
-    stock modules.  Defaults are yolov5s (depth 0.33, width 0.50, 80 classes -> 7,235,389 parameters for '6.0')."""
+    stock modules.  Defaults are yolov5s (depth 0.33, width 0.50, 80 classes -> 7,235,389 parameters for '6.0').
+    upsample='carafe' | 'dysample': the head's two nn.Upsample rows become the learned upsampler (UPSAMPLE_ROWS)."""
     import copy
     if version == '6.0':
         bb = [[-1, 1, 'Conv', [64, 6, 2, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'C3', [128]], [-1, 1, 'Conv', [256, 3, 2]],
@@ -123,7 +141,7 @@ def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0'):
           [-1, 1, 'Conv', [512, 3, 2]], [[-1, 10], 1, 'Concat', [1]], [-1, 3, 'C3', [1024, False]],
           [[17, 20, 23], 1, 'Detect', ['nc', 'anchors']]]
     return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors or COCO_ANCHORS),
-                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+                backbone=copy.deepcopy(bb), head=_swap_upsample(copy.deepcopy(hd), upsample))
 
 
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
@@ -143,11 +161,12 @@ def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
                 backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
 
 
-def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None):
+def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None, upsample='nearest'):
     """The layer table of models/hub/yolov10.yaml as a dict: Conv / C2f / SCDown backbone, C2fCIB at P5, SPPF, PSA, a C2f / C2fCIB PAN head
     and the plain Detect.  Defaults are the yaml's (depth 1.0, width 1.0, 10 classes).  anchors=None gives the COCO anchors: the yaml's
     `anchors: 3` is a placeholder (list(range(6)) per level) that only makes sense after autoanchor; anchors=3 reproduces the yaml exactly -
-    `somi_amd.autoanchor.check_anchors(dataset, model)` then replaces the placeholder from the data set's labels."""
+    `somi_amd.autoanchor.check_anchors(dataset, model)` then replaces the placeholder from the data set's labels.
+    upsample='carafe' | 'dysample': the head's two nn.Upsample rows become the learned upsampler (UPSAMPLE_ROWS)."""
     import copy
     bb = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'Conv', [128, 3, 2]], [-1, 3, 'C2f', [128, True]], [-1, 1, 'Conv', [256, 3, 2]],
           [-1, 6, 'C2f', [256, True]], [-1, 1, 'SCDown', [512, 3, 2]], [-1, 6, 'C2f', [512, True]], [-1, 1, 'SCDown', [1024, 3, 2]],
@@ -160,7 +179,7 @@ def yolov10_cfg(width=1.0, depth=1.0, nc=10, anchors=None):
           [[16, 19, 22], 1, 'Detect', ['nc', 'anchors']]]
     anchors = COCO_ANCHORS if anchors is None else anchors
     return dict(nc=nc, depth_multiple=depth, width_multiple=width, anchors=copy.deepcopy(anchors),
-                backbone=copy.deepcopy(bb), head=copy.deepcopy(hd))
+                backbone=copy.deepcopy(bb), head=_swap_upsample(copy.deepcopy(hd), upsample))
 
 
 YOLOV3_TINY_ANCHORS = [[10, 14, 23, 27, 37, 58], [81, 82, 135, 169, 344, 319]]

@@ -7,7 +7,8 @@ raw_l = (B,na,ny,nx,no).  Input is the reference's `(B,3,H,W)` NCHW batch, eithe
 section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, Concat, Detect - BASELINE configs[0]) and the Ghost set
 of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv), the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
 C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny, yolov5-fpn / -panet / -p6 / -p7): BottleneckCSP,
-nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels.
+nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; and the two learned
+drop-ins for the neck's nn.Upsample rows, CARAFE and DySample.
 """
 import math
 from copy import deepcopy
@@ -64,6 +65,14 @@ def parse_model(d, ch):
             args = [len(f)]
         elif name == 'nn.Upsample':
             m = B.Upsample
+            c2 = ch[f]
+        elif name == 'CARAFE':                                    # models/yolo.py:1540-1542
+            m = B.CARAFE
+            c2 = ch[f]
+            args = [c2, *args]
+        elif name == 'DySample':                                  # models/yolo.py:1572-1574
+            m = B.DySample
+            args.insert(0, ch[f])
             c2 = ch[f]
         elif name in _PASS_THROUGH:                               # parameter-free, channels pass through
             m = _PASS_THROUGH[name]
@@ -168,7 +177,7 @@ class Model(nn.Module):
             return 2 * m.conv.conv.stride[0]
         if isinstance(m, B.ODConv_3rd):
             return m.conv.stride
-        if isinstance(m, B.Upsample):
+        if isinstance(m, (B.Upsample, B.CARAFE, B.DySample)):
             return 0.5
         if isinstance(m, B.MaxPool2d):                            # stride 2 halves the map; yolov3-tiny's padded stride-1 pool keeps it
             return m.stride

@@ -385,6 +385,112 @@ def spp_pool_backward_(dbuf, codes, c, k, x_coff=0):
     return dbuf
 
 
+def _up_out(x, c, out, what):
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, 2 * H, 2 * W, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, 2 * H, 2 * W):
+        raise RuntimeError(f'{what}: output must be ({B}, {2 * H}, {2 * W}, .), got {tuple(out.shape)}')
+    return out
+
+
+def carafe(x, logits, c, k_up, x_coff=0, l_coff=0, *, out=None, y_coff=0, weights=False):
+    """CARAFE's reassembly (models/common.py:4482-4489) of slice [x_coff, x_coff + c) of x (B,H,W,cs) by the 4 * k_up^2 encoder logits in slice
+    [l_coff, ...) of `logits` (B,H,W,*) -> out (B,2H,2W,*) slice at y_coff.  weights=True (training): -> (out, weights), the softmax weights
+    (B,2H,2W,k_up^2) carafe_backward needs - nothing else is kept."""
+    B, H, W, _ = x.shape
+    if tuple(logits.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'carafe: logits must be ({B}, {H}, {W}, .), got {tuple(logits.shape)}')
+    out = _up_out(x, c, out, 'carafe')
+    wts = torch.empty(B, 2 * H, 2 * W, k_up * k_up, device=x.device, dtype=torch.float32) if weights else None
+    check(_lib.lib().somi_carafe_nhwc_f32(_ptr(_f32c(x)), _ptr(_f32c(logits)), _ptr(_f32c(out)), _ptr(wts), B, H, W, c, int(k_up), x.shape[3], x_coff,
+                                          logits.shape[3], l_coff, out.shape[3], y_coff, _stream()), 'carafe')
+    return (out, wts) if weights else out
+
+
+def carafe_backward(dy, x, weights, c, k_up, dy_coff=0, x_coff=0, *, out=None, dx_coff=0, dlogits=None, dl_coff=0):
+    """-> (dx, dlogits): dx (B,H,W,*) slice at dx_coff, written (not added), and the gradient of the encoder logits (B,H,W,*) slice at dl_coff in the
+    logits' own channel layout, from dy (B,2H,2W,*), x and carafe's softmax weights.  Owner-computes, fixed order, no float atomics."""
+    B, H, W, _ = x.shape
+    kk = int(k_up) * int(k_up)
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if dlogits is None:
+        dlogits = torch.empty(B, H, W, 4 * kk, device=x.device, dtype=torch.float32)
+    if (tuple(dy.shape[:3]) != (B, 2 * H, 2 * W) or tuple(out.shape[:3]) != (B, H, W) or tuple(dlogits.shape[:3]) != (B, H, W) or
+            tuple(weights.shape) != (B, 2 * H, 2 * W, kk)):
+        raise RuntimeError(f'carafe_backward: dy must be ({B}, {2 * H}, {2 * W}, .), dx and dlogits ({B}, {H}, {W}, .), weights ({B}, {2 * H}, {2 * W}, {kk})')
+    check(_lib.lib().somi_carafe_bwd_nhwc_f32(_ptr(_f32c(dy)), _ptr(_f32c(x)), _ptr(_f32c(weights)), _ptr(_f32c(out)), _ptr(_f32c(dlogits)), B, H, W, c,
+                                              int(k_up), dy.shape[3], dy_coff, x.shape[3], x_coff, out.shape[3], dx_coff, dlogits.shape[3], dl_coff,
+                                              _stream()), 'carafe_backward')
+    return out, dlogits
+
+
+_DYS_LAST = None         # the far-tap word of the last dysample_backward (device int32)
+_DYS_FAR = {}            # device -> int64 device counter: far taps of every dysample_backward since the last reset
+
+
+def dysample_far_taps(total=False):
+    """FAR bilinear corners of DySample's backward - those added to dx as fp32 atomics because they landed more than 2 pixels from their source pixel
+    (0 <=> bit-reproducible), the policy of dcn_overflow_taps.  Default: the last call only (None before any).  total=True: summed over every call on
+    every device since reset_dysample_far_taps().  Host sync; diagnostics / tests."""
+    if total:
+        return int(sum(int(t.item()) for t in _DYS_FAR.values()))
+    return None if _DYS_LAST is None else int(_DYS_LAST.item())
+
+
+def reset_dysample_far_taps():
+    for t in _DYS_FAR.values():
+        t.zero_()
+
+
+def _dysample_args(x, offset, init_pos, c, groups, what):
+    B, H, W, _ = x.shape
+    if tuple(offset.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'{what}: offset must be ({B}, {H}, {W}, .), got {tuple(offset.shape)}')
+    if init_pos.numel() != 8 * groups or init_pos.dtype != torch.float32 or not init_pos.is_contiguous():
+        raise RuntimeError(f'{what}: init_pos must hold {8 * groups} contiguous float32 values')
+    if c % groups or (c // groups) % 4:
+        raise RuntimeError(f'{what}: needs c % groups == 0 and (c / groups) % 4 == 0, got c={c}, groups={groups}')
+    return B, H, W
+
+
+def dysample(x, offset, init_pos, c, groups, x_coff=0, f_coff=0, *, out=None, y_coff=0):
+    """DySample's 'lp' sampling (models/common.py:4277-4296) of slice [x_coff, x_coff + c) of x (B,H,W,cs) at the positions the RAW offset-conv output in
+    slice [f_coff, f_coff + 8 * groups) of `offset` gives (the 0.25, init_pos, the border clamp and the pixel shuffle happen in the kernel)
+    -> out (B,2H,2W,*) slice at y_coff."""
+    B, H, W = _dysample_args(x, offset, init_pos, c, groups, 'dysample')
+    out = _up_out(x, c, out, 'dysample')
+    check(_lib.lib().somi_dysample_nhwc_f32(_ptr(_f32c(x)), _ptr(_f32c(offset)), _ptr(init_pos), _ptr(_f32c(out)), B, H, W, c, int(groups), x.shape[3],
+                                            x_coff, offset.shape[3], f_coff, out.shape[3], y_coff, _stream()), 'dysample')
+    return out
+
+
+def dysample_backward(dy, x, offset, init_pos, c, groups, dy_coff=0, x_coff=0, f_coff=0, *, out=None, dx_coff=0, doffset=None, df_coff=0):
+    """-> (dx, doffset): dx (B,H,W,*) slice at dx_coff, written (not added), and the gradient of the raw offset-conv output (B,H,W,*) slice at df_coff in
+    its own layout (0.25 included, 0 where the coordinate was clamped).  dx is owner-computes up to 2 pixels of reach; corners beyond go through fp32
+    atomics and are counted (dysample_far_taps)."""
+    global _DYS_LAST
+    B, H, W = _dysample_args(x, offset, init_pos, c, groups, 'dysample_backward')
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if doffset is None:
+        doffset = torch.empty(B, H, W, 8 * groups, device=x.device, dtype=torch.float32)
+    if tuple(dy.shape[:3]) != (B, 2 * H, 2 * W) or tuple(out.shape[:3]) != (B, H, W) or tuple(doffset.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'dysample_backward: dy must be ({B}, {2 * H}, {2 * W}, .), dx and doffset ({B}, {H}, {W}, .)')
+    far = torch.zeros(1, device=x.device, dtype=torch.int32)
+    check(_lib.lib().somi_dysample_bwd_nhwc_f32(_ptr(_f32c(dy)), _ptr(_f32c(x)), _ptr(_f32c(offset)), _ptr(init_pos), _ptr(_f32c(out)),
+                                                _ptr(_f32c(doffset)), _ptr(far), B, H, W, c, int(groups), dy.shape[3], dy_coff, x.shape[3], x_coff,
+                                                offset.shape[3], f_coff, out.shape[3], dx_coff, doffset.shape[3], df_coff, _stream()),
+          'dysample_backward')
+    _DYS_LAST = far
+    tot = _DYS_FAR.get(x.device)
+    if tot is None:
+        tot = _DYS_FAR[x.device] = torch.zeros(1, dtype=torch.int64, device=x.device)
+    tot.add_(far)
+    return out, doffset
+
+
 def bifpn(srcs, ups, w_dev, eps=1e-4, out=None):
     """y = sum_i w_i / (sum_j swish(w_j) + eps) * src_i; `w_dev` is the raw fusion parameter on the device."""
     n = len(srcs)
