@@ -193,3 +193,28 @@ def check_checkpoint_roundtrip(ref, imgs, foreign_prefixes, what):
     want_model = copy.deepcopy(ref).half().float().eval()
     with torch.no_grad():
         rel_close(loaded(imgs.cuda())[0], want_model(imgs.float() / 255)[0], what=f'{what} z from the loaded checkpoint')
+
+
+def check_accumulate_contract(block, x, c, gen, tag, device='cuda'):
+    """The accumulate contract of a block that declares it (`accumulates`), on a deep copy of the built `block`: a training forward and
+    backward(dy) give dx; the same forward again and backward(dy, dx_out=have, accumulate=True) must leave R + dx in have[..., :c], where `have`
+    is a whole padded contiguous tensor drawn from `gen` (pad channels zero) and R what it held before the call.
+    x: the NHWC input (pad4(c) wide, pad channels zero), c its logical channels."""
+    from somi_amd.blocks import Act, pad4
+    blk = bn_hyper(copy.deepcopy(block)).to(device).train()
+    assert type(blk).accumulates, f'{tag}: {type(blk).__name__} does not declare the accumulate contract'
+    x = x.to(device)
+    y = blk(Act(x.clone(), 0, c))
+    dy = torch.randn(y.t.shape, generator=gen)
+    dy[..., y.coff + y.c:] = 0
+    dy = dy.to(device)
+    dx = blk.backward(Act(dy.clone(), y.coff, y.c))
+    dx = dx.t[..., dx.coff:dx.coff + c].clone()
+    blk(Act(x.clone(), 0, c))
+    have = torch.randn(*x.shape[:3], pad4(c), generator=gen)
+    have[..., c:] = 0
+    have = have.to(device)
+    before = have[..., :c].clone()
+    got = blk.backward(Act(dy.clone(), y.coff, y.c), dx_out=Act(have, 0, c), accumulate=True)
+    assert got.t.data_ptr() == have.data_ptr() and got.coff == 0, f'{tag}: backward(dx_out=) returned another tensor'
+    rel_close(have[..., :c], before + dx, what=f'{tag}: dx_out after backward(accumulate=True) against R + dx')

@@ -70,10 +70,14 @@ def autopad(k, p=None, d=1):
 class _Packed(nn.Module):
     """Mixin: device-side packed parameters are rebuilt lazily after any parameter change."""
 
+    def _pack_params(self):
+        """The parameters _pack reads (they key the cache); a block whose children pack themselves names its own."""
+        return self.parameters()
+
     def _packed(self, dev):
         # in-place edits through torch (load_state_dict, copy_) bump the version counters; the fused optimizer writes through
         # raw pointers and calls Model.invalidate() itself
-        key = (dev, self.training, tuple(p._version for p in self.parameters()))
+        key = (dev, self.training, tuple(p._version for p in self._pack_params()))
         cache = self.__dict__.get('_pk')
         if cache is None or cache[0] != key:
             with torch.no_grad():
@@ -94,24 +98,54 @@ def _acc_grad(param, g):
         param.grad.add_(g)
 
 
-def _grad_target(param):
-    """Buffer a backward kernel may accumulate into directly: the parameter's gradient when it is a contiguous fp32 tensor
-    (the optimizer's flat views are), else a zero scratch that the caller adds with _acc_grad.  -> (buffer, is_scratch)"""
-    g = param.grad
-    if g is not None and g.is_contiguous() and g.dtype == torch.float32:
-        return g, False
-    return torch.zeros_like(param, dtype=torch.float32), True
-
-
 def _grad_targets(*params):
-    """_grad_target for several parameters -> (buffers, finish): the kernels accumulate into `buffers`, finish() adds the scratch ones (if any) to .grad."""
-    tg = [_grad_target(p_) for p_ in params]
+    """Buffers a backward kernel may accumulate into directly: each parameter's gradient when it is a contiguous fp32 tensor (the optimizer's
+    flat views are), else a zero scratch.  -> (buffers, finish): finish() adds the scratch ones (if any) to .grad with _acc_grad."""
+    direct = [p_.grad is not None and p_.grad.is_contiguous() and p_.grad.dtype == torch.float32 for p_ in params]
+    bufs = [p_.grad if d else torch.zeros_like(p_, dtype=torch.float32) for p_, d in zip(params, direct)]
 
     def finish():
-        for p_, (buf, scratch) in zip(params, tg):
-            if scratch:
+        for p_, buf, d in zip(params, bufs, direct):
+            if not d:
                 _acc_grad(p_, buf)
-    return [t[0] for t in tg], finish
+    return bufs, finish
+
+
+def _plain_conv_backward(conv, src, dy, wt=None, *, dy_coff=0, dx_out=None, accumulate=False, need_dx=True, direct=()):
+    """Backward of a plain nn.Conv2d (stride 1, pad k // 2; no norm, no activation) that read the Act `src`: weight and bias gradients into .grad,
+    -> the data gradient as an Act (written into dx_out if given, added to it if accumulate; None without need_dx).
+    dy: gradient tensor w.r.t. the output, pad4(out_channels) wide from channel dy_coff (pad channels zero).  wt: the weight packed for the
+    data-gradient kernel (packed here when None).  direct: which of 'weight' / 'bias' the kernels accumulate straight into .grad when it is
+    a contiguous fp32 tensor and nothing is padded (the weight of a 1x1 conv only); the others go through a scratch tensor and _acc_grad."""
+    k = conv.kernel_size[0]
+    c1, c2 = conv.in_channels, conv.out_channels
+    c1p, cp = pad4(c1), pad4(c2)
+    g = conv.weight.grad
+    if ('weight' in direct and k == 1 and c1p == c1 and cp == c2 and g is not None and g.is_contiguous() and g.dtype == torch.float32 and
+            g.device == dy.device):
+        gv = g.view(c2, c1)                                       # the optimizer's flat view: the kernel adds to it in place
+        ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=cp, dy_coff=dy_coff, out=gv, accumulate=gv)
+    else:
+        dw = ops.conv2d_wgrad_nhwc(src.t, dy, kh=k, kw=k, stride=1, pad=k // 2, cin=c1p, x_coff=src.coff, cout=cp, dy_coff=dy_coff)
+        _acc_grad(conv.weight, dw.view(cp, k, k, c1p)[:c2, :, :, :c1].permute(0, 3, 1, 2))
+    if conv.bias is not None:
+        if 'bias' in direct and cp == c2:
+            (db,), fin = _grad_targets(conv.bias)
+        else:
+            db = torch.zeros(cp, device=dy.device)
+            fin = lambda: _acc_grad(conv.bias, db[:c2])          # noqa: E731
+        ops.chan_sum_(dy, cp, dy_coff, db)
+        fin()
+    if not need_dx:
+        return None
+    if wt is None:
+        wt = pack_dgrad_weight(conv.weight.detach().float()).to(dy.device)
+    B, H, W, _ = src.shape
+    if dx_out is None:
+        dx_out = Act(torch.empty(B, H, W, c1p, device=dy.device, dtype=torch.float32), 0, c1)
+    ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1p, kh=k, kw=k, stride=1, pad=k // 2, cout=cp, dy_coff=dy_coff, out=dx_out.t,
+                          dx_coff=dx_out.coff, accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff)
+    return dx_out
 
 
 _NBT_PENDING = None      # Model.forward collects the BatchNorm step counters here and bumps them with one multi-tensor add
@@ -138,6 +172,75 @@ class collect_batches_tracked:
         if pending and exc[0] is None:
             torch._foreach_add_(pending, 1)
         return False
+
+
+# ------------------------------------------------------------------------------------------------ BatchNorm in training mode
+def _bn_vectors(bn, dev, cp):
+    """The BatchNorm vectors as the kernels read them, cp >= num_features wide: the module's own tensors when nothing is padded (the running
+    statistics then update in place), else padded device copies (gamma / beta / mean 0 and variance 1 in the pad channels)."""
+    c2 = bn.num_features
+    if cp == c2 and bn.weight.device == dev:
+        return dict(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var, inplace=True)
+    padv = lambda t, fill: torch.cat([t.detach().float().to(dev), torch.full((cp - c2,), fill, device=dev)])   # noqa: E731
+    return dict(gamma=padv(bn.weight, 0.), beta=padv(bn.bias, 0.), rm=padv(bn.running_mean, 0.), rv=padv(bn.running_var, 1.), inplace=False)
+
+
+def _bn_clones(bn):
+    """_bn_vectors of a layer that packs nothing: the module's parameters and clones of its running statistics for the kernel to update."""
+    return dict(gamma=bn.weight.detach().float().contiguous(), beta=bn.bias.detach().float().contiguous(),
+                rm=bn.running_mean.detach().clone(), rv=bn.running_var.detach().clone(), inplace=False)
+
+
+def _bn_train(bn, c, x=None, *, coff=0, act='none', partials=None, npix=None, vec=None):
+    """Forward half of a training BatchNorm over c channels: batch statistics of x's channel slice at coff (of act(x) when given, never stored)
+    or from the partial sums a conv epilogue left (partials = the dict that launch filled, over npix pixels; its pivot is vec['rm']), the
+    running statistics updated in `vec` (_bn_vectors / slices of it; _bn_clones(bn) when None).
+    -> ((mean, rstd, scale, shift), commit): commit() writes the running statistics back to the module where `vec` holds copies and bumps
+    num_batches_tracked - call it once per forward of `bn`, after the launches that today precede the write-back."""
+    vec = _bn_clones(bn) if vec is None else vec
+    if partials is not None:
+        st = ops.bn_stats_from_partials(partials['part'], partials['rows'], npix, c, vec['gamma'], vec['beta'], bn.eps, bn.momentum,
+                                        vec['rm'], vec['rv'])
+    else:
+        st = ops.bn_stats(x, c, coff, vec['gamma'], vec['beta'], bn.eps, bn.momentum, vec['rm'], vec['rv'], act=act)
+
+    def commit():
+        with torch.no_grad():
+            if not vec['inplace']:
+                bn.running_mean.copy_(vec['rm'][:bn.num_features])
+                bn.running_var.copy_(vec['rv'][:bn.num_features])
+            _bump_batches_tracked(bn)
+    return st, commit
+
+
+def _bn_grad_targets(bn, cp, dev):
+    """_grad_targets of a BatchNorm's (weight, bias) for kernels that write cp >= num_features channels: padded scratch vectors when cp is wider."""
+    if cp == bn.num_features:
+        return _grad_targets(bn.weight, bn.bias)
+    bufs = [torch.zeros(cp, device=dev), torch.zeros(cp, device=dev)]
+
+    def finish():
+        _acc_grad(bn.weight, bufs[0][:bn.num_features])
+        _acc_grad(bn.bias, bufs[1][:bn.num_features])
+    return bufs, finish
+
+
+def _bn_backward(bn, dz, dz_coff, x, st, act, dx, c, *, coff=0, order=0, batch_stats=True, pooled=None, cp=None, targets=None):
+    """Backward half: gradient of act(BN(x)) (order 0) or BN(act(x)) (order 1) over the channel slice [coff, coff + c) of x and dx, from dz's
+    slice at dz_coff and the forward's st = (mean, rstd, scale, shift); gamma / beta gradients accumulated into .grad.  -> dx.
+    batch_stats=False: the forward normalised with fixed statistics (ODConv's squeeze at batch 1) - nothing for the parameters.
+    pooled: ops.bn_act_backward.  cp: the width the kernel writes the parameter gradients at (c when None).  targets: the (dgamma, dbeta)
+    slices of a caller that resolved the buffers itself and finishes them after several calls (BottleneckCSP's two halves)."""
+    if targets is not None:
+        (dg, db), fin = targets, None
+    elif batch_stats:
+        (dg, db), fin = _bn_grad_targets(bn, c if cp is None else cp, x.device)
+    else:
+        dg, db, fin = torch.zeros(c, device=x.device), torch.zeros(c, device=x.device), None
+    ops.bn_act_backward(dz, dz_coff, x, coff, c, *st, act, order, batch_stats, dx, coff, dg, db, pooled=pooled)
+    if fin:
+        fin()
+    return dx
 
 
 def _act_name(m):
@@ -194,6 +297,12 @@ class Conv(_Packed):
         self.bn = nn.BatchNorm2d(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
 
+    # What Model's graph walk reads of every block.  accumulates: backward(dout, dx_out=<whole padded contiguous tensor>,
+    # accumulate=True) adds the input gradient into dx_out in place.  folds_pooled: the closing Conv's BatchNorm + SiLU passes take a reader's global
+    # pools in forward(pool=) and fold a pending Act.pooled in backward(pooled=).  reduction: input map size / output map size.
+    accumulates = folds_pooled = True
+    reduction = property(lambda self: self.conv.stride[0])
+
     def _pack(self, dev):
         if self.conv.groups > 1:
             return self._pack_grouped(dev)
@@ -208,14 +317,7 @@ class Conv(_Packed):
             else:
                 wf = w.detach().float()
                 wp, gp, wt = pack_conv_weight(wf, cout_pad=cp).to(dev), None, pack_dgrad_weight(wf).to(dev)
-            bn = self.bn
-            if cp == c2 and bn.weight.device == dev:             # no padding: the module's own tensors, running statistics in place
-                vec = dict(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var, inplace=True)
-            else:
-                padv = lambda t, fill: torch.cat([t.detach().float().to(dev), torch.full((cp - c2,), fill, device=dev)])   # noqa: E731
-                vec = dict(gamma=padv(bn.weight, 0.), beta=padv(bn.bias, 0.), rm=padv(bn.running_mean, 0.), rv=padv(bn.running_var, 1.),
-                           inplace=False)
-            return dict(wp=wp, gp=gp, wt=wt, **vec)
+            return dict(wp=wp, gp=gp, wt=wt, **_bn_vectors(self.bn, dev, cp))
         return _pack_wb(*_fold_conv_bn(self.conv, getattr(self, 'bn', None)), dev)
 
     def _pack_grouped(self, dev):
@@ -226,13 +328,7 @@ class Conv(_Packed):
             bp = torch.zeros(cp, device=dev)
             bp[:c2] = b.to(dev)
             return pack_gconv_weight(w, cp).to(dev), bp
-        bn = self.bn
-        if cp == c2 and bn.weight.device == dev:
-            vec = dict(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var, inplace=True)
-        else:
-            padv = lambda t, fill: torch.cat([t.detach().float().to(dev), torch.full((cp - c2,), fill, device=dev)])   # noqa: E731
-            vec = dict(gamma=padv(bn.weight, 0.), beta=padv(bn.bias, 0.), rm=padv(bn.running_mean, 0.), rv=padv(bn.running_var, 1.), inplace=False)
-        return dict(gw=pack_gconv_weight(self.conv.weight.detach(), cp).to(dev), **vec)
+        return dict(gw=pack_gconv_weight(self.conv.weight.detach(), cp).to(dev), **_bn_vectors(self.bn, dev, cp))
 
     # ------------------------------------------------------------------------------------------ training mode
     def _forward_train(self, x, out, residual, pool=None):
@@ -245,27 +341,15 @@ class Conv(_Packed):
         B, H, W, _ = x.shape
         Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
         y = torch.empty(B, Ho, Wo, cp, device=x.t.device, dtype=torch.float32)
+        st = {'pivot': pk['rm']} if self.conv.groups > 1 or y.numel() * 4 <= 0xE0000000 else None     # the epilogue leaves y's per-channel partial sums
         if self.conv.groups > 1:                                 # grouped / depthwise: the same partial sums, from the stencil kernel
-            st = {'pivot': pk['rm']}
             ops.gconv2d_nhwc(x.t, pk['gw'], c1=self.conv.in_channels, c2=c2, groups=self.conv.groups, k=k, stride=s, x_coff=x.coff, out=y, cw=cp,
                              bn_stats=st)
-            mean, rstd, scale, shift = ops.bn_stats_from_partials(st['part'], st['rows'], B * Ho * Wo, cp, pk['gamma'], pk['beta'],
-                                                                  self.bn.eps, self.bn.momentum, pk['rm'], pk['rv'])
-        elif y.numel() * 4 <= 0xE0000000:                        # the conv epilogue leaves the per-channel partial sums of y
-            st = {'pivot': pk['rm']}
-            ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
-                            alg_cin=x.c, alg_cout=c2, bn_stats=st)
-            mean, rstd, scale, shift = ops.bn_stats_from_partials(st['part'], st['rows'], B * Ho * Wo, cp, pk['gamma'], pk['beta'],
-                                                                  self.bn.eps, self.bn.momentum, pk['rm'], pk['rv'])
         else:
             ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
-                            alg_cin=x.c, alg_cout=c2)
-            mean, rstd, scale, shift = ops.bn_stats(y, cp, 0, pk['gamma'], pk['beta'], self.bn.eps, self.bn.momentum, pk['rm'], pk['rv'])
-        with torch.no_grad():                                    # running statistics back into the module buffers
-            if not pk['inplace']:
-                self.bn.running_mean.copy_(pk['rm'][:c2])
-                self.bn.running_var.copy_(pk['rv'][:c2])
-            _bump_batches_tracked(self.bn)
+                            alg_cin=x.c, alg_cout=c2, bn_stats=st)
+        (mean, rstd, scale, shift), commit = _bn_train(self.bn, cp, y, partials=st, npix=B * Ho * Wo, vec=pk)
+        commit()                                                 # running statistics back into the module buffers
         if out is None:
             out = new_act(x.t, Ho, Wo, c2)
         elif c2 % 4:
@@ -301,23 +385,14 @@ class Conv(_Packed):
         cw = cp if (dz.coff == 0 and dz.t.shape[3] == cp) else c2     # whole padded tensor, or an aligned slice
         if cw % 4:
             raise NotImplementedError('training backward on a channel slice needs out_channels % 4 == 0')
-        gw, gb = self.bn.weight.grad, self.bn.bias.grad
-        direct = cp == c2 and gw is not None and gb is not None and gw.is_contiguous() and gb.is_contiguous() and gw.device == dev
         if cbam is not None:                                      # CBAM's step C + pooled gradients + BatchNorm backward in two passes over (dz, y)
             if cw != cp or cp != c2:
                 raise NotImplementedError('fused CBAM backward works on whole, unpadded tensors')
-            dgam, dbet = (gw, gb) if direct else (torch.zeros(cp, device=dev), torch.zeros(cp, device=dev))
+            (dgam, dbet), fin = _bn_grad_targets(self.bn, cp, dev)
             ops.cbam_bn_backward_apply(cbam, rstd, pooled[0], pooled[1], dy, dgam, dbet)
-            if not direct:
-                _acc_grad(self.bn.weight, dgam)
-                _acc_grad(self.bn.bias, dbet)
-        elif direct:                                              # the kernel accumulates straight into the gradient buffers
-            ops.bn_act_backward(dz.t, dz.coff, y, 0, cw, mean, rstd, scale, shift, _act_name(self.act), 0, True, dy, 0, gw, gb, pooled=pooled)
+            fin()
         else:
-            dgam, dbet = torch.zeros(cp, device=dev), torch.zeros(cp, device=dev)
-            ops.bn_act_backward(dz.t, dz.coff, y, 0, cw, mean, rstd, scale, shift, _act_name(self.act), 0, True, dy, 0, dgam, dbet, pooled=pooled)
-            _acc_grad(self.bn.weight, dgam[:c2])
-            _acc_grad(self.bn.bias, dbet[:c2])
+            _bn_backward(self.bn, dz.t, dz.coff, y, (mean, rstd, scale, shift), _act_name(self.act), dy, cw, pooled=pooled, cp=cp)
         B, H, W, _ = x.shape
         if self.conv.groups > 1:
             return self._backward_grouped(x, dy, pk, dx_out, accumulate, need_dx, also_add)
@@ -427,23 +502,9 @@ class PlainConv(_Packed):
             self.__dict__['_ctx'] = x
         return out
 
-    def backward(self, dy, dx_out=None, accumulate=False):
+    def backward(self, dy, dx_out=None, accumulate=False, need_dx=True):
         """dy: whole padded gradient tensor (pad channels zero).  Returns dx (Act): written into dx_out if given, added to it if accumulate."""
-        x = self.__dict__.pop('_ctx')
-        k = self.conv.kernel_size[0]
-        c1, c2 = self.conv.in_channels, self.conv.out_channels
-        cp = pad4(c2)
-        B, H, W, _ = x.shape
-        dw = ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=1, pad=k // 2, cin=pad4(c1), x_coff=x.coff, cout=cp)
-        _acc_grad(self.conv.weight, dw.view(cp, k, k, pad4(c1))[:c2, :, :, :c1].permute(0, 3, 1, 2))
-        db = torch.zeros(cp, device=dy.device)
-        ops.chan_sum_(dy, cp, 0, db)
-        _acc_grad(self.conv.bias, db[:c2])
-        wt = pack_dgrad_weight(self.conv.weight.detach().float()).to(dy.device)
-        dx = Act(torch.empty(B, H, W, pad4(c1), device=dy.device, dtype=torch.float32), 0, c1) if dx_out is None else dx_out
-        ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=pad4(c1), kh=k, kw=k, stride=1, pad=k // 2, cout=cp, out=dx.t, dx_coff=dx.coff,
-                              accumulate=dx.t if accumulate else None, acc_coff=dx.coff)
-        return dx
+        return _plain_conv_backward(self.conv, self.__dict__.pop('_ctx'), dy, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
 class ChannelAttentionModule(_Packed):
@@ -475,12 +536,9 @@ class ChannelAttentionModule(_Packed):
         amaxp (B,C) int32: first pixel of every channel's spatial maximum (the CBAM backward finds it in its own pass over x)."""
         x, avg, mx, ca, (W1, b1, W2, b2) = self.__dict__.pop('_ctx')
         l1, l2 = self.shared_MLP[0], self.shared_MLP[2]
-        prms = (l1.weight, l1.bias, l2.weight, l2.bias)
-        g = [_grad_target(prm) for prm in prms]                  # the kernel accumulates; same layout as the parameters
-        davg, dmax = ops.attn_mlp_backward(0, dca, ca, avg, mx, W1, b1, W2, g[0][0], g[1][0], g[2][0], g[3][0])
-        for prm, (gr, scratch) in zip(prms, g):
-            if scratch:
-                _acc_grad(prm, gr)
+        g, fin = _grad_targets(l1.weight, l1.bias, l2.weight, l2.bias)      # the kernel accumulates; same layout as the parameters
+        davg, dmax = ops.attn_mlp_backward(0, dca, ca, avg, mx, W1, b1, W2, *g)
+        fin()
         if defer:
             return davg, dmax, amaxp
         ops.pool_backward_add_(dt.t, dt.coff, x.c, davg, dmax, amaxp)
@@ -524,12 +582,9 @@ class SpatialAttentionModule(_Packed):
         backward(cbam=...) - is returned (ops.cbam_backward)."""
         x, ca, stats, sa, w = self.__dict__.pop('_ctx')
         k = self.cv1.kernel_size[0]
-        (dw, sw), (db, sb) = _grad_target(self.cv1.weight), _grad_target(self.cv1.bias)    # the kernel accumulates in nn.Conv2d's (1,2,k,k) layout
+        (dw, db), fin = _grad_targets(self.cv1.weight, self.cv1.bias)    # the kernel accumulates in nn.Conv2d's (1,2,k,k) layout
         res = ops.cbam_backward(dt2, x.t, x.coff, x.c, ca, sa, stats, w, k, dw, db, t_max=t_max, dw_chw=True, bn=bn)
-        if sw:
-            _acc_grad(self.cv1.weight, dw)
-        if sb:
-            _acc_grad(self.cv1.bias, db)
+        fin()
         return res
 
 
@@ -561,9 +616,11 @@ class CBAMBottleneck(nn.Module):
         c_ = self.cv1.conv.out_channels
         return ops.SYNC_BN is None and isinstance(self.cv1.act, nn.SiLU) and pad4(c_) == c_ and d.coff == t.coff == 0 and d.t.shape[3] == c_
 
-    def backward(self, dout, dx_out):
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         """dout: gradient w.r.t. the block output (Act); the input gradient is ADDED into dx_out (Act, e.g. a slice of the
-        C2f gradient buffer that already holds the gradient of the input's other consumers)."""
+        C2f gradient buffer that already holds the gradient of the input's other consumers) - the only form this block has."""
+        if dx_out is None or not accumulate or not need_dx:
+            raise NotImplementedError('CBAMBottleneck adds its input gradient into dx_out')
         x, t = self.__dict__.pop('_ctx')
         d = self.cv2.backward(dout)                               # d(t*ca*sa)
         bn = None
@@ -593,6 +650,8 @@ class C2fCBAM(nn.Module):
             CBAMBottleneck(self.c, self.c, shortcut, g, k=(3, 3), e=1.0, ratio=16, kernel_size=kernel_size)
             for _ in range(n))
 
+    accumulates, folds_pooled, reduction = True, True, 1
+
     def forward(self, x, pool=None):
         """pool: a dict the closing conv's BatchNorm + SiLU pass fills with the output's global average / max (Conv._forward_train)."""
         c, n = self.c, len(self.m)
@@ -605,13 +664,13 @@ class C2fCBAM(nn.Module):
             blk(cat.slice((1 + i) * c, c), out=cat.slice((2 + i) * c, c))
         return self.cv2(cat, pool=pool)
 
-    def backward(self, dout, dx_out=None, accumulate=False, pooled=None):
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True, pooled=None):
         """pooled: a pending part of dout that is constant over each image's pixels (Act.pooled): the closing conv's BatchNorm backward folds it in."""
         c, n = self.c, len(self.m)
         dcat = self.cv2.backward(dout, pooled=pooled)             # gradient of every piece through the 1x1 mix
         for i in reversed(range(n)):
-            self.m[i].backward(dcat.slice((2 + i) * c, c), dcat.slice((1 + i) * c, c))
-        return self.cv1.backward(dcat.slice(0, 2 * c), dx_out=dx_out, accumulate=accumulate)
+            self.m[i].backward(dcat.slice((2 + i) * c, c), dx_out=dcat.slice((1 + i) * c, c), accumulate=True)
+        return self.cv1.backward(dcat.slice(0, 2 * c), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
 class SPPF(nn.Module):
@@ -625,6 +684,8 @@ class SPPF(nn.Module):
         self.cv1 = Conv(c1, c_, 1, 1)
         self.cv2 = Conv(c_ * 4, c2, 1, 1)
 
+    accumulates, folds_pooled, reduction = True, False, 1
+
     def forward(self, x):
         c_ = self.cv1.conv.out_channels
         B, H, W, _ = x.shape
@@ -636,12 +697,12 @@ class SPPF(nn.Module):
             ops.sppf_pool_(cat.t, c_, 0)
         return self.cv2(cat)
 
-    def backward(self, dout, dx_out=None, accumulate=False):
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         cat, codes = self.__dict__.pop('_ctx')
         c_ = self.cv1.conv.out_channels
         dcat = self.cv2.backward(dout)
         ops.sppf_pool_backward_(cat.t, dcat.t, c_, 0, codes=codes)
-        return self.cv1.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate)
+        return self.cv1.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
 class Swish(nn.Module):
@@ -659,6 +720,8 @@ class BiFPN(_Packed):
         self.swish = Swish()
         self.epsilon = 0.0001
 
+    accumulates, folds_pooled, reduction = False, False, 1       # several inputs: backward(dout) returns the list of their gradients
+
     def forward(self, xs):
         for a in xs:
             if a.coff != 0 or a.t.shape[3] != xs[0].t.shape[3]:
@@ -674,10 +737,9 @@ class BiFPN(_Packed):
     def backward(self, dout):
         """Returns the list of input gradients (low-resolution for the virtually upsampled inputs)."""
         xs = self.__dict__.pop('_ctx')
-        dw, scratch = _grad_target(self.weight)
+        (dw,), fin = _grad_targets(self.weight)
         ds = ops.bifpn_backward([a.t for a in xs], [a.up for a in xs], self.weight.detach(), dout.t, dw, self.epsilon)
-        if scratch:
-            _acc_grad(self.weight, dw)
+        fin()
         return [Act(d, 0, a.c) for d, a in zip(ds, xs)]
 
 
@@ -689,11 +751,15 @@ class Upsample(nn.Module):
         if size is not None or scale_factor != 2 or mode != 'nearest':
             raise NotImplementedError('only 2x nearest upsampling is on the SOMI path')
 
+    accumulates, folds_pooled, reduction = False, False, 0.5
+
     def forward(self, x):
         return Act(x.t, x.coff, x.c, up=x.up + 1)
 
-    def backward(self, dout):
-        return dout                                              # the consumer (BiFPN) already produced the low-resolution gradient
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('Upsample hands its gradient through')
+        return dout if need_dx else None                         # the consumer (BiFPN) already produced the low-resolution gradient
 
 
 def _up_backward_target(dout, x, dx_out, accumulate):
@@ -734,6 +800,8 @@ class CARAFE(nn.Module):
         self.scale, self.k_up = scale, k_up
         self.comp = Conv(c, c_mid)
         self.enc = Conv(c_mid, (scale * k_up) ** 2, k=k_enc, act=False)
+
+    accumulates, folds_pooled, reduction = False, False, 0.5
 
     def forward(self, x):
         if x.up:
@@ -782,6 +850,8 @@ class DySample(nn.Module):
         h = torch.arange((-scale + 1) / 2, (scale - 1) / 2 + 1) / scale
         self.register_buffer('init_pos', torch.stack(torch.meshgrid(h, h, indexing='ij')).transpose(1, 2).repeat(1, groups, 1).reshape(1, -1, 1, 1))
         self.__dict__['_offset'] = PlainConv(self.offset)       # the runner shares the parameters, stays out of state_dict
+
+    accumulates, folds_pooled, reduction = False, False, 0.5
 
     def invalidate(self):
         self._offset.invalidate()
@@ -850,6 +920,12 @@ class ODConv_3rd(_Packed):
         self.bn = nn.BatchNorm2d(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
 
+    accumulates, folds_pooled = True, False
+    # the graph walk's hand-off with a producer that folds_pooled: the forward reads the global average that producer left in its input's Act.pool,
+    # backward(defer_pool=True) returns the squeeze gradient as the result's Act.pooled; dx_out has to be a whole UNPADDED tensor
+    squeezes_input = True
+    reduction = property(lambda self: self.conv.stride)
+
     # ------------------------------------------------------------------------------------------ training mode
     def _forward_train(self, x):
         cv = self.conv
@@ -866,12 +942,8 @@ class ODConv_3rd(_Packed):
         zpre = ops.linear(gap, fcw, None, 'none')
         one, zero = torch.ones(hid, device=dev), torch.zeros(hid, device=dev)
         if B > 1:                                                 # BatchNorm over the B samples (models/common.py:4562-4563)
-            rm, rv = cv.bn.running_mean.detach().clone(), cv.bn.running_var.detach().clone()
-            st = ops.bn_stats(zpre.view(B, 1, 1, hid), hid, 0, f(cv.bn.weight), f(cv.bn.bias), cv.bn.eps, cv.bn.momentum, rm, rv)
-            with torch.no_grad():
-                cv.bn.running_mean.copy_(rm)
-                cv.bn.running_var.copy_(rv)
-                _bump_batches_tracked(cv.bn)
+            st, commit = _bn_train(cv.bn, hid, zpre.view(B, 1, 1, hid))
+            commit()
         else:
             st = (zero, one, one, zero)
         z = ops.chan_affine_act(zpre.view(B, 1, 1, hid), hid, 0, st[2], st[3], 'relu', 0, torch.empty(B, 1, 1, hid, device=dev)).view(B, hid)
@@ -886,18 +958,14 @@ class ODConv_3rd(_Packed):
         Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
         y = torch.empty(B, Ho, Wo, cout, device=dev)
         ops.conv2d_nhwc(x.t, wout, bout, kh=k, kw=k, stride=s, pad=p, act='none', out=y, cout=cout, per_sample_w=True)
-        rm, rv = self.bn.running_mean.detach().clone(), self.bn.running_var.detach().clone()
-        so = ops.bn_stats(y, cout, 0, f(self.bn.weight), f(self.bn.bias), self.bn.eps, self.bn.momentum, rm, rv)
-        with torch.no_grad():
-            self.bn.running_mean.copy_(rm)
-            self.bn.running_var.copy_(rv)
-            _bump_batches_tracked(self.bn)
+        so, commit = _bn_train(self.bn, cout, y)
+        commit()
         out = torch.empty_like(y)
         ops.chan_affine_act(y, cout, 0, so[2], so[3], _act_name(self.act), 0, out)
         self.__dict__['_ctx'] = (x, gap, fcw, zpre, st, z, attn, heads, Wk, biask, wout, y, so)
         return Act(out, 0, cout)
 
-    def backward(self, dz, need_dx=True, dx_out=None, accumulate=False, defer_pool=False):
+    def backward(self, dz, dx_out=None, accumulate=False, need_dx=True, defer_pool=False):
         """dx_out / accumulate: the data gradient is written (added) into that Act (a whole tensor) by the dgrad epilogue.  defer_pool: the squeeze's
         gradient - constant over an image's pixels - is not added here by a pass of its own but handed on as the result's `pooled` part, for the
         producing Conv's BatchNorm backward to fold in."""
@@ -909,9 +977,7 @@ class ODConv_3rd(_Packed):
         cin, cout, kk, K = cv.in_channels, cv.out_channels, k * k, cv.K
         hid = fcw.shape[0]
         f = lambda t: t.detach().float().contiguous()            # noqa: E731
-        (dg, db), fin = _grad_targets(self.bn.weight, self.bn.bias)      # the kernel accumulates straight into .grad when it can
-        dy = ops.bn_act_backward(dz.t, dz.coff, y, 0, cout, *so, _act_name(self.act), 0, True, torch.empty_like(y), 0, dg, db)
-        fin()
+        dy = _bn_backward(self.bn, dz.t, dz.coff, y, so, _act_name(self.act), torch.empty_like(y), cout)
         # per-sample conv: bias, weight and data gradients
         dbias_b, _ = ops.global_pool(dy, want_max=False)
         dbias_b = dbias_b * float(dy.shape[1] * dy.shape[2])                  # sum over pixels = mean * HoWo
@@ -938,13 +1004,9 @@ class ODConv_3rd(_Packed):
             _acc_grad(lin.weight, gW)
             _acc_grad(lin.bias, gb)
         # relu + BatchNorm over the batch (or plain relu for one sample)
-        if B > 1:
-            (g2, b2), fin = _grad_targets(cv.bn.weight, cv.bn.bias)
-        else:                                                     # one sample: no BatchNorm in the forward (models/common.py:4562), nothing for its parameters
-            g2, b2, fin = torch.zeros(hid, device=dev), torch.zeros(hid, device=dev), lambda: None
-        dzpre = ops.bn_act_backward(dzv.view(B, 1, 1, hid), 0, zpre.view(B, 1, 1, hid), 0, hid, *st, 'relu', 0, B > 1,
-                                    torch.empty(B, 1, 1, hid, device=dev), 0, g2, b2).view(B, hid)
-        fin()
+        # (one sample: no BatchNorm in the forward (models/common.py:4562), nothing for its parameters)
+        dzpre = _bn_backward(cv.bn, dzv.view(B, 1, 1, hid), 0, zpre.view(B, 1, 1, hid), st, 'relu', torch.empty(B, 1, 1, hid, device=dev), hid,
+                             batch_stats=B > 1).view(B, hid)
         gfc = torch.zeros_like(fcw)
         dgap = torch.empty_like(gap) if need_dx else None
         ops.linear_backward(gap, fcw, dzpre, dzpre, 0, 'none', gfc, None, dgap)
@@ -1039,33 +1101,24 @@ class SEAM(_Packed):
                     W1=f(self.fc[0].weight), W2=f(self.fc[2].weight))
 
     # ------------------------------------------------------------------------------------------ training mode
+    accumulates, folds_pooled, reduction = False, False, 1
+
     def _bn_train(self, u, bn, residual=None):
         """z = BN_batch(GELU(u)) [+ residual] (act before the norm, models/common.py:8455-8457; the Residual wrapper's add :7183 rides the same
         pass); returns z and the saved statistics."""
         dev, c = u.device, u.shape[3]
-        rm, rv = bn.running_mean.detach().clone(), bn.running_var.detach().clone()
         if ops.SYNC_BN is None:
             # two passes over u: the statistics of gelu(u) taken on the fly, then z = gelu(u) * scale + shift (order 1) - gelu(u) is never stored
             # (the backward reads u too); three passes and a tensor less than act -> statistics -> affine
-            st = ops.bn_stats(u, c, 0, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, rm, rv, act='gelu')
+            st, commit = _bn_train(bn, c, u, act='gelu')
             z = ops.chan_affine_act(u, c, 0, st[2], st[3], 'gelu', 1, torch.empty_like(u), residual=residual)
         else:
+            vec = _bn_clones(bn)
             g = ops.chan_affine_act(u, c, 0, torch.ones(c, device=dev), torch.zeros(c, device=dev), 'gelu', 0, torch.empty_like(u))
-            st = ops.bn_stats(g, c, 0, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, rm, rv)
+            st, commit = _bn_train(bn, c, g, vec=vec)
             z = ops.chan_affine_act(g, c, 0, st[2], st[3], 'none', 0, g, residual=residual)
-        with torch.no_grad():
-            bn.running_mean.copy_(rm)
-            bn.running_var.copy_(rv)
-            _bump_batches_tracked(bn)
-        return z, tuple(st)
-
-    def _bn_backward(self, dz, u, st, bn, pooled=None):
-        """gradient w.r.t. u of BN_batch(GELU(u)) (order 1), parameter gradients accumulated.  pooled: ops.bn_act_backward (dz may then be None)."""
-        c = u.shape[3]
-        (dg, db), fin = _grad_targets(bn.weight, bn.bias)
-        du = ops.bn_act_backward(dz, 0, u, 0, c, *st, 'gelu', 1, True, torch.empty_like(u), 0, dg, db, pooled=pooled)
-        fin()
-        return du
+        commit()
+        return z, st
 
     def _forward_train(self, x):
         self.invalidate()
@@ -1079,13 +1132,8 @@ class SEAM(_Packed):
         if ops.SYNC_BN is None:
             # BN(GELU(u2)) is read by the global average pool only, and the mean of an affine map is the affine map of the mean: the statistics pass,
             # then ONE pass that averages gelu(u2) per image and applies scale / shift to the (B,C) result - the normalised tensor is never written
-            bn2 = st[3]
-            rm, rv = bn2.running_mean.detach().clone(), bn2.running_var.detach().clone()
-            s2 = tuple(ops.bn_stats(u2, c := u2.shape[3], 0, bn2.weight.detach(), bn2.bias.detach(), bn2.eps, bn2.momentum, rm, rv, act='gelu'))
-            with torch.no_grad():
-                bn2.running_mean.copy_(rm)
-                bn2.running_var.copy_(rv)
-                _bump_batches_tracked(bn2)
+            s2, commit = _bn_train(st[3], c := u2.shape[3], u2, act='gelu')
+            commit()
             avg = ops.global_pool_act(u2, 'gelu', s2[2], s2[3], c=c)
         else:
             y2, s2 = self._bn_train(u2, st[3])
@@ -1094,7 +1142,9 @@ class SEAM(_Packed):
         self.__dict__['_ctx'] = (x, u0, s0, y0, u1, s1, y1, u2, s2, avg, sc, pk)
         return Act(ops.scale_channels(x.t, sc), 0, x.c)
 
-    def backward(self, dout):
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('SEAM writes its own input gradient')
         x, u0, s0, y0, u1, s1, y1, u2, s2, avg, sc, pk = self.__dict__.pop('_ctx')
         d, st = self.DCovN, self.DCovN[3]
         c = x.c
@@ -1105,24 +1155,19 @@ class SEAM(_Packed):
         fin()
         # y2 is read by the global average pool only: its gradient is davg / HW at every pixel - handed to the BatchNorm backward as such
         # (no zero tensor filled, added to and read twice)
-        du2 = self._bn_backward(None, u2, s2, st[3], pooled=(davg, None, None))
-        dwp = ops.conv2d_wgrad_nhwc(y1, du2, kh=1, kw=1)
-        _acc_grad(st[1].weight, dwp.view(c, c, 1, 1))
-        (dbp,), fin = _grad_targets(st[1].bias)
-        ops.chan_sum_(du2, c, 0, dbp)
-        fin()
-        dy1 = ops.conv2d_dgrad_nhwc(du2, pk['pwt'], B=x.shape[0], H=x.shape[1], W=x.shape[2], cin=c, kh=1, kw=1)
-        du1 = self._bn_backward(dy1, u1, s1, st[0].fn[2])
+        du2 = _bn_backward(st[3], None, 0, u2, s2, 'gelu', torch.empty_like(u2), c, order=1, pooled=(davg, None, None))     # of BN(GELU(u)): order 1
+        dy1 = _plain_conv_backward(st[1], Act(y1), du2, pk['pwt'], direct=('bias',)).t
+        du1 = _bn_backward(st[0].fn[2], dy1, 0, u1, s1, 'gelu', torch.empty_like(u1), c, order=1)
         gw, gb = torch.zeros_like(pk['dw1']), torch.zeros(c, device=dev)
         dy0 = ops.dwconv3x3_backward(du1, y0, pk['dw1'], gw, gb, dx_accumulate=dy1)       # + the residual branch
         _acc_grad(st[0].fn[0].weight, gw.view(3, 3, c).permute(2, 0, 1).unsqueeze(1))
         _acc_grad(st[0].fn[0].bias, gb)
-        du0 = self._bn_backward(dy0, u0, s0, d[2])
+        du0 = _bn_backward(d[2], dy0, 0, u0, s0, 'gelu', torch.empty_like(u0), c, order=1)
         gw0, gb0 = torch.zeros_like(pk['dw0']), torch.zeros(c, device=dev)
         dx = ops.dwconv3x3_backward(du0, x.t, pk['dw0'], gw0, gb0, dx_accumulate=dx)
         _acc_grad(d[0].weight, gw0.view(3, 3, c).permute(2, 0, 1).unsqueeze(1))
         _acc_grad(d[0].bias, gb0)
-        return Act(dx, 0, c)
+        return Act(dx, 0, c) if need_dx else None
 
     def forward(self, x):
         if x.coff != 0 or x.t.shape[3] != x.c or x.c % 4:
@@ -1158,10 +1203,7 @@ class Decouple(nn.Module):
         self._c3.invalidate()
 
     def forward(self, x):
-        if self.training:
-            self._b3.train(), self._c3.train()
-        else:
-            self._b3.eval(), self._c3.eval()
+        self._b3.train(self.training), self._c3.train(self.training)
         x = self.a(x)
         b = self._b3(self.b2(self.b1(x)))
         c = self._c3(self.c2(self.c1(x)))
@@ -1176,6 +1218,7 @@ class Decouple(nn.Module):
 class DecoupledDetect(nn.Module):
     """models/yolo.py:925-980.  forward returns (z, [raw_i]) in eval like the reference; raw_i is (B,na,ny,nx,no)."""
     stride = None
+    accumulates, folds_pooled, reduction = False, False, 1       # the head: backward(draws) returns the list of its inputs' gradients
 
     def __init__(self, nc=10, anchors=(), ch=(), inplace=False):
         super().__init__()
@@ -1232,6 +1275,8 @@ class Bottleneck(nn.Module):
         self.cv2 = Conv(c_, c2, k[1], 1, g=g)
         self.add = shortcut and c1 == c2
 
+    accumulates, folds_pooled, reduction = False, False, 1       # takes dx_out / accumulate, but not yet walked that way: it would reorder a sum
+
     def forward(self, x, out=None):
         return self.cv2(self.cv1(x), out=out, residual=x if self.add else None)
 
@@ -1256,6 +1301,8 @@ class C3(nn.Module):
         self.cv2 = Conv(c1, c_, 1, 1)
         self.cv3 = Conv(2 * c_, c2, 1)
         self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
+
+    accumulates, folds_pooled, reduction = True, False, 1
 
     def forward(self, x):
         c_ = self.cv1.conv.out_channels
@@ -1302,6 +1349,8 @@ class SPP(nn.Module):
         self.cv2 = Conv(c_ * (len(k) + 1), c2, 1, 1)
         self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])    # parameter-free; kept for state_dict / repr parity
 
+    accumulates, folds_pooled, reduction = True, False, 1
+
     def forward(self, x):
         if self.k == (5, 9, 13):
             return SPPF.forward(self, x)
@@ -1317,14 +1366,14 @@ class SPP(nn.Module):
             ops.spp_pool_(cat.t, c_, self.k, 0)
         return self.cv2(cat)
 
-    def backward(self, dout, dx_out=None, accumulate=False):
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         if self.k == (5, 9, 13):
-            return SPPF.backward(self, dout, dx_out=dx_out, accumulate=accumulate)
+            return SPPF.backward(self, dout, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
         codes = self.__dict__.pop('_ctx')
         c_ = self.cv1.conv.out_channels
         dcat = self.cv2.backward(dout)
         ops.spp_pool_backward_(dcat.t, codes, c_, self.k, dcat.coff)
-        return self.cv1.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate)
+        return self.cv1.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
 class MaxPool2d(nn.Module):
@@ -1338,6 +1387,9 @@ class MaxPool2d(nn.Module):
             raise NotImplementedError(f'nn.MaxPool2d({kernel_size}, {stride}, {padding}) is not on the SOMI path (kernel 2, stride 1 or 2, padding 0)')
         self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
         self.pad = (0, 0, 0, 0)
+
+    accumulates, folds_pooled = False, False
+    reduction = property(lambda self: self.stride)                # stride 2 halves the map; yolov3-tiny's padded stride-1 pool keeps it
 
     def extra_repr(self):
         return f'kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, zero_pad={self.pad}'
@@ -1377,6 +1429,8 @@ class ZeroPad2d(nn.Module):
         self.padding = p
         self.folded = False
 
+    accumulates, folds_pooled, reduction = False, False, 1
+
     def extra_repr(self):
         return f'padding={self.padding}'
 
@@ -1397,6 +1451,9 @@ class Repeat(nn.Sequential):
     """n > 1 repeats of a module the yaml does not repeat inside itself (models/yolo.py:1650: an nn.Sequential, so the names stay model.<i>.<j>...):
     forward and backward walk the children."""
 
+    accumulates, folds_pooled = False, False
+    reduction = property(lambda self: math.prod(m.reduction for m in self))
+
     def forward(self, x):
         for m in self:
             x = m(x)
@@ -1404,14 +1461,9 @@ class Repeat(nn.Sequential):
 
     def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         mods = list(self)
-        for j in range(len(mods) - 1, 0, -1):
-            dout = mods[j].backward(dout)
-        kw = {}
-        if dx_out is not None:
-            kw.update(dx_out=dx_out, accumulate=accumulate)
-        if not need_dx:
-            kw['need_dx'] = False
-        return mods[0].backward(dout, **kw)
+        for m in mods[:0:-1]:
+            dout = m.backward(dout)
+        return mods[0].backward(dout, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
 class BottleneckCSP(_Packed):
@@ -1432,18 +1484,10 @@ class BottleneckCSP(_Packed):
         self.act = nn.SiLU()
         self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
 
-    def _packed(self, dev):
-        own = (self.cv2.weight, self.cv3.weight, self.bn.weight, self.bn.bias)      # the children pack themselves
-        key = (dev, self.training, tuple(p._version for p in own))
-        cache = self.__dict__.get('_pk')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                cache = (key, self._pack(dev))
-            self.__dict__['_pk'] = cache
-        return cache[1]
+    accumulates, folds_pooled, reduction = True, False, 1
 
-    def invalidate(self):
-        self.__dict__.pop('_pk', None)
+    def _pack_params(self):
+        return self.cv2.weight, self.cv3.weight, self.bn.weight, self.bn.bias      # the children pack themselves
 
     def _pack(self, dev):
         c_ = self.cv3.out_channels
@@ -1465,7 +1509,8 @@ class BottleneckCSP(_Packed):
         bn = self.bn
         if bn.weight.device != dev:
             raise RuntimeError('BottleneckCSP: move the module to the device before a training forward')
-        pk.update(gamma=bn.weight.detach(), beta=bn.bias.detach(), rm=bn.running_mean, rv=bn.running_var)
+        vec = _bn_vectors(bn, dev, 2 * c_)                       # bn's own tensors, updated in place: cv3's half, then cv2's
+        pk['bn'] = [{k: v if k == 'inplace' else v[o:o + c_] for k, v in vec.items()} for o in (0, c_)]
         return pk
 
     def forward(self, x):
@@ -1483,38 +1528,16 @@ class BottleneckCSP(_Packed):
             return self.cv4(z)
         y = torch.empty(B, H, W, 2 * c_, device=x.t.device, dtype=torch.float32)     # raw cv3 | cv2 outputs: what bn normalises
         stats = []
-        for name, src, o in (('3', t, 0), ('2', x, c_)):
-            st = {'pivot': pk['rm'][o:o + c_]}
+        for name, src, o, vec in (('3', t, 0, pk['bn'][0]), ('2', x, c_, pk['bn'][1])):
+            st = {'pivot': vec['rm']}
             ops.conv2d_nhwc(src.t, pk['w' + name], None, kh=1, kw=1, stride=1, pad=0, act='none', cin=pad4(src.c), x_coff=src.coff, out=y, cout=c_,
                             y_coff=o, alg_cin=src.c, alg_cout=c_, bn_stats=st)
-            s4 = ops.bn_stats_from_partials(st['part'], st['rows'], B * H * W, c_, pk['gamma'][o:o + c_], pk['beta'][o:o + c_], self.bn.eps,
-                                            self.bn.momentum, pk['rm'][o:o + c_], pk['rv'][o:o + c_])
+            s4, commit = _bn_train(self.bn, c_, partials=st, npix=B * H * W, vec=vec)
             ops.chan_affine_act(y, c_, o, s4[2], s4[3], 'silu', 0, z.t, o)
             stats.append(s4)
-        with torch.no_grad():
-            _bump_batches_tracked(self.bn)
+        commit()                                                 # both halves ran in place on bn's own buffers: one step counted
         self.__dict__['_ctx'] = (x, t, y, stats, pk)
         return self.cv4(z)
-
-    def _plain_backward(self, conv, wt, src, dy, o, dx_out, accumulate, need_dx):
-        """Weight gradient of the plain 1x1 `conv` (input src, output gradient dy's slice at o) into .grad; -> its data gradient."""
-        c1, c_ = conv.in_channels, conv.out_channels
-        c1p = pad4(c1)
-        g = conv.weight.grad
-        if c1p == c1 and g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == dy.device:
-            gv = g.view(c_, c1)                                   # the kernel accumulates straight into the gradient (the optimizer's flat view)
-            ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=c_, dy_coff=o, out=gv, accumulate=gv)
-        else:
-            dw = ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=c_, dy_coff=o)
-            _acc_grad(conv.weight, dw.view(c_, 1, 1, c1p)[:, :, :, :c1].permute(0, 3, 1, 2))
-        if not need_dx:
-            return None
-        B, H, W, _ = src.shape
-        if dx_out is None:
-            dx_out = Act(torch.empty(B, H, W, c1p, device=dy.device, dtype=torch.float32), 0, c1)
-        ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1p, kh=1, kw=1, cout=c_, dy_coff=o, out=dx_out.t, dx_coff=dx_out.coff,
-                              accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff)
-        return dx_out
 
     def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         x, t, y, stats, pk = self.__dict__.pop('_ctx')
@@ -1522,11 +1545,11 @@ class BottleneckCSP(_Packed):
         dz = self.cv4.backward(dout)
         dy = torch.empty_like(y)
         (gw, gb), fin = _grad_targets(self.bn.weight, self.bn.bias)
-        for (mean, rstd, scale, shift), o in zip(stats, (0, c_)):
-            ops.bn_act_backward(dz.t, dz.coff + o, y, o, c_, mean, rstd, scale, shift, 'silu', 0, True, dy, o, gw[o:o + c_], gb[o:o + c_])
+        for st, o in zip(stats, (0, c_)):
+            _bn_backward(self.bn, dz.t, dz.coff + o, y, st, 'silu', dy, c_, coff=o, targets=(gw[o:o + c_], gb[o:o + c_]))
         fin()
-        dx = self._plain_backward(self.cv2, pk['t2'], x, dy, c_, dx_out, accumulate, need_dx)
-        d = self._plain_backward(self.cv3, pk['t3'], t, dy, 0, None, False, True)
+        dx = _plain_conv_backward(self.cv2, x, dy, pk['t2'], dy_coff=c_, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, direct=('weight',))
+        d = _plain_conv_backward(self.cv3, t, dy, pk['t3'], direct=('weight',))
         for blk in reversed(self.m):
             d = blk.backward(d)
         self.cv1.backward(d, dx_out=dx, accumulate=True, need_dx=need_dx)
@@ -1541,6 +1564,9 @@ class Focus(nn.Module):
         if act is not True:
             raise NotImplementedError("the reference passes `act` into Conv's dilation slot (models/common.py:1993); only act=True runs there")
         self.conv = Conv(c1 * 4, c2, k, s, p, g)
+
+    accumulates, folds_pooled = False, False
+    reduction = property(lambda self: 2 * self.conv.reduction)
 
     def forward(self, x):
         if x.shape[1] % 2 or x.shape[2] % 2:
@@ -1564,6 +1590,8 @@ class DWConv(Conv):
     def __init__(self, c1, c2, k=1, s=1, act=True):
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), act=act)
 
+    folds_pooled = False      # the pools ride the dense Conv's passes only
+
 
 class GhostConv(nn.Module):
     """cat(cv1(x), cv2(cv1(x))) with cv2 a 5x5 depthwise Conv (models/common.py:2001-2011).  cv1 writes channels [0, c_) of the output,
@@ -1575,6 +1603,9 @@ class GhostConv(nn.Module):
         c_ = c2 // 2
         self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
         self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
+
+    accumulates, folds_pooled = True, False
+    reduction = property(lambda self: self.cv1.reduction)
 
     def forward(self, x, out=None, residual=None):
         """residual: an Act of 2c_ channels added to the output (GhostBottleneck's shortcut): its halves ride the two convs' output passes -
@@ -1615,6 +1646,8 @@ class GhostBottleneck(nn.Module):
     @property
     def stride(self):
         return 2 if isinstance(self.conv[1], Conv) else 1
+
+    accumulates, folds_pooled, reduction = True, False, stride
 
     def forward(self, x, out=None):
         g1, dw, g2 = self.conv
@@ -1662,6 +1695,8 @@ class C2f(nn.Module):
         self.cv2 = Conv((2 + n) * self.c, c2, 1)
         self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
 
+    accumulates, folds_pooled, reduction = True, False, 1
+
     def forward(self, x):
         c, n = self.c, len(self.m)
         if c % 4:
@@ -1689,6 +1724,9 @@ class SCDown(nn.Module):
         self.cv1 = Conv(c1, c2, 1, 1)
         self.cv2 = Conv(c2, c2, k=k, s=s, g=c2, act=False)
 
+    accumulates, folds_pooled = True, False
+    reduction = property(lambda self: self.cv2.reduction)
+
     def forward(self, x, out=None):
         return self.cv2(self.cv1(x), out=out)
 
@@ -1708,6 +1746,8 @@ class CIB(nn.Module):
         self.cv1 = nn.Sequential(Conv(c1, c1, 3, g=c1), Conv(c1, 2 * c_, 1), Conv(2 * c_, 2 * c_, 3, g=2 * c_), Conv(2 * c_, c2, 1),
                                  Conv(c2, c2, 3, g=c2))
         self.add = shortcut and c1 == c2
+
+    accumulates, folds_pooled, reduction = False, False, 1
 
     def forward(self, x, out=None):
         t = x
@@ -1788,6 +1828,8 @@ class PSA(nn.Module):
         self.attn = AttentionPSA(self.c, attn_ratio=0.5, num_heads=self.c // 64)
         self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
 
+    accumulates, folds_pooled, reduction = True, False, 1
+
     def forward(self, x):
         c = self.c
         B, H, W, _ = x.shape
@@ -1818,6 +1860,8 @@ class Concat(nn.Module):
         if dimension != 1:
             raise NotImplementedError('channel concatenation only')
         self.d = dimension
+
+    accumulates, folds_pooled, reduction = False, False, 1       # several inputs: backward(dout) returns the list of their gradients
 
     def forward(self, xs):
         B, H, W = xs[0].shape[0], xs[0].shape[1] << xs[0].up, xs[0].shape[2] << xs[0].up
@@ -1853,6 +1897,7 @@ class Detect(nn.Module):
     """The stock anchor head (models/yolo.py:46-109): one 1x1 conv (+bias) per level, the view/permute and the eval decode in one
     kernel.  forward returns (z, [raw_i]) in eval and [raw_i] in training like the reference; raw_i is (B,na,ny,nx,no)."""
     stride = None
+    accumulates, folds_pooled, reduction = False, False, 1       # the head: backward(draws) returns the list of its inputs' gradients
 
     def __init__(self, nc=80, anchors=(), ch=(), inplace=True):
         super().__init__()
@@ -1916,6 +1961,8 @@ class DCNv3_YOLO(_Packed):
         self.bn = nn.BatchNorm2d(c)
         self.act = nn.SiLU()
 
+    accumulates, folds_pooled, reduction = False, False, 1
+
     def _pack(self, dev):
         """eval: output projection with the BatchNorm folded in (W' = diag(s) W, b' = s b + t)."""
         s_, t_ = bn_fold(self.bn)
@@ -1931,29 +1978,22 @@ class DCNv3_YOLO(_Packed):
             w, b = self._packed(x.t.device)
             return Act(self.dcnv3._forward_impl(x.t, out_proj=(w, b, _act_name(self.act))), 0, c)
         self.invalidate()
-        bn, dev = self.bn, x.t.device
-        rm, rv = bn.running_mean.detach().clone(), bn.running_var.detach().clone()
-        sd = {'pivot': rm} if x.t.numel() * 4 <= 0xE0000000 else None
+        vec = _bn_clones(self.bn)
+        sd = {'pivot': vec['rm']} if x.t.numel() * 4 <= 0xE0000000 else None
         u, saved = self.dcnv3._forward_impl(x.t, keep=True, bn_stats=sd)
-        if sd is not None and 'part' in sd:                       # the output projection's epilogue left the partial sums: no extra read of u
-            st = ops.bn_stats_from_partials(sd['part'], sd['rows'], u.numel() // c, c, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum,
-                                            rm, rv)
-        else:
-            st = ops.bn_stats(u, c, 0, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, rm, rv)
-        with torch.no_grad():
-            bn.running_mean.copy_(rm)
-            bn.running_var.copy_(rv)
-            _bump_batches_tracked(bn)
+        # when the output projection's epilogue left the partial sums: no extra read of u
+        st, commit = _bn_train(self.bn, c, u, partials=sd if sd is not None and 'part' in sd else None, npix=u.numel() // c, vec=vec)
+        commit()
         out = ops.chan_affine_act(u, c, 0, st[2], st[3], _act_name(self.act), 0, torch.empty_like(u))
         self.__dict__['_ctx'] = (u, st, saved)
         return Act(out, 0, c)
 
-    def backward(self, dz, need_dx=True):
+    def backward(self, dz, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('DCNv3_YOLO writes its own input gradient')
         u, st, saved = self.__dict__.pop('_ctx')
-        c, dev = self.bn.num_features, u.device
-        (dg, db), fin = _grad_targets(self.bn.weight, self.bn.bias)
-        du = ops.bn_act_backward(dz.t, dz.coff, u, 0, c, *st, _act_name(self.act), 0, True, torch.empty_like(u), 0, dg, db)
-        fin()
+        c = self.bn.num_features
+        du = _bn_backward(self.bn, dz.t, dz.coff, u, st, _act_name(self.act), torch.empty_like(u), c)
         dinput, grads = self.dcnv3._backward_impl(saved, du)
         for p_, g_ in zip(self.dcnv3._params(), grads):
             _acc_grad(p_, g_.view_as(p_) if g_.numel() == p_.numel() else g_[:p_.shape[0]])

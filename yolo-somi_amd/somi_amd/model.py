@@ -158,32 +158,9 @@ class Model(nn.Module):
         for m in self.model:
             src = m.f if isinstance(m.f, int) else m.f[0]
             r = 1.0 if m.i == 0 else (red[m.i - 1] if src == -1 else red[src])
-            r *= self._reduction(m)
+            r *= m.reduction                                      # the factor by which the layer shrinks its input map (1 / 2 for an upsampler)
             red.append(r)
         return [float(red[j]) for j in self.model[-1].f]
-
-    @staticmethod
-    def _reduction(m):
-        """Factor by which a layer shrinks its input map (1 / 2 for the upsample)."""
-        if isinstance(m, B.Conv):                                 # DWConv too
-            return m.conv.stride[0]
-        if isinstance(m, B.GhostConv):
-            return m.cv1.conv.stride[0]
-        if isinstance(m, B.GhostBottleneck):
-            return m.stride
-        if isinstance(m, B.SCDown):
-            return m.cv2.conv.stride[0]
-        if isinstance(m, B.Focus):
-            return 2 * m.conv.conv.stride[0]
-        if isinstance(m, B.ODConv_3rd):
-            return m.conv.stride
-        if isinstance(m, (B.Upsample, B.CARAFE, B.DySample)):
-            return 0.5
-        if isinstance(m, B.MaxPool2d):                            # stride 2 halves the map; yolov3-tiny's padded stride-1 pool keeps it
-            return m.stride
-        if isinstance(m, B.Repeat):
-            return math.prod(Model._reduction(sub) for sub in m)
-        return 1
 
     @staticmethod
     def _check_anchor_order(m):
@@ -293,35 +270,29 @@ class Model(nn.Module):
             if g is None:
                 raise RuntimeError(f'layer {m.i} ({m.type}) received no gradient')
             srcs = self._sources(m)
-            pend = None
+            kw = {}
             if g.pooled is not None:                              # a part constant over each image's pixels, not added yet (ODConv's squeeze gradient)
-                if type(m) in (B.Conv, B.C2fCBAM):
-                    pend, g.pooled = g.pooled, None               # this layer's (closing conv's) BatchNorm backward folds it in
+                if m.folds_pooled:
+                    kw['pooled'], g.pooled = g.pooled, None       # this layer's (closing conv's) BatchNorm backward folds it in
                 else:
                     B.settle_pooled(g)
-            if isinstance(m, (B.BiFPN, B.Concat)):
+            if not isinstance(m.f, int):                          # several inputs: a list of gradients
                 for src, d in zip(srcs, m.backward(g)):
                     give(src, d)
             elif srcs[0] < 0:
-                m.backward(g, need_dx=False, **({'pooled': pend} if pend is not None else {}))
-            elif isinstance(m, B.DCNv3_YOLO):
-                give(srcs[0], m.backward(g))
+                m.backward(g, need_dx=False, **kw)
             else:
                 have = grads.get(srcs[0])
-                kw = {'pooled': pend} if pend is not None else {}
-                if (have is not None and isinstance(m, (B.Conv, B.C2fCBAM, B.C3, B.SPPF, B.SPP, B.ODConv_3rd, B.GhostConv, B.GhostBottleneck,
-                                                                B.C2f, B.SCDown, B.PSA, B.BottleneckCSP)) and
-                        have.coff == 0 and
-                        have.t.shape[3] == B.pad4(have.c) and have.t.is_contiguous() and have.pooled is None and
-                        (not isinstance(m, B.ODConv_3rd) or have.t.shape[3] == have.c)):
-                    # the input already holds another consumer's gradient: the data-gradient epilogue adds to it in place
-                    if isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.SYNC_BN is None:
-                        have.pooled = m.backward(g, dx_out=have, accumulate=True, defer_pool=True).pooled    # the last consumer to arrive: see below
-                    else:
-                        m.backward(g, dx_out=have, accumulate=True, **kw)
-                elif have is None and isinstance(m, B.ODConv_3rd) and type(self.model[srcs[0]]) in (B.Conv, B.C2fCBAM) and ops.SYNC_BN is None:
-                    # the only consumer of a plain Conv's output (later layers have all been walked): its squeeze gradient rides that Conv's BatchNorm backward
-                    give(srcs[0], m.backward(g, defer_pool=True))
+                squeeze = getattr(m, 'squeezes_input', False)     # ODConv
+                # the input already holds another consumer's gradient: the data-gradient epilogue adds to it in place
+                acc = (have is not None and m.accumulates and have.coff == 0 and have.t.shape[3] == B.pad4(have.c) and have.t.is_contiguous() and
+                       have.pooled is None and (not squeeze or have.t.shape[3] == have.c))
+                if squeeze and (acc or have is None) and self.model[srcs[0]].folds_pooled and ops.SYNC_BN is None:
+                    # the last consumer of its producer's output to arrive (later layers have all been walked): its squeeze gradient rides that
+                    # layer's BatchNorm backward
+                    kw['defer_pool'] = True
+                if acc:
+                    have.pooled = m.backward(g, dx_out=have, accumulate=True, **kw).pooled      # a deferred squeeze gradient, else None as before
                 else:
                     give(srcs[0], m.backward(g, **kw))
             if hook:
@@ -342,7 +313,7 @@ class Model(nn.Module):
                 if m.f != -1:
                     a = y[m.f] if isinstance(m.f, int) else [a if j == -1 else y[j] for j in m.f]
                 nxt = self.model[m.i + 1] if m.i + 1 < len(self.model) else None
-                if self.training and type(m) in (B.Conv, B.C2fCBAM) and isinstance(nxt, B.ODConv_3rd) and nxt.f == -1:
+                if self.training and m.folds_pooled and getattr(nxt, 'squeezes_input', False) and nxt.f == -1:
                     pool = {}                                     # the next layer squeezes this output: its last BatchNorm + SiLU pass takes the average
                     a = m(a, pool=pool)
                     if 'avg' in pool:

@@ -14,6 +14,30 @@ from ._lib import ConvDesc, check
 DCN_DIRECT = os.environ.get('SOMI_DCN_DIRECT', '0') == '1'          # 1: DCNv3 backward scatters with fp32 atomics (the reference's form)
 PROFILE = None   # bench.py sets this to a list: every conv launch appends (kernel name, algorithmic FLOPs, ev0, ev1)
 
+
+
+class _timed:
+    """`with _timed(info):` around a launch: while bench.py profiles (PROFILE is a list) an event pair brackets the body on torch's current
+    stream - the stream the kernel runs on - and info() -> (kernel name, algorithmic work, shape key) completes the entry
+    (name, work, ev0, ev1, key).  Otherwise nothing happens: no events, info is never called."""
+    __slots__ = ('info', 'ev')
+
+    def __init__(self, info):
+        self.info, self.ev = info, None
+
+    def __enter__(self):
+        if PROFILE is not None:
+            self.ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.ev[0].record()
+
+    def __exit__(self, etype, *exc):
+        if self.ev is not None and etype is None:
+            self.ev[1].record()
+            name, work, key = self.info()
+            PROFILE.append((name, work, *self.ev, key))
+        return False
+
+
 ACT = {'none': 0, None: 0, 'silu': 1, 'gelu': 2, 'relu': 3, 'sigmoid': 4, 'softmax': 5}
 
 
@@ -84,16 +108,9 @@ def conv2d_nhwc(x, w, bias=None, *, kh, kw, stride=1, pad=0, dil=1, act='none', 
         part = torch.empty(2, rows, cout, device=x.device, dtype=torch.float32)
         d.stat_sum, d.stat_sumsq, d.stat_pivot = part[0].data_ptr(), part[1].data_ptr(), _ptr(bn_stats.get('pivot'))
         bn_stats['part'], bn_stats['rows'] = part, rows
-    if PROFILE is None:
+    with _timed(lambda: (_lib.lib().somi_conv2d_kernel_name(C.byref(d)).decode(), 2.0 * B * Ho * Wo * (alg_cout or cout) * (alg_cin or cin) * kh * kw,
+                         (B, H, W, cin, cout, kh, stride, int(per_sample_w)))):
         check(_lib.lib().somi_conv2d_nhwc_f32(C.byref(d), _stream()), 'conv2d_nhwc')
-        return out
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()                                               # torch's current stream == the stream the kernel runs on
-    check(_lib.lib().somi_conv2d_nhwc_f32(C.byref(d), _stream()), 'conv2d_nhwc')
-    e1.record()
-    name = _lib.lib().somi_conv2d_kernel_name(C.byref(d)).decode()
-    flops = 2.0 * B * Ho * Wo * (alg_cout or cout) * (alg_cin or cin) * kh * kw
-    PROFILE.append((name, flops, e0, e1, (B, H, W, cin, cout, kh, stride, int(per_sample_w))))
     return out
 
 
@@ -111,17 +128,11 @@ def dcnv3_forward_raw(input, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, group
                  float(offset_scale), int(im2col_step), _stream()), 'dcnv3_forward')
         return out
     out = torch.empty(N, Ho, Wo, group * group_channels, device=input.device, dtype=torch.float32)
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_lib.lib().somi_dcnv3_forward_f32(_ptr(input), _ptr(offset), _ptr(mask), _ptr(out), N, H, W, group,
-                                            group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale),
-                                            int(im2col_step), _stream()), 'dcnv3_forward')
-    if prof:                                                      # algorithmic bytes: 4 (2C + 3GK) per output pixel
-        e1.record()
-        C_ = group * group_channels
-        PROFILE.append(('dcnv3_fwd_kernel', 4.0 * N * Ho * Wo * (2 * C_ + 3 * group * kh * kw), e0, e1, (N, H, W, C_, group, kh, sh, 10)))
+    C_, GK = group * group_channels, group * kh * kw             # algorithmic bytes: 4 (2C + 3GK) per output pixel
+    with _timed(lambda: ('dcnv3_fwd_kernel', 4.0 * N * Ho * Wo * (2 * C_ + 3 * GK), (N, H, W, C_, group, kh, sh, 10))):
+        check(_lib.lib().somi_dcnv3_forward_f32(_ptr(input), _ptr(offset), _ptr(mask), _ptr(out), N, H, W, group,
+                                                group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale),
+                                                int(im2col_step), _stream()), 'dcnv3_forward')
     return out
 
 
@@ -187,23 +198,16 @@ def dcnv3_backward_raw(input, offset, mask, grad_output, kh, kw, sh, sw, ph, pw,
     gi = torch.zeros_like(input)
     go = torch.empty_like(offset)
     gm = torch.empty_like(mask)
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L = _lib.lib()
-    nbytes = 0 if DCN_DIRECT else L.somi_dcnv3_backward_workspace_bytes(N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale))
-    ws = _dcn_workspace(nbytes, input.device) if nbytes else None   # staging slab + near masks + overflow word of the windowed form
+    C_, GK, (Ho, Wo) = group * group_channels, group * kh * kw, grad_output.shape[1:3]          # 4 (4C + 6GK) bytes per output pixel
     global DCN_LAST_WORKSPACE
-    DCN_LAST_WORKSPACE = ws                                      # tests read the overflow-tap counter at its end (dcn_overflow_taps)
-    check(L.somi_dcnv3_backward_f32(_ptr(input), _ptr(offset), _ptr(mask), _ptr(grad_output), _ptr(gi), _ptr(go),
-                                    _ptr(gm), N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw,
-                                    float(offset_scale), int(im2col_step), _ptr(ws), nbytes, _stream()), 'dcnv3_backward')
-    if prof:                                                      # 4 (4C + 6GK) per output pixel
-        e1.record()
-        C_ = group * group_channels
-        Ho, Wo = grad_output.shape[1], grad_output.shape[2]
-        PROFILE.append(('dcnv3_bwd_kernel', 4.0 * N * Ho * Wo * (4 * C_ + 6 * group * kh * kw), e0, e1, (N, H, W, C_, group, kh, sh, 11)))
+    with _timed(lambda: ('dcnv3_bwd_kernel', 4.0 * N * Ho * Wo * (4 * C_ + 6 * GK), (N, H, W, C_, group, kh, sh, 11))):
+        L = _lib.lib()
+        nbytes = 0 if DCN_DIRECT else L.somi_dcnv3_backward_workspace_bytes(N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale))
+        ws = _dcn_workspace(nbytes, input.device) if nbytes else None   # staging slab + near masks + overflow word of the windowed form
+        DCN_LAST_WORKSPACE = ws                                  # tests read the overflow-tap counter at its end (dcn_overflow_taps)
+        check(L.somi_dcnv3_backward_f32(_ptr(input), _ptr(offset), _ptr(mask), _ptr(grad_output), _ptr(gi), _ptr(go),
+                                        _ptr(gm), N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw,
+                                        float(offset_scale), int(im2col_step), _ptr(ws), nbytes, _stream()), 'dcnv3_backward')
     if ws is not None:
         _dcn_count_far(ws)
     return gi, go, gm
@@ -218,17 +222,11 @@ def dcnv3_forward_merged(input, om, kh, kw, sh, sw, ph, pw, dh, dw, group, group
     if om.shape[:3] != (N, Ho, Wo) or R < 3 * GK or not om.is_contiguous() or om.dtype != torch.float32:
         raise RuntimeError(f'dcnv3 (merged offset/mask): om must be contiguous float32 ({N},{Ho},{Wo},>={3 * GK}), got {tuple(om.shape)}')
     out = torch.empty(N, Ho, Wo, group * group_channels, device=input.device, dtype=torch.float32)
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_lib.lib().somi_dcnv3_forward_strided_f32(_ptr(input), om.data_ptr(), om.data_ptr() + 8 * GK, R, R, _ptr(out), N, H, W, group,
-                                                    group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale), int(im2col_step),
-                                                    _stream()), 'dcnv3_forward')
-    if prof:
-        e1.record()
-        C_ = group * group_channels
-        PROFILE.append(('dcnv3_fwd_kernel', 4.0 * N * Ho * Wo * (2 * C_ + 3 * GK), e0, e1, (N, H, W, C_, group, kh, sh, 10)))
+    C_ = group * group_channels
+    with _timed(lambda: ('dcnv3_fwd_kernel', 4.0 * N * Ho * Wo * (2 * C_ + 3 * GK), (N, H, W, C_, group, kh, sh, 10))):
+        check(_lib.lib().somi_dcnv3_forward_strided_f32(_ptr(input), om.data_ptr(), om.data_ptr() + 8 * GK, R, R, _ptr(out), N, H, W, group,
+                                                        group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale), int(im2col_step),
+                                                        _stream()), 'dcnv3_forward')
     return out
 
 
@@ -241,23 +239,16 @@ def dcnv3_backward_merged(input, om, grad_output, kh, kw, sh, sw, ph, pw, dh, dw
     d_om = torch.empty_like(om)
     if R != 3 * GK:
         d_om[..., 3 * GK:].zero_()                                # the operator writes the first 3GK columns of every row; the pad stays zero
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    L = _lib.lib()
-    nbytes = 0 if DCN_DIRECT else L.somi_dcnv3_backward_workspace_bytes(N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale))
-    ws = _dcn_workspace(nbytes, input.device) if nbytes else None
+    C_, (Ho, Wo) = group * group_channels, grad_output.shape[1:3]
     global DCN_LAST_WORKSPACE
-    DCN_LAST_WORKSPACE = ws
-    check(L.somi_dcnv3_backward_strided_f32(_ptr(input), om.data_ptr(), om.data_ptr() + 8 * GK, R, R, _ptr(grad_output), _ptr(gi),
-                                            d_om.data_ptr(), d_om.data_ptr() + 8 * GK, N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw,
-                                            dh, dw, float(offset_scale), int(im2col_step), _ptr(ws), nbytes, _stream()), 'dcnv3_backward')
-    if prof:
-        e1.record()
-        C_ = group * group_channels
-        Ho, Wo = grad_output.shape[1], grad_output.shape[2]
-        PROFILE.append(('dcnv3_bwd_kernel', 4.0 * N * Ho * Wo * (4 * C_ + 6 * GK), e0, e1, (N, H, W, C_, group, kh, sh, 11)))
+    with _timed(lambda: ('dcnv3_bwd_kernel', 4.0 * N * Ho * Wo * (4 * C_ + 6 * GK), (N, H, W, C_, group, kh, sh, 11))):
+        L = _lib.lib()
+        nbytes = 0 if DCN_DIRECT else L.somi_dcnv3_backward_workspace_bytes(N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw, dh, dw, float(offset_scale))
+        ws = _dcn_workspace(nbytes, input.device) if nbytes else None
+        DCN_LAST_WORKSPACE = ws
+        check(L.somi_dcnv3_backward_strided_f32(_ptr(input), om.data_ptr(), om.data_ptr() + 8 * GK, R, R, _ptr(grad_output), _ptr(gi),
+                                                d_om.data_ptr(), d_om.data_ptr() + 8 * GK, N, H, W, group, group_channels, kh, kw, sh, sw, ph, pw,
+                                                dh, dw, float(offset_scale), int(im2col_step), _ptr(ws), nbytes, _stream()), 'dcnv3_backward')
     if ws is not None:
         _dcn_count_far(ws)
     return gi, d_om
@@ -747,23 +738,18 @@ def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, cou
         d.residual2, d.res2_cs, d.res2_coff = _ptr(_f32c(accumulate2)), accumulate2.shape[3], acc2_coff
     if w_dgrad.numel() != (B if per_sample_w else 1) * cin * kh * kw * cout:
         raise RuntimeError('dgrad weight has the wrong number of elements')
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_lib.lib().somi_conv2d_dgrad_nhwc_f32(C.byref(d), _ptr(_f32c(dy)), dy_cs, dy_coff, _ptr(_f32c(w_dgrad)), _ptr(_f32c(out)),
-                                                out.shape[3], dx_coff, _ptr(accumulate),
-                                                accumulate.shape[3] if accumulate is not None else 0, acc_coff, _stream()),
-          'conv2d_dgrad_nhwc')
-    if prof:
-        e1.record()
+    def info():
         g = ConvDesc()                                           # the geometry the kernel runs in: rows = forward-input pixels
         g.B, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout = B, Ho, Wo, cout, H, W, cin
         g.kh, g.kw, g.stride, g.per_sample_w = kh, kw, stride, int(per_sample_w)
         if stride == 1:
             g.workspace, g.workspace_bytes = d.workspace, d.workspace_bytes
-        name = _lib.lib().somi_conv2d_kernel_name(C.byref(g)).decode()
-        PROFILE.append((name, 2.0 * B * Ho * Wo * cout * cin * kh * kw, e0, e1, (B, H, W, cin, cout, kh, stride, 2)))
+        return _lib.lib().somi_conv2d_kernel_name(C.byref(g)).decode(), 2.0 * B * Ho * Wo * cout * cin * kh * kw, (B, H, W, cin, cout, kh, stride, 2)
+    with _timed(info):
+        check(_lib.lib().somi_conv2d_dgrad_nhwc_f32(C.byref(d), _ptr(_f32c(dy)), dy_cs, dy_coff, _ptr(_f32c(w_dgrad)), _ptr(_f32c(out)),
+                                                    out.shape[3], dx_coff, _ptr(accumulate),
+                                                    accumulate.shape[3] if accumulate is not None else 0, acc_coff, _stream()),
+              'conv2d_dgrad_nhwc')
     return out
 
 
@@ -784,16 +770,10 @@ def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, cin=None, x_coff=0, cou
     L = _lib.lib()
     nbytes = L.somi_conv2d_wgrad_workspace_bytes(C.byref(d))
     ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
-    prof = PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(L.somi_conv2d_wgrad_nhwc_f32(C.byref(d), _ptr(_f32c(x)), x_cs, x_coff, _ptr(_f32c(dy)), dy_cs, dy_coff, _ptr(_f32c(out)),
-                                       _ptr(accumulate), _ptr(ws), nbytes, _stream()), 'conv2d_wgrad_nhwc')
-    if prof:
-        e1.record()
-        PROFILE.append((L.somi_conv2d_wgrad_kernel_name(C.byref(d)).decode(), 2.0 * B * Ho * Wo * cout * cin * kh * kw, e0, e1,
-                        (B, H, W, cin, cout, kh, stride, 3)))
+    with _timed(lambda: (L.somi_conv2d_wgrad_kernel_name(C.byref(d)).decode(), 2.0 * B * Ho * Wo * cout * cin * kh * kw,
+                         (B, H, W, cin, cout, kh, stride, 3))):
+        check(L.somi_conv2d_wgrad_nhwc_f32(C.byref(d), _ptr(_f32c(x)), x_cs, x_coff, _ptr(_f32c(dy)), dy_cs, dy_coff, _ptr(_f32c(out)),
+                                           _ptr(accumulate), _ptr(ws), nbytes, _stream()), 'conv2d_wgrad_nhwc')
     return out
 
 
