@@ -38,7 +38,7 @@ typedef void *somi_stream_t;
 
 int somi_abi_version(void);
 const char *somi_last_error(void);
-/* sizeof of a descriptor struct as the library was compiled (0: somi_conv_desc, 1: somi_loss_desc): lets a binding check its mirror */
+/* sizeof of a descriptor struct as the library was compiled (0: somi_conv_desc, 1: somi_loss_desc, 2: somi_loss_box_rule): lets a binding check its mirror */
 size_t somi_sizeof_desc(int which);
 
 /* ------------------------------------------------------------------------------------------
@@ -711,6 +711,33 @@ typedef struct somi_loss_level {
 size_t somi_loss5_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5);
 int somi_yolo_loss5_f32(const somi_loss_desc *d, const somi_loss_level *l5, float *out9, void *workspace, size_t workspace_bytes,
                         somi_stream_t stream);
+
+/* The box-regression rule of the loss: which reference call stands where utils/loss.py:161 hard-codes bbox_iou(..., CIoU=True).
+ * kind IOU..WIOU: bbox_iou(pbox.T, tbox, x1y1x2y2=False, <flag>, Focal, alpha, gamma, scale) (utils/metrics.py:476-583); SHAPE: shape_iou
+ * (:397-439); inner != 0: bbox_inner_iou(pbox, tbox, xywh=True, <flag>, ratio) (:604-702, its xywh branch as written).  A tensor result r
+ * enters the loss as mean(1 - r) with similarity s = r; a pair (r0, r1) as mean(r1.detach() * (1 - r0)), s = r0 (Focal, unscaled WIoU); the
+ * triple of scaled WIoU as mean(r0 * r1), s = r2.  s takes the place of the CIoU in the NWD blend, the objectness target and the SlideLoss mean.
+ * Which combinations mean something is the caller's business (somi_amd.loss.ComputeLoss refuses the rest); the library checks ranges only. */
+enum somi_loss_iou_kind { SOMI_LOSS_IOU = 0, SOMI_LOSS_GIOU = 1, SOMI_LOSS_DIOU = 2, SOMI_LOSS_CIOU = 3, SOMI_LOSS_EIOU = 4, SOMI_LOSS_SIOU = 5,
+                          SOMI_LOSS_EFFICICIOU = 6, SOMI_LOSS_WIOU = 7, SOMI_LOSS_SHAPE = 8 };
+typedef struct somi_loss_box_rule {
+    int32_t kind;        /* enum somi_loss_iou_kind */
+    int32_t focal;       /* Focal=True: the pair form, weight (inter / (union + eps)) ** gamma */
+    int32_t inner;       /* bbox_inner_iou with `inner_ratio` instead of bbox_iou */
+    int32_t wiou_scaled; /* WIoU with scale=True: the non-monotonic focusing factor of WIoU_Scale (v3) */
+    float alpha;         /* >= 1; 1 leaves every pow out */
+    float gamma;         /* Focal exponent */
+    float inner_ratio;
+    float shape_scale;   /* shape_iou's scale1 */
+    double *wiou_mean;   /* device, one element: WIoU_Scale.iou_mean.  Read and (with wiou_train) updated by every call with wiou_scaled, level by
+                          * level in level order before that level's factor is formed, with momentum 1 - 0.5 ** (1 / 7000); no host round trip */
+    int32_t wiou_train;  /* WIoU_Scale._is_train */
+} somi_loss_box_rule;
+/* `l5` NULL: up to four levels; else d->nl = 5.  CIoU without focal / inner and alpha = 1 - the default rule - runs the very kernels of
+ * somi_yolo_loss_f32 / somi_yolo_loss5_f32 and gives their bits.  out9: as there (eight floats are written for up to four levels). */
+size_t somi_loss_rule_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5, const somi_loss_box_rule *rule);
+int somi_yolo_loss_rule_f32(const somi_loss_desc *d, const somi_loss_level *l5, const somi_loss_box_rule *rule, float *out9, void *workspace,
+                            size_t workspace_bytes, somi_stream_t stream);
 
 /* Repulsion loss, RepGT + RepBox (utils/RepulsionLoss.py:47-95; imported by utils/loss.py:8 but never called by ComputeLoss,
  * so it is an optional term and off by default).  pbox, gtbox: (B,A,4) xyxy; fg_mask: (B,A) bytes (non-zero = foreground).

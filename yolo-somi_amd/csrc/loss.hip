@@ -22,6 +22,11 @@
 // weights of both BCE terms (stacked like :125-131), the NWD box term (:162-169, utils/metrics.py:341-354) blended into the box loss,
 // its gradient and the objectness target.  SlideLoss needs the level's mean IoU before any BCE can be weighted, so the class BCE of
 // the matched entries is evaluated in pass 1b (after a one-workgroup-per-level mean, 1a).  autobalance is host state: the per-level objectness means it feeds on leave in out[4..7].
+// The box rule (somi_loss_box_rule): every kernel that sees entries is a template over GEN.  GEN = false is the CIoU path above, line for line what
+// it was; GEN = true evaluates the selected rule of utils/metrics.py (bbox_iou's switches, shape_iou, bbox_inner_iou) as a Dual function and keeps
+// the entry's box term apart from its similarity.  Scaled WIoU needs the level's mean of 1 - inter/union before its factor exists: the match pass
+// leaves that value in the slot, 1a reduces it in the SlideLoss mean's fixed order, one lane folds the levels into the running mean (device state)
+// and pass 1b writes the box term.
 #include "common.h"
 
 namespace somi {
@@ -47,15 +52,24 @@ struct LossDescN {
     int32_t slide;
     float nwd_ratio, nwd_constant;
 };
+// somi_loss_box_rule as the kernels read it
+struct BoxRule {
+    int kind, focal, inner, scaled, train;
+    float alpha, gamma, ratio, shape_scale;
+    double momentum;        // 1 - 0.5 ** (1 / 7000) (WIoU_Scale._momentum)
+    double *wiou_mean;
+};
 struct LossArgs {
     LossDescN d;
+    BoxRule r;
+    double *wiou_lvl;       // [MAXL] scaled WIoU: the level's mean of 1 - inter/union, then (after the state step) the running mean that level divides by
     int no;
     long cells[MAXL];       // B*na*ny*nx per level
     long cell_off[MAXL];    // prefix of cells (offset into the tobj workspace)
     int nblk[MAXL];         // dense workgroups per level
     int blk_off[MAXL];
     unsigned *tobj;         // [sum cells] float bits (>= 0), zeroed
-    float *slots;           // [nl][na*nt*NOFF][SLOT] = {box loss or -1 (invalid), cls bce sum, clamp(iou,0,1)}
+    float *slots;           // [nl][na*nt*NOFF][SLOT] = {box loss or -1 (invalid), cls bce sum, clamp(iou,0,1)}; GEN: the third is -1 when invalid
     float *auto_iou;        // [MAXL] per level: mean of the entries' clamped IoU (SlideLoss), 0.5 when the level has none
     int *nent;              // [MAXL] entries per level, zeroed
     int *head;              // [sum cells] last entry pushed onto the cell's list, -1 = none (only with gradients)
@@ -117,6 +131,149 @@ __device__ __forceinline__ Dual ciou_xywh(Dual px, Dual py, Dual pw, Dual ph, fl
     const Dual v = (da * da) * (4.f / (3.14159265358979323846f * 3.14159265358979323846f));
     const float alpha = v.v / (v.v - iou.v + (1.f + CIOU_EPS));          // computed under no_grad
     return iou - (rho2 / c2 + (v * alpha + CIOU_EPS));
+}
+
+// ---- the other box rules (GEN = true).  Written term by term after utils/metrics.py, eps where the reference has it.
+__device__ __forceinline__ Dual dpowc(Dual a, float p) {                                   // torch.pow(a, p), p constant; p = 1 is the identity
+    if (p == 1.f) return a;
+    Dual r; r.v = powf(a.v, p); const float s = p * powf(a.v, p - 1.f);
+    for (int i = 0; i < 4; ++i) r.g[i] = a.g[i] * s;
+    return r;
+}
+__device__ __forceinline__ Dual dabs(Dual a) { return a.v >= 0.f ? a : a * -1.f; }
+__device__ __forceinline__ Dual dcos2asin(Dual a) {                                        // cos(2 asin(x) - pi/2), |x| <= sqrt(2)/2 where it is used
+    const float ang = asinf(a.v) * 2.f - 1.57079632679489661923f;
+    Dual r; r.v = cosf(ang); const float s = -sinf(ang) * 2.f / sqrtf(1.f - a.v * a.v);
+    for (int i = 0; i < 4; ++i) r.g[i] = a.g[i] * s;
+    return r;
+}
+__device__ __forceinline__ Dual one_minus(Dual a) { return dconst(1.f) - a; }
+__device__ __forceinline__ Dual dpow4(Dual a) { const Dual b = a * a; return b * b; }
+// (1 - exp(-omiga_w))^4 + (1 - exp(-omiga_h))^4 (utils/metrics.py:435,554,697)
+__device__ __forceinline__ Dual shape_cost(Dual ow, Dual oh) { return dpow4(one_minus(dexp(ow * -1.f))) + dpow4(one_minus(dexp(oh * -1.f))); }
+// SIoU's distance_cost + shape_cost (:540-554, :683-697); dx, dy = b2_1 + b2_2 - b1_1 - b1_2
+__device__ __forceinline__ Dual siou_cost(Dual dx, Dual dy, Dual cw, Dual ch, Dual w1, Dual h1, Dual w2, Dual h2) {
+    const Dual scw = dx * 0.5f + CIOU_EPS, sch = dy * 0.5f + CIOU_EPS;
+    const Dual sigma = dsqrt(scw * scw + sch * sch);
+    const Dual sin1 = dabs(scw) / sigma, sin2 = dabs(sch) / sigma;
+    const Dual gam = dcos2asin(sin1.v > 0.70710678118654752440f ? sin2 : sin1) + (-2.f);
+    const Dual rx = scw / cw, ry = sch / ch;
+    const Dual dist = dconst(2.f) - dexp(gam * (rx * rx)) - dexp(gam * (ry * ry));
+    return dist + shape_cost(dabs(w1 - w2) / dmax(w1, w2), dabs(h1 - h2) / dmax(h1, h2));
+}
+// What a rule hands the entry: the box term (value and derivatives), the similarity s, and 1 - inter/union (what WIoU_Scale averages)
+struct BoxOut {
+    Dual t;
+    float s, u;
+};
+enum { K_IOU = 0, K_GIOU, K_DIOU, K_CIOU, K_EIOU, K_SIOU, K_EFFICI, K_WIOU, K_SHAPE };
+// bbox_iou(x1y1x2y2=False) (utils/metrics.py:476-583) and shape_iou (:397-439); wmean: WIoU_Scale.iou_mean as this level sees it
+__device__ __forceinline__ BoxOut rule_bbox_iou(const BoxRule &br, Dual px, Dual py, Dual pw, Dual ph, float tx, float ty, float tw, float th, float wmean) {
+    const Dual b1x1 = px - pw * 0.5f, b1x2 = px + pw * 0.5f, b1y1 = py - ph * 0.5f, b1y2 = py + ph * 0.5f;
+    const Dual b2x1 = dconst(tx - tw / 2), b2x2 = dconst(tx + tw / 2), b2y1 = dconst(ty - th / 2), b2y2 = dconst(ty + th / 2);
+    const Dual inter = dclamp0(dmin(b1x2, b2x2) - dmax(b1x1, b2x1)) * dclamp0(dmin(b1y2, b2y2) - dmax(b1y1, b2y1));
+    const Dual w1 = b1x2 - b1x1, h1r = b1y2 - b1y1, h1 = h1r + CIOU_EPS;
+    const Dual w2 = b2x2 - b2x1, h2r = b2y2 - b2y1, h2 = h2r + CIOU_EPS;
+    const Dual uni = (w1 * h1 + w2 * h2 - inter) + CIOU_EPS;
+    const Dual cw = dmax(b1x2, b2x2) - dmin(b1x1, b2x1), ch = dmax(b1y2, b2y2) - dmin(b1y1, b2y1);
+    const Dual dx = (b2x1 + b2x2) - b1x1 - b1x2, dy = (b2y1 + b2y2) - b1y1 - b1y2;
+    BoxOut o;
+    o.u = 1.f - inter.v / uni.v;
+    if (br.kind == K_SHAPE) {
+        const float sw = powf(w2.v, br.shape_scale), sh = powf(h2.v, br.shape_scale);
+        const float ww = 2.f * sw / (sw + sh), hh = 2.f * sh / (sw + sh);
+        const Dual c2 = (cw * cw + ch * ch) + CIOU_EPS;
+        const Dual cd = (dx * dx) * 0.25f * hh + (dy * dy) * 0.25f * ww;
+        const Dual r = (inter / uni - cd / (c2 + CIOU_EPS)) - shape_cost(dabs(w1 - w2) * hh / dmax(w1, w2), dabs(h1 - h2) * ww / dmax(h1, h2)) * 0.5f;
+        o.t = one_minus(r);
+        o.s = r.v;
+        return o;
+    }
+    const Dual ratio = inter / (uni + CIOU_EPS);
+    const Dual iou = dpowc(ratio, br.alpha);
+    Dual r = iou;
+    if (br.kind == K_GIOU) {
+        const Dual c_area = cw * ch + CIOU_EPS;
+        r = iou - dpowc((c_area - uni) / c_area + CIOU_EPS, br.alpha);
+    } else if (br.kind != K_IOU) {
+        const Dual c2 = dpowc(cw * cw + ch * ch, br.alpha) + CIOU_EPS;
+        const Dual pen = dpowc((dx * dx + dy * dy) * 0.25f, br.alpha) / c2;                // rho2 / c2
+        if (br.kind == K_WIOU) {
+            const Dual e = dexp(pen);
+            if (br.scaled) {                                                               // (:465-472) beta / (delta * gamma^(beta - delta)), detached
+                const float beta = o.u / wmean;
+                o.t = (one_minus(iou) * e) * (beta / (3.f * powf(1.9f, beta - 3.f)));
+            } else {
+                o.t = one_minus(iou) * e.v;
+            }
+            o.s = iou.v;
+            return o;
+        }
+        if (br.kind == K_DIOU) {
+            r = iou - pen;
+        } else if (br.kind == K_CIOU || br.kind == K_EFFICI) {
+            const Dual da = datan(w2 / h2) - datan(w1 / h1);
+            const Dual v = (da * da) * (4.f / (3.14159265358979323846f * 3.14159265358979323846f));
+            const float a = v.v / (v.v - iou.v + (1.f + CIOU_EPS));                        // computed under no_grad
+            if (br.kind == K_CIOU) {
+                r = iou - (pen + dpowc(v * a + CIOU_EPS, br.alpha));
+            } else {
+                const Dual wd = w1 - w2, hd = h1r - h2r;
+                r = iou - (pen + (wd * wd) / (cw * cw + CIOU_EPS) + (hd * hd) / (ch * ch + CIOU_EPS) + v * a);
+            }
+        } else if (br.kind == K_EIOU) {
+            const Dual rw = w2 - w1, rh = h2r - h1r;
+            r = iou - (pen + (rw * rw) / dpowc(cw * cw + CIOU_EPS, br.alpha) + (rh * rh) / dpowc(ch * ch + CIOU_EPS, br.alpha));
+        } else {                                                                           // K_SIOU
+            r = iou - dpowc(siou_cost(dx, dy, cw, ch, w1, h1, w2, h2) * 0.5f + CIOU_EPS, br.alpha);
+        }
+    }
+    o.t = br.focal ? one_minus(r) * powf(ratio.v, br.gamma) : one_minus(r);                // Focal: (1 - r0) weighted by the detached IoU^gamma
+    o.s = r.v;
+    return o;
+}
+// bbox_inner_iou(xywh=True) with get_inner_iou (utils/metrics.py:604-702): widths and heights without eps, SIoU's eps outside the bracket
+__device__ __forceinline__ BoxOut rule_inner_iou(const BoxRule &br, Dual px, Dual py, Dual pw, Dual ph, float tx, float ty, float tw, float th) {
+    const Dual w1 = pw, h1 = ph, w2 = dconst(tw), h2 = dconst(th);
+    const Dual b1x1 = px - pw * 0.5f, b1x2 = px + pw * 0.5f, b1y1 = py - ph * 0.5f, b1y2 = py + ph * 0.5f;
+    const Dual b2x1 = dconst(tx - tw / 2), b2x2 = dconst(tx + tw / 2), b2y1 = dconst(ty - th / 2), b2y2 = dconst(ty + th / 2);
+    const float q = br.ratio;
+    const Dual hw1 = (pw * q) * 0.5f, hh1 = (ph * q) * 0.5f;
+    const float hw2 = (tw * q) / 2, hh2 = (th * q) / 2;
+    const Dual iin = dclamp0(dmin(px + hw1, dconst(tx + hw2)) - dmax(px - hw1, dconst(tx - hw2))) *
+                     dclamp0(dmin(py + hh1, dconst(ty + hh2)) - dmax(py - hh1, dconst(ty - hh2)));
+    const Dual uin = ((w1 * h1) * q * q + (w2 * h2) * q * q - iin) + CIOU_EPS;
+    const Dual inner = iin / uin;
+    const Dual inter = dclamp0(dmin(b1x2, b2x2) - dmax(b1x1, b2x1)) * dclamp0(dmin(b1y2, b2y2) - dmax(b1y1, b2y1));
+    const Dual uni = (w1 * h1 + w2 * h2 - inter) + CIOU_EPS;
+    const Dual cw = dmax(b1x2, b2x2) - dmin(b1x1, b2x1), ch = dmax(b1y2, b2y2) - dmin(b1y1, b2y1);
+    const Dual dx = (b2x1 + b2x2) - b1x1 - b1x2, dy = (b2y1 + b2y2) - b1y1 - b1y2;
+    Dual r = inner;
+    if (br.kind == K_GIOU) {
+        const Dual c_area = cw * ch + CIOU_EPS;
+        r = inner - (c_area - uni) / c_area;
+    } else if (br.kind != K_IOU) {
+        const Dual c2 = (cw * cw + ch * ch) + CIOU_EPS;
+        const Dual pen = (dx * dx + dy * dy) * 0.25f / c2;
+        if (br.kind == K_CIOU) {
+            const Dual da = datan(w2 / h2) - datan(w1 / h1);
+            const Dual v = (da * da) * (4.f / (3.14159265358979323846f * 3.14159265358979323846f));
+            const float a = v.v / (v.v - inter.v / uni.v + (1.f + CIOU_EPS));
+            r = inner - (pen + v * a);
+        } else if (br.kind == K_EIOU) {
+            const Dual rw = (b2x2 - b2x1) - (b1x2 - b1x1), rh = (b2y2 - b2y1) - (b1y2 - b1y1);
+            r = inner - (pen + (rw * rw) / (cw * cw + CIOU_EPS) + (rh * rh) / (ch * ch + CIOU_EPS));
+        } else if (br.kind == K_SIOU) {
+            r = (inner - siou_cost(dx, dy, cw, ch, w1, h1, w2, h2) * 0.5f) + CIOU_EPS;
+        } else {                                                                           // K_DIOU
+            r = inner - pen;
+        }
+    }
+    BoxOut o;
+    o.t = one_minus(r);
+    o.s = r.v;
+    o.u = 0.f;
+    return o;
 }
 
 __device__ __forceinline__ float softplus_neg(float x) { return fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x))); }
@@ -188,11 +345,13 @@ __device__ __forceinline__ Triple load_triple(const LossDescN &d, int l, int an,
 // One entry (triple, offset k): its cell, the decoded box, CIoU with the derivatives w.r.t. the four box logits
 struct Entry {
     size_t cell;
-    Dual c;                 // the box term's similarity: CIoU, or (1-r) CIoU + r NWD with the NWD branch on; box loss = 1 - c.v
-    float iou01;            // what goes to the objectness target / SlideLoss mean: clamp(c.v, 0, 1)
+    Dual t;                 // the box term: its value and d / d (px, py, pw, ph).  Default rule: 1 - c with c the CIoU, or (1-r) CIoU + r NWD
+    float iou01;            // the similarity s as the objectness target / SlideLoss mean take it: clamp(s, 0, 1), s blended with the NWD likewise
+    float u;                // scaled WIoU: 1 - inter/union, what the level's running-mean update averages
     float s0, s1, s2, s3;
 };
-__device__ __forceinline__ Entry eval_entry(const LossDescN &d, int no, const float *pl, const Triple &r, int an, int k) {
+template <bool GEN>
+__device__ __forceinline__ Entry eval_entry(const LossDescN &d, const BoxRule &br, float wmean, int no, const float *pl, const Triple &r, int an, int k) {
     const float offx[NOFF] = {0.f, 0.5f, 0.f, -0.5f, 0.f}, offy[NOFF] = {0.f, 0.f, 0.5f, 0.f, -0.5f};
     int gi = (int)(r.gx - offx[k]), gj = (int)(r.gy - offy[k]);                           // .long(): truncation
     gi = min(max(gi, 0), r.nx - 1);                                                       // clamp_ (also feeds tbox)
@@ -205,15 +364,33 @@ __device__ __forceinline__ Entry eval_entry(const LossDescN &d, int no, const fl
     e.s2 = 1.f / (1.f + expf(-ps[2])); e.s3 = 1.f / (1.f + expf(-ps[3]));
     const float pxv = e.s0 * 2.f - 0.5f, pyv = e.s1 * 2.f - 0.5f;
     const float pwv = (e.s2 * 2.f) * (e.s2 * 2.f) * r.aw, phv = (e.s3 * 2.f) * (e.s3 * 2.f) * r.ah;
-    e.c = ciou_xywh(dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh);
-    if (d.nwd_ratio > 0.f) {                                                              // utils/loss.py:162-169
-        const Dual w = nwd_xywh(dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh, d.nwd_constant);
-        e.c = e.c * (1.f - d.nwd_ratio) + w * d.nwd_ratio;
+    if constexpr (!GEN) {
+        Dual c = ciou_xywh(dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh);
+        if (d.nwd_ratio > 0.f) {                                                          // utils/loss.py:162-169
+            const Dual w = nwd_xywh(dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh, d.nwd_constant);
+            c = c * (1.f - d.nwd_ratio) + w * d.nwd_ratio;
+        }
+        e.t.v = 1.f - c.v;                                                                // exact negations: the sums downstream see what they saw
+        for (int i = 0; i < 4; ++i) e.t.g[i] = -c.g[i];
+        e.iou01 = fminf(fmaxf(c.v, 0.f), 1.f);
+        e.u = 0.f;
+    } else {
+        const BoxOut o = br.inner ? rule_inner_iou(br, dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh)
+                                  : rule_bbox_iou(br, dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh, wmean);
+        e.t = o.t;
+        float s = o.s;
+        if (d.nwd_ratio > 0.f) {                                                          // lbox += (1-r) box term + r (1 - nwd); s blended the same way
+            const Dual w = nwd_xywh(dvar(pxv, 0), dvar(pyv, 1), dvar(pwv, 2), dvar(phv, 3), tbx, tby, r.gw, r.gh, d.nwd_constant);
+            e.t = e.t * (1.f - d.nwd_ratio) + one_minus(w) * d.nwd_ratio;
+            s = s * (1.f - d.nwd_ratio) + w.v * d.nwd_ratio;
+        }
+        e.iou01 = fminf(fmaxf(s, 0.f), 1.f);
+        e.u = o.u;
     }
-    e.iou01 = fminf(fmaxf(e.c.v, 0.f), 1.f);
     return e;
 }
 
+template <bool GEN>
 __global__ __launch_bounds__(256) void loss_match_kernel(const LossArgs a) {
     const LossDescN &d = a.d;
     const int l = blockIdx.y;
@@ -223,15 +400,17 @@ __global__ __launch_bounds__(256) void loss_match_kernel(const LossArgs a) {
     const int an = idx / d.nt, t = idx % d.nt;                 // anchor-major like targets.repeat(na,1,1)
     float *slot = a.slots + ((size_t)l * per_level + idx) * NOFF * SLOT;
     for (int k = 0; k < NOFF; ++k) slot[k * SLOT] = -1.f;      // invalid
+    if constexpr (GEN)
+        for (int k = 0; k < NOFF; ++k) slot[k * SLOT + 2] = -1.f;   // a rule's box term is not sign-bound: the clamped similarity carries the mark
     const Triple r = load_triple(d, l, an, t);
     if (!r.ok) return;
     const float *pl = d.p[l];
     int emitted = 0;
     for (int k = 0; k < NOFF; ++k) {
         if (!r.use[k]) continue;
-        const Entry e = eval_entry(d, a.no, pl, r, an, k);
-        slot[k * SLOT] = 1.f - e.c.v;
-        slot[k * SLOT + 1] = 0.f;
+        const Entry e = eval_entry<GEN>(d, a.r, 1.f, a.no, pl, r, an, k);
+        slot[k * SLOT] = e.t.v;                                 // scaled WIoU: rewritten in 1b, once the level's mean is known
+        slot[k * SLOT + 1] = GEN && a.r.scaled ? e.u : 0.f;
         slot[k * SLOT + 2] = e.iou01;
         atomicMax(a.tobj + a.cell_off[l] + e.cell, __float_as_uint((1.f - d.gr) + d.gr * e.iou01));
         if (d.grad[l]) {                                        // push onto the cell's list; 1b sums the list in a fixed order
@@ -245,6 +424,8 @@ __global__ __launch_bounds__(256) void loss_match_kernel(const LossArgs a) {
 
 // ------------------------------------------------------------------------------------------------ 1a. per-level mean IoU (SlideLoss)
 // auto_iou = iou.mean() over the level's entries (utils/loss.py:180); 0.5 - SlideLoss's default - for a level without entries (:191-194)
+// MODE 0: the default rule; 1: a rule (the validity mark sits in the third slot); 2: scaled WIoU's mean of 1 - inter/union (second slot), kept in double
+template <int MODE>
 __global__ __launch_bounds__(256) void loss_level_mean_kernel(const LossArgs a) {
     __shared__ double red[256];
     const LossDescN &d = a.d;
@@ -253,17 +434,33 @@ __global__ __launch_bounds__(256) void loss_level_mean_kernel(const LossArgs a) 
     const float *sl = a.slots + (size_t)l * per_level * SLOT;
     double s = 0.0;
     for (int i = threadIdx.x; i < per_level; i += 256)
-        if (sl[i * SLOT] >= 0.f) s += sl[i * SLOT + 2];
+        if (sl[i * SLOT + (MODE ? 2 : 0)] >= 0.f) s += sl[i * SLOT + (MODE == 2 ? 1 : 2)];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
         if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.auto_iou[l] = a.nent[l] ? (float)(red[0] / a.nent[l]) : 0.5f;
+    if constexpr (MODE == 2) {
+        if (threadIdx.x == 0) a.wiou_lvl[l] = a.nent[l] ? red[0] / a.nent[l] : 0.0;
+    } else {
+        if (threadIdx.x == 0) a.auto_iou[l] = a.nent[l] ? (float)(red[0] / a.nent[l]) : 0.5f;
+    }
+}
+// WIoU_Scale._update (utils/metrics.py:459-462) for the levels of one call, in level order, by one lane: a level with entries moves the running mean
+// (when training) before its own factor is formed; what each level divides by is left in wiou_lvl
+__global__ void loss_wiou_state_kernel(const LossArgs a) {
+    if (threadIdx.x || blockIdx.x) return;
+    double m = *a.r.wiou_mean;
+    for (int l = 0; l < a.d.nl; ++l) {
+        if (a.nent[l] && a.r.train) m = (1.0 - a.r.momentum) * m + a.r.momentum * a.wiou_lvl[l];
+        a.wiou_lvl[l] = m;
+    }
+    *a.r.wiou_mean = m;
 }
 
 // ------------------------------------------------------------------------------------------------ 1b. gradient of the matched entries
+template <bool GEN>
 __global__ __launch_bounds__(256) void loss_scatter_kernel(const LossArgs a) {
     const LossDescN &d = a.d;
     const int l = blockIdx.y;
@@ -278,10 +475,15 @@ __global__ __launch_bounds__(256) void loss_scatter_kernel(const LossArgs a) {
     const int base = (int)l * per_level * NOFF;
     const float ai = d.slide ? a.auto_iou[l] : 0.5f;
     float *slot = a.slots + ((size_t)l * per_level + idx) * NOFF * SLOT;
+    const float wm = GEN && a.r.scaled ? (float)a.wiou_lvl[l] : 1.f;
     for (int k = 0; k < NOFF; ++k) {
         if (!r.use[k]) continue;
-        const Entry own = eval_entry(d, a.no, pl, r, an, k);
+        const Entry own = eval_entry<GEN>(d, a.r, wm, a.no, pl, r, an, k);
         const float *ps = pl + own.cell * a.no;
+        if (GEN && a.r.scaled) {
+            slot[k * SLOT] = own.t.v;
+            slot[k * SLOT + 1] = 0.f;
+        }
         if (d.nc > 1) {                                          // this entry's class BCE (utils/loss.py:182-189)
             float csum = 0.f;
             for (int j = 0; j < d.nc; ++j) {
@@ -308,11 +510,11 @@ __global__ __launch_bounds__(256) void loss_scatter_kernel(const LossArgs a) {
             const int rel = m - base, k2 = rel % NOFF, idx2 = rel / NOFF;
             const int an2 = idx2 / d.nt, t2 = idx2 % d.nt;       // same level, same anchor (the cell index contains it)
             const Triple r2 = load_triple(d, l, an2, t2);
-            const Entry e = eval_entry(d, a.no, pl, r2, an2, k2);
-            gb[0] += -e.c.g[0] * 2.f * e.s0 * (1.f - e.s0);     // d(1 - similarity)/d logits, unscaled
-            gb[1] += -e.c.g[1] * 2.f * e.s1 * (1.f - e.s1);
-            gb[2] += -e.c.g[2] * 8.f * e.s2 * e.s2 * (1.f - e.s2) * r2.aw;
-            gb[3] += -e.c.g[3] * 8.f * e.s3 * e.s3 * (1.f - e.s3) * r2.ah;
+            const Entry e = eval_entry<GEN>(d, a.r, wm, a.no, pl, r2, an2, k2);
+            gb[0] += e.t.g[0] * 2.f * e.s0 * (1.f - e.s0);      // d(box term)/d logits, unscaled
+            gb[1] += e.t.g[1] * 2.f * e.s1 * (1.f - e.s1);
+            gb[2] += e.t.g[2] * 8.f * e.s2 * e.s2 * (1.f - e.s2) * r2.aw;
+            gb[3] += e.t.g[3] * 8.f * e.s3 * e.s3 * (1.f - e.s3) * r2.ah;
             if (d.nc > 1) {
                 for (int j = 0; j < d.nc; ++j) {
                     float v, g_;
@@ -370,6 +572,7 @@ __global__ __launch_bounds__(256) void loss_dense_kernel(const LossArgs a, int l
 // ------------------------------------------------------------------------------------------------ 4. finish
 // grid (LOSS_FOLD, nl): box / cls sums of one segment of a level's slots - thread-strided partial sums in double, then a tree over the 256 lanes
 // (fixed order).  Round 4: the finish kernel did this walk alone, one workgroup for every level: 227 us per step.
+template <bool GEN>
 __global__ __launch_bounds__(256) void loss_slots_fold_kernel(const LossArgs a) {
     __shared__ double red[2][256];
     const LossDescN &d = a.d;
@@ -378,16 +581,17 @@ __global__ __launch_bounds__(256) void loss_slots_fold_kernel(const LossArgs a) 
     const float *sl = a.slots + (size_t)l * per_level * SLOT;
     double sb = 0.0, sc = 0.0;
     for (int i = i0 + threadIdx.x; i < i1; i += 4 * 256) {
-        float vb[4], vc[4];
+        float vb[4], vc[4], vm[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int j = i + u * 256;
             vb[u] = j < i1 ? sl[(size_t)j * SLOT] : -1.f;
             vc[u] = j < i1 ? sl[(size_t)j * SLOT + 1] : 0.f;
+            vm[u] = !GEN ? vb[u] : j < i1 ? sl[(size_t)j * SLOT + 2] : -1.f;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (vb[u] >= 0.f) { sb += vb[u]; sc += vc[u]; }
+            if (vm[u] >= 0.f) { sb += vb[u]; sc += vc[u]; }
     }
     red[0][threadIdx.x] = sb;
     red[1][threadIdx.x] = sc;
@@ -458,6 +662,8 @@ static int plan(const somi_loss_desc &pd, const somi_loss_level *l5, LossArgs &a
     d.anchor_t = pd.anchor_t; d.cp = pd.cp; d.cn = pd.cn; d.gr = pd.gr;
     d.fl_gamma = pd.fl_gamma; d.slide = pd.slide; d.nwd_ratio = pd.nwd_ratio; d.nwd_constant = pd.nwd_constant;
     a.no = d.nc + 5;
+    a.r = BoxRule{K_CIOU, 0, 0, 0, 0, 1.f, 0.5f, 0.f, 0.5f, 0.0, nullptr};   // the default rule
+    a.wiou_lvl = nullptr;
     long off = 0;
     int boff = 0;
     for (int l = 0; l < MAXL; ++l) {
@@ -486,6 +692,21 @@ static size_t workspace_bytes_of(const LossArgs &a) {
     return tobj + 256 + slots + part + tobj + next + MAXL * LOSS_FOLD * 2 * sizeof(double);   // + the per-cell list heads, the entry links of the gradient pass, the slot-segment sums
 }
 
+// The rule into the plan; *gen: whether it needs the rule kernels (false: the default rule, which keeps its own)
+static int plan_rule(const somi_loss_box_rule &pr, LossArgs &a, bool *gen) {
+    SOMI_REQUIRE(pr.kind >= K_IOU && pr.kind <= K_SHAPE, SOMI_EINVAL, "loss: unknown box rule %d", pr.kind);
+    SOMI_REQUIRE(pr.alpha >= 1.f, SOMI_EINVAL, "loss: box rule alpha %g < 1", pr.alpha);
+    SOMI_REQUIRE(!pr.inner || (pr.inner_ratio > 0.f && pr.kind <= K_SIOU), SOMI_EINVAL, "loss: inner ratio %g / no inner form of rule %d", pr.inner_ratio, pr.kind);
+    SOMI_REQUIRE(!pr.focal || pr.gamma >= 0.f, SOMI_EINVAL, "loss: focal gamma %g < 0", pr.gamma);
+    const bool scaled = pr.kind == K_WIOU && pr.wiou_scaled;
+    SOMI_REQUIRE(!scaled || pr.wiou_mean, SOMI_EINVAL, "loss: scaled WIoU without its running mean");
+    a.r = BoxRule{pr.kind, pr.focal != 0, pr.inner != 0, scaled, pr.wiou_train != 0, pr.alpha, pr.gamma, pr.inner_ratio, pr.shape_scale,
+                  1.0 - pow(0.5, 1.0 / 7000.0), scaled ? pr.wiou_mean : nullptr};
+    *gen = !(pr.kind == K_CIOU && !pr.focal && !pr.inner && pr.alpha == 1.f);
+    return 0;
+}
+
+template <bool GEN>
 static int run_loss(const LossArgs &planned, float *out, void *workspace, size_t workspace_bytes, somi_stream_t stream, const char *what) {
     LossArgs a = planned;
     const LossDescN &d = a.d;
@@ -496,7 +717,8 @@ static int run_loss(const LossArgs &planned, float *out, void *workspace, size_t
     const size_t tobj_b = align_up((size_t)(a.cell_off[d.nl - 1] + a.cells[d.nl - 1]) * 4, 256);
     a.tobj = reinterpret_cast<unsigned *>(w); w += tobj_b;
     a.nent = reinterpret_cast<int *>(w);
-    a.auto_iou = reinterpret_cast<float *>(w + 64); w += 256;          // same zeroed 256-byte block: counters, then the level means
+    a.auto_iou = reinterpret_cast<float *>(w + 64);                    // same zeroed 256-byte block: counters, then the level means
+    a.wiou_lvl = reinterpret_cast<double *>(w + 128); w += 256;        // ... and scaled WIoU's
     a.slots = reinterpret_cast<float *>(w); w += align_up((size_t)d.nl * d.na * (d.nt > 0 ? d.nt : 1) * NOFF * SLOT * 4, 256);
     a.partial = reinterpret_cast<float *>(w); w += align_up((size_t)(a.blk_off[d.nl - 1] + a.nblk[d.nl - 1]) * 4, 256);
     a.head = reinterpret_cast<int *>(w); w += tobj_b;
@@ -510,15 +732,20 @@ static int run_loss(const LossArgs &planned, float *out, void *workspace, size_t
         if (d.grad[l]) (void)hipMemsetAsync(d.grad[l], 0, (size_t)a.cells[l] * a.no * 4, s);
     SOMI_REQUIRE(d.fl_gamma >= 0.f && d.nwd_ratio >= 0.f && d.nwd_ratio <= 1.f && (d.nwd_ratio == 0.f || d.nwd_constant > 0.f), SOMI_EINVAL,
                  "loss: bad focal gamma / NWD ratio / NWD constant");
+    const bool scaled = GEN && a.r.scaled;
     if (d.nt > 0) {
-        hipLaunchKernelGGL(loss_match_kernel, dim3(cdiv((long)d.na * d.nt, 256), d.nl), dim3(256), 0, s, a);
-        if (d.slide) hipLaunchKernelGGL(loss_level_mean_kernel, dim3(d.nl), dim3(256), 0, s, a);
-        if (any_grad || d.nc > 1) hipLaunchKernelGGL(loss_scatter_kernel, dim3(cdiv((long)d.na * d.nt, 256), d.nl), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(loss_match_kernel<GEN>, dim3(cdiv((long)d.na * d.nt, 256), d.nl), dim3(256), 0, s, a);
+        if (d.slide) hipLaunchKernelGGL(loss_level_mean_kernel<GEN ? 1 : 0>, dim3(d.nl), dim3(256), 0, s, a);
+        if (scaled) {
+            hipLaunchKernelGGL(loss_level_mean_kernel<2>, dim3(d.nl), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(loss_wiou_state_kernel, dim3(1), dim3(64), 0, s, a);
+        }
+        if (any_grad || d.nc > 1 || scaled) hipLaunchKernelGGL(loss_scatter_kernel<GEN>, dim3(cdiv((long)d.na * d.nt, 256), d.nl), dim3(256), 0, s, a);
     } else if (d.slide) {
-        hipLaunchKernelGGL(loss_level_mean_kernel, dim3(d.nl), dim3(256), 0, s, a);     // no entries anywhere: every level gets the default
+        hipLaunchKernelGGL(loss_level_mean_kernel<GEN ? 1 : 0>, dim3(d.nl), dim3(256), 0, s, a);     // no entries anywhere: every level gets the default
     }
     for (int l = 0; l < d.nl; ++l) hipLaunchKernelGGL(loss_dense_kernel, dim3(a.nblk[l]), dim3(256), 0, s, a, l);
-    if (d.nt > 0) hipLaunchKernelGGL(loss_slots_fold_kernel, dim3(LOSS_FOLD, d.nl), dim3(256), 0, s, a);
+    if (d.nt > 0) hipLaunchKernelGGL(loss_slots_fold_kernel<GEN>, dim3(LOSS_FOLD, d.nl), dim3(256), 0, s, a);
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, a, out);
     return launch_status(what);
 }
@@ -538,7 +765,7 @@ extern "C" int somi_yolo_loss_f32(const somi_loss_desc *dp, float *out8, void *w
     LossArgs a;
     int rc = plan(*dp, nullptr, a);
     if (rc) return rc;
-    return run_loss(a, out8, workspace, workspace_bytes, stream, "somi_yolo_loss_f32");
+    return run_loss<false>(a, out8, workspace, workspace_bytes, stream, "somi_yolo_loss_f32");
 }
 
 extern "C" size_t somi_loss5_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5) {
@@ -553,5 +780,24 @@ extern "C" int somi_yolo_loss5_f32(const somi_loss_desc *dp, const somi_loss_lev
     LossArgs a;
     int rc = plan(*dp, l5, a);
     if (rc) return rc;
-    return run_loss(a, out9, workspace, workspace_bytes, stream, "somi_yolo_loss5_f32");
+    return run_loss<false>(a, out9, workspace, workspace_bytes, stream, "somi_yolo_loss5_f32");
+}
+
+extern "C" size_t somi_loss_rule_workspace_bytes(const somi_loss_desc *d, const somi_loss_level *l5, const somi_loss_box_rule *rule) {
+    LossArgs a;
+    bool gen;
+    if (!d || !rule || plan(*d, l5, a) || plan_rule(*rule, a, &gen)) return 0;
+    return workspace_bytes_of(a);
+}
+
+extern "C" int somi_yolo_loss_rule_f32(const somi_loss_desc *dp, const somi_loss_level *l5, const somi_loss_box_rule *rule, float *out9, void *workspace,
+                                       size_t workspace_bytes, somi_stream_t stream) {
+    SOMI_REQUIRE(dp && rule && out9 && workspace, SOMI_EINVAL, "loss: null argument");
+    LossArgs a;
+    bool gen = false;
+    int rc = plan(*dp, l5, a);
+    if (!rc) rc = plan_rule(*rule, a, &gen);
+    if (rc) return rc;
+    return gen ? run_loss<true>(a, out9, workspace, workspace_bytes, stream, "somi_yolo_loss_rule_f32")
+               : run_loss<false>(a, out9, workspace, workspace_bytes, stream, "somi_yolo_loss_rule_f32");
 }

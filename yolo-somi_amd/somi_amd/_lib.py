@@ -41,6 +41,13 @@ class LossLevel(C.Structure):
     _fields_ = [('p', C.c_void_p), ('grad', C.c_void_p), ('ny', C.c_int32), ('nx', C.c_int32), ('balance', C.c_float)]
 
 
+class LossBoxRule(C.Structure):
+    """struct somi_loss_box_rule (include/somi_hip.h): which box-regression rule the loss scores matched boxes with."""
+    _fields_ = [('kind', C.c_int32), ('focal', C.c_int32), ('inner', C.c_int32), ('wiou_scaled', C.c_int32),
+                ('alpha', C.c_float), ('gamma', C.c_float), ('inner_ratio', C.c_float), ('shape_scale', C.c_float),
+                ('wiou_mean', C.c_void_p), ('wiou_train', C.c_int32)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -173,6 +180,8 @@ SIGNATURES = {
     'somi_yolo_loss_f32': (I, [C.POINTER(LossDesc), P, P, Z, S]),
     'somi_loss5_workspace_bytes': (Z, [C.POINTER(LossDesc), C.POINTER(LossLevel)]),
     'somi_yolo_loss5_f32': (I, [C.POINTER(LossDesc), C.POINTER(LossLevel), P, P, Z, S]),
+    'somi_loss_rule_workspace_bytes': (Z, [C.POINTER(LossDesc), C.POINTER(LossLevel), C.POINTER(LossBoxRule)]),
+    'somi_yolo_loss_rule_f32': (I, [C.POINTER(LossDesc), C.POINTER(LossLevel), C.POINTER(LossBoxRule), P, P, Z, S]),
     'somi_maxpool2_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_maxpool2_bwd_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
@@ -223,7 +232,8 @@ def lib():
             fn.restype, fn.argtypes = res, args
         if L.somi_abi_version() != ABI_VERSION and not lax:
             raise RuntimeError('libsomi_hip.so ABI version mismatch')
-        if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)):
+        if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)
+                        or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

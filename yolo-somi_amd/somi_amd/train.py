@@ -63,7 +63,7 @@ def scheduler_step(optimizer, epoch, lf):
 
 class TrainStep:
     def __init__(self, model, hyp, batch_size, dist=None, nbs=64, bucket_mb=48, accumulate=1, adam=True, sync_bn=False, amp=None, multi_scale=False, imgsz=640,
-                 broadcast_buffers=True):
+                 broadcast_buffers=True, loss_kwargs=None):
         """accumulate: optimizer step every `accumulate` batches (train.py:121,252,272: max(round(nbs / total_batch), 1) in the
         reference loop; gradients simply keep accumulating in the flat buffers in between).  Default 1: every batch.
         sync_bn: --sync-bn (train.py:165-167, SyncBatchNorm.convert_sync_batchnorm): every BatchNorm layer takes its training
@@ -76,7 +76,8 @@ class TrainStep:
         [0.5, 1.5] imgsz on the stride grid before the forward pass (Python's `random`, as the reference draws it).
         broadcast_buffers: N > 1 only - DDP's default (train.py:208-209): rank 0's BatchNorm running statistics overwrite every rank's before
         each forward (one flat-buffer broadcast on the side stream, ddp.GradBuckets.broadcast_buffers).  False: the statistics are made equal
-        once at construction and then follow each rank's own shard (rank 0's are the ones EMA / checkpoints use either way)."""
+        once at construction and then follow each rank's own shard (rank 0's are the ones EMA / checkpoints use either way).
+        loss_kwargs: keywords for this step's ComputeLoss (the box rule: iou=, focal=, alpha=, gamma=, inner_ratio=, shape_scale=, wiou_scale=)."""
         if not next(model.parameters()).is_cuda:
             raise RuntimeError('TrainStep runs on the MI355X only (no CPU fallback)')
         self.model, self.dist = model, dist
@@ -93,7 +94,7 @@ class TrainStep:
         model.hyp = hyp
         model.train()
         self.optimizer = build_optimizer(model, hyp, batch_size * self.world, nbs=nbs, ema=True, adam=adam)
-        self.compute_loss = ComputeLoss(model)
+        self.compute_loss = ComputeLoss(model, **(loss_kwargs or {}))
         self.accumulate, self._since_step = max(int(accumulate), 1), 0
         self.broadcast_buffers = bool(broadcast_buffers)
         self.buckets = None
