@@ -12,7 +12,14 @@
  *    allocates, frees, copies or synchronises: outputs and workspaces are caller-owned;
  *  - tensors are fp32, activations are NHWC with an explicit channel stride (`*_cs`, in floats)
  *    and channel offset (`*_coff`) so that channel slices / concatenations need no copy;
- *    vectorised paths need `*_cs % 4 == 0`, `*_coff % 4 == 0` and 16-byte aligned bases;
+ *  - THE SLICE RULE, checked the same way at every entry point that takes a slice (pointer, `*_cs`,
+ *    `*_coff`): the pointer is non-NULL and 16-byte aligned; `*_cs` > 0 and `*_cs % 4 == 0`;
+ *    `*_coff` >= 0 and `*_coff % 4 == 0`; and the channels the entry point touches,
+ *    [coff, coff + width), lie inside the stride: width > 0, coff + width <= cs.  width is C unless
+ *    the entry point's comment names more (4 * C for SPPF, heads * 128 for attention's qkv, ...).
+ *    An optional slice (residual, accumulate, ...) is checked when its pointer is given.  A slice
+ *    that breaks the rule is SOMI_EINVAL, and somi_last_error() names the parameter and the reason:
+ *    "add: out = [12, 20) of 16 channels: runs past the channel stride";
  *  - `stream` is a hipStream_t passed as void*; kernels are enqueued on it and the call returns;
  *  - return value: 0 on success, a negative SOMI_E* code on a rejected argument (nothing was
  *    launched), or a positive hipError_t from the launch.  somi_last_error() gives the text.
@@ -250,7 +257,7 @@ int somi_sppf_pool_nhwc_f32(float *buf, int B, int H, int W, int C, int cs, int 
  * (row-major) in its 5x5 window of the previous slice: `codes` = 3*B*H*W*C bytes, handed to somi_sppf_pool_bwd_nhwc_f32 as its workspace with buf = NULL. */
 int somi_sppf_pool_codes_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, somi_stream_t stream);
 
-/* Max-pooling outside SPPF's chained 5x5 (pool.hip).  NHWC fp32 channel slices; C, strides and offsets are multiples of 4.
+/* Max-pooling outside SPPF's chained 5x5 (pool.hip).  NHWC fp32 channel slices (the slice rule above); C is a multiple of 4.
  * Routing rule of every entry: a pooled value's gradient goes to the FIRST maximum of its full window in row-major order (torch's max_pool2d
  * autograd on the CPU); the forward leaves that position as one byte r * k + q per pooled element (`codes`, NULL in eval), the backward gathers by
  * it: owner-computes, a fixed order of terms, no float atomics.
@@ -272,7 +279,7 @@ int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, 
 int somi_spp_pool_bwd_nhwc_f32(const void *codes, float *dbuf, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
                                somi_stream_t stream);
 
-/* The learned 2x upsamplers of the neck (upsample.hip).  NHWC fp32 channel slices; C, strides and offsets are multiples of 4.  New symbols only: the ABI
+/* The learned 2x upsamplers of the neck (upsample.hip).  NHWC fp32 channel slices (the slice rule above); C is a multiple of 4.  New symbols only: the ABI
  * version does not move.
  *
  * carafe: out[c, 2h+dy, 2w+dx] = sum_{a,b} softmax_t(logits[t*4 + dy*2 + dx, h, w])[a*k+b] * x[c, h+a-r, w+b-r], k = k_up (3 or 5), r = k / 2, x zero outside
@@ -556,8 +563,8 @@ int somi_pack_dgrad_weights_f32(const float *w_packed, float *w_dgrad, int Cout,
  * Grouped / depthwise convolution (Conv with g > 1, DWConv, the GhostConv cheap operation; models/common.py:53-70, 9580-9583, 2001-2011).
  * NHWC fp32; C1 input and C2 output channels in `groups` groups of cin_g = C1/groups and cout_g = C2/groups; k in {1, 3, 5},
  * stride 1 or 2, pad k/2, dilation 1; cin_g <= 16.  Depthwise (cin_g = cout_g = 1) reads float4 quads of channels.
- * Weights are packed [k*k][cin_g][w_cs] (tap-major, output channel fastest, columns >= C2 zero).  Channel slices: offsets and row
- * strides multiples of 4.  Deterministic: fixed-order reductions, no float atomics.  fp32 only (the conv precision switch does not apply).
+ * Weights are packed [k*k][cin_g][w_cs] (tap-major, output channel fastest, columns >= C2 zero).  Channel slices follow the slice
+ * rule above (x and dy are read to their width rounded up to 4).  Deterministic: fixed-order reductions, no float atomics.  fp32 only (the conv precision switch does not apply).
  *
  * Forward: y[.., y_coff + co] = act(conv + bias) [+ residual] for co < Cw (Cw >= C2, a multiple of 4; channels C2..Cw come out zero
  * when their weights and bias are).  stat_sum / stat_sumsq (optional, [somi_gconv2d_stat_rows][Cw] each): per-channel partial sums of
@@ -580,8 +587,8 @@ int somi_gconv2d_wgrad_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int
 /* ------------------------------------------------------------------------------------------
  * PSA multi-head spatial self-attention (AttentionPSA, models/common.py:7203-7230; yolov10.yaml).  NHWC fp32, key_dim 32 and head_dim
  * 64 fixed (scale 32^-0.5).  q, k and v are read in place from the qkv Conv's output: per pixel (row stride qkv_cs), head h's channels
- * qkv_coff + h*128 + [0,32) are q, + [32,64) k and + [64,128) v.  N = H*W tokens per image, any N >= 1.  Channel offsets and row
- * strides are multiples of 4.  The N x N matrix never reaches memory.  Deterministic: fixed-order sums, no float atomics.  fp32 only.
+ * qkv_coff + h*128 + [0,32) are q, + [32,64) k and + [64,128) v.  N = H*W tokens per image, any N >= 1.  Slices of heads*128 (qkv, dqkv)
+ * and heads*64 (o, dout) channels under the slice rule above.  The N x N matrix never reaches memory.  Deterministic: fixed-order sums, no float atomics.  fp32 only.
  *
  * Forward: o[.., o_coff + h*64 + d] = sum_j softmax_j(q.k_j * scale) v_j[d].  lse (optional, (B, heads, N)): the natural-log
  * log-sum-exp of each row's scaled scores, for the backward pass.  v_out (optional): v written contiguously as (B, N, heads*64),
@@ -604,7 +611,7 @@ int somi_psa_attention_backward_f32(const float *qkv, int qkv_cs, int qkv_coff, 
  *   `nn.Upsample(None, 2, 'nearest')` folded into the copy.
  *     reduce = 0:  dst[b, h, w, dst_coff + c] = src[b, h >> up, w >> up, src_coff + c]      src (B,Hs,Ws,src_cs) -> dst (B,Hs<<up,Ws<<up,dst_cs)
  *     reduce = 1:  dst[b, h, w, dst_coff + c] (+)= sum_{i,j < 2^up} src[b, (h<<up)+i, (w<<up)+j, src_coff + c]   (the adjoint; fixed order)
- *   C, the strides and the offsets are multiples of 4, bases 16-byte aligned.
+ *   C is a multiple of 4; both slices follow the slice rule above.
  * somi_space_to_depth_nhwc_f32 - `Focus` (models/common.py:1996): y[b,h,w,q*C+c] = x[b, 2h+(q&1), 2w+(q>>1), c], q = 0..3;
  *   inverse = 1: x is the gradient in y's layout (B,Ho,Wo,x_cs), y receives the gradient in the image layout (B,2Ho,2Wo,y_cs).
  * somi_detect_plain_decode_f32 - `Detect.forward` (models/yolo.py:66-98): t (B,ny,nx,t_cs >= na*no) = the level's 1x1 conv output ->

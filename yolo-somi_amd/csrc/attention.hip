@@ -311,10 +311,6 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_dkv_kernel(AttnArgs a) {
     }
 }
 
-bool slice_ok(const void *p, int cs, int coff, int width) {
-    return p && aligned16(p) && cs > 0 && cs % 4 == 0 && coff >= 0 && coff % 4 == 0 && coff + width <= cs;
-}
-
 }  // namespace
 }  // namespace somi
 
@@ -323,9 +319,8 @@ using namespace somi;
 extern "C" int somi_psa_attention_f32(const float *qkv, int qkv_cs, int qkv_coff, int B, int N, int heads, float *o, int o_cs, int o_coff,
                                       float *lse, float *v_out, somi_stream_t stream) {
     SOMI_REQUIRE(B > 0 && N > 0 && heads > 0 && heads <= 65535 && B <= 65535, SOMI_EINVAL, "psa attention: bad sizes");
-    SOMI_REQUIRE(slice_ok(qkv, qkv_cs, qkv_coff, heads * QKV_H) && slice_ok(o, o_cs, o_coff, heads * HD) && (!lse || aligned16(lse)) &&
-                     (!v_out || aligned16(v_out)),
-                 SOMI_EINVAL, "psa attention: bad tensors or channel slices");
+    SOMI_REQUIRE_SLICES("psa attention", {"qkv", qkv, qkv_cs, qkv_coff, heads * QKV_H}, {"o", o, o_cs, o_coff, heads * HD});
+    SOMI_REQUIRE((!lse || aligned16(lse)) && (!v_out || aligned16(v_out)), SOMI_EINVAL, "psa attention: lse and v_out must be 16-byte aligned");
     AttnArgs a = {};
     a.qkv = qkv; a.qkv_cs = qkv_cs; a.qkv_coff = qkv_coff; a.out = o; a.o_cs = o_cs; a.o_coff = o_coff; a.lse_out = lse; a.v_out = v_out;
     a.B = B; a.N = N; a.heads = heads;
@@ -338,10 +333,9 @@ extern "C" int somi_psa_attention_backward_f32(const float *qkv, int qkv_cs, int
                                                float *dqkv, int g_cs, int g_coff, const float *dv_add, float *workspace,
                                                somi_stream_t stream) {
     SOMI_REQUIRE(B > 0 && N > 0 && heads > 0 && heads <= 65535 && B <= 65535, SOMI_EINVAL, "psa attention backward: bad sizes");
-    SOMI_REQUIRE(slice_ok(qkv, qkv_cs, qkv_coff, heads * QKV_H) && slice_ok(o, o_cs, o_coff, heads * HD) &&
-                     slice_ok(dout, do_cs, do_coff, heads * HD) && slice_ok(dqkv, g_cs, g_coff, heads * QKV_H) && lse && workspace &&
-                     (!dv_add || aligned16(dv_add)),
-                 SOMI_EINVAL, "psa attention backward: bad tensors or channel slices");
+    SOMI_REQUIRE_SLICES("psa attention backward", {"qkv", qkv, qkv_cs, qkv_coff, heads * QKV_H}, {"o", o, o_cs, o_coff, heads * HD},
+                        {"dout", dout, do_cs, do_coff, heads * HD}, {"dqkv", dqkv, g_cs, g_coff, heads * QKV_H});
+    SOMI_REQUIRE(lse && workspace && (!dv_add || aligned16(dv_add)), SOMI_EINVAL, "psa attention backward: needs lse, workspace and a 16-byte aligned dv_add");
     AttnArgs a = {};
     a.qkv = qkv; a.qkv_cs = qkv_cs; a.qkv_coff = qkv_coff; a.o = o; a.o_cs = o_cs; a.o_coff = o_coff; a.dout = dout; a.do_cs = do_cs;
     a.do_coff = do_coff; a.lse = lse; a.dqkv = dqkv; a.g_cs = g_cs; a.g_coff = g_coff; a.dv_add = dv_add; a.dsum = workspace;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include "../../include/somi_hip.h"
 
 namespace somi {
@@ -28,6 +29,37 @@ static inline int launch_status(const char *what) {
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline int r4(int c) { return (c + 3) / 4 * 4; }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// THE channel-slice rule (include/somi_hip.h, Conventions): nullptr if the channels [coff, coff + width) of a cs-channel NHWC tensor at p can be
+// walked by the float4 paths (p + pix * cs + coff), else why not.  width = what the entry point's kernels really touch.
+static inline const char *slice_fault(const void *p, int cs, int coff, int width) {
+    if (!p) return "null pointer";
+    if (!aligned16(p)) return "base not 16-byte aligned";
+    if (cs <= 0 || cs % 4) return "channel stride not a positive multiple of 4";
+    if (coff < 0 || coff % 4) return "channel offset not a non-negative multiple of 4";
+    if (width <= 0) return "no channels";
+    if ((long)coff + width > cs) return "runs past the channel stride";
+    return nullptr;
+}
+
+// One slice argument of an entry point; name = its pointer parameter as the header spells it.  An optional slice is checked when its pointer is given.
+struct Slice { const char *name; const void *p; int cs, coff, width; bool optional; };
+constexpr bool kOptional = true;
+static inline int slices_status(const char *who, std::initializer_list<Slice> slices) {
+    for (const Slice &s : slices)
+        if (const char *why = s.optional && !s.p ? nullptr : slice_fault(s.p, s.cs, s.coff, s.width)) {
+            set_error("%s: %s = [%d, %ld) of %d channels: %s", who, s.name, s.coff, (long)s.coff + s.width, s.cs, why);
+            return SOMI_EINVAL;
+        }
+    return 0;
+}
+// SOMI_REQUIRE_SLICES("add", {"a", a, a_cs, a_coff, C}, {"out", out, o_cs, o_coff, C}, {"residual", res, res_cs, res_coff, C, kOptional});
+#define SOMI_REQUIRE_SLICES(who, ...)                                          \
+    do {                                                                       \
+        if (::somi::slices_status(who, {__VA_ARGS__})) return SOMI_EINVAL;     \
+    } while (0)
 
 constexpr int kNumXCD = 8;
 

@@ -735,28 +735,22 @@ namespace somi {
 static int conv_launch(const somi_conv_desc *dp, somi_stream_t stream, int dgrad) {
     SOMI_REQUIRE(dp, SOMI_EINVAL, "conv: null descriptor");
     const somi_conv_desc &d = *dp;
-    SOMI_REQUIRE(d.x && d.w && d.y, SOMI_EINVAL, "conv: null tensor");
+    SOMI_REQUIRE(d.w && aligned16(d.w), SOMI_EINVAL, "conv: the weights must be given and 16 B aligned");
     SOMI_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0, SOMI_EINVAL, "conv: empty shape");
     SOMI_REQUIRE(d.kh > 0 && d.kw > 0 && d.stride > 0 && d.dil > 0 && d.pad >= 0, SOMI_EINVAL, "conv: bad geometry");
     SOMI_REQUIRE(dgrad || (d.Ho == (d.H + 2 * d.pad - (d.dil * (d.kh - 1) + 1)) / d.stride + 1 &&
                            d.Wo == (d.W + 2 * d.pad - (d.dil * (d.kw - 1) + 1)) / d.stride + 1),
                  SOMI_EINVAL, "conv: Ho/Wo (%d,%d) do not match the geometry", d.Ho, d.Wo);
-    SOMI_REQUIRE(d.Cin % 4 == 0 && d.x_cs % 4 == 0 && d.x_coff % 4 == 0 && aligned16(d.x) && aligned16(d.w),
-                 SOMI_EINVAL, "conv: Cin (%d), x_cs (%d), x_coff (%d) must be multiples of 4 and bases 16 B aligned",
-                 d.Cin, d.x_cs, d.x_coff);
-    SOMI_REQUIRE(d.x_coff + d.Cin <= d.x_cs && d.y_coff + d.Cout <= d.y_cs, SOMI_EINVAL, "conv: channel slice out of range");
+    // the data gradient runs the same launch with dy (the forward's Cout channels) as the operand, dx as the output and `accumulate` as the residual
+    const char *who = dgrad ? "conv dgrad" : "conv";
+    SOMI_REQUIRE(d.Cin % 4 == 0, SOMI_EINVAL, "%s: %s (%d): operand channel counts must be multiples of 4", who, dgrad ? "Cout" : "Cin", d.Cin);
+    SOMI_REQUIRE_SLICES(who, {dgrad ? "dy" : "x", d.x, d.x_cs, d.x_coff, d.Cin}, {dgrad ? "dx" : "y", d.y, d.y_cs, d.y_coff, d.Cout},
+                        {dgrad ? "accumulate" : "residual", d.residual, d.res_cs, d.res_coff, d.Cout, kOptional},
+                        {"residual2", d.residual2, d.res2_cs, d.res2_coff, d.Cout, kOptional});
     SOMI_REQUIRE(!d.post_scale == !d.post_shift, SOMI_EINVAL, "conv: post_scale and post_shift go together");
-    SOMI_REQUIRE(!d.residual || d.res_coff + d.Cout <= d.res_cs, SOMI_EINVAL, "conv: residual slice out of range");
     SOMI_REQUIRE(d.act >= SOMI_ACT_NONE && d.act <= SOMI_ACT_SIGMOID, SOMI_EINVAL, "conv: unknown activation %d", d.act);
     SOMI_REQUIRE((long)d.B * d.Ho * d.Wo < (1L << 31), SOMI_EINVAL, "conv: too many output pixels");
     if (d.a_chan_scale) SOMI_REQUIRE(aligned16(d.a_chan_scale), SOMI_EINVAL, "conv: a_chan_scale must be 16 B aligned");
-
-    SOMI_REQUIRE(d.y_cs % 4 == 0 && d.y_coff % 4 == 0 && aligned16(d.y), SOMI_EINVAL,
-                 "conv: y_cs (%d), y_coff (%d) must be multiples of 4 and y 16 B aligned", d.y_cs, d.y_coff);
-    SOMI_REQUIRE(!d.residual || (d.res_cs % 4 == 0 && d.res_coff % 4 == 0 && aligned16(d.residual)), SOMI_EINVAL,
-                 "conv: residual stride / offset must be multiples of 4 and 16 B aligned");
-    SOMI_REQUIRE(!d.residual2 || (d.res2_cs % 4 == 0 && d.res2_coff % 4 == 0 && aligned16(d.residual2) && d.res2_coff + d.Cout <= d.res2_cs),
-                 SOMI_EINVAL, "conv: residual2 slice must be 16 B aligned and inside its channel stride");
     SOMI_REQUIRE((!d.bias || aligned16(d.bias)) && (!d.post_scale || (aligned16(d.post_scale) && aligned16(d.post_shift))),
                  SOMI_EINVAL, "conv: bias / post_scale / post_shift must be 16 B aligned");
     ConvArgs a;
@@ -826,7 +820,7 @@ extern "C" int somi_conv2d_dgrad_nhwc_f32(const somi_conv_desc *f, const float *
                                           float *dx, int dx_cs, int dx_coff, const float *accumulate, int acc_cs, int acc_coff,
                                           somi_stream_t stream) {
     using namespace somi;
-    SOMI_REQUIRE(f && dy && wt && dx, SOMI_EINVAL, "conv dgrad: null argument");
+    SOMI_REQUIRE(f && wt, SOMI_EINVAL, "conv dgrad: null descriptor or weights");
     SOMI_REQUIRE(f->dil == 1, SOMI_ENOTIMPL, "conv dgrad: dilation 1 only");
     SOMI_REQUIRE(f->Ho == (f->H + 2 * f->pad - f->kh) / f->stride + 1 && f->Wo == (f->W + 2 * f->pad - f->kw) / f->stride + 1,
                  SOMI_EINVAL, "conv dgrad: Ho/Wo do not match the forward geometry");

@@ -404,13 +404,11 @@ extern "C" const char *somi_conv2d_wgrad_kernel_name(const somi_conv_desc *fwd) 
 extern "C" int somi_conv2d_wgrad_nhwc_f32(const somi_conv_desc *fwd, const float *x, int x_cs, int x_coff, const float *dy, int dy_cs,
                                           int dy_coff, float *dw, const float *accumulate, void *workspace, size_t workspace_bytes,
                                           somi_stream_t stream) {
-    SOMI_REQUIRE(fwd && x && dy && dw && workspace, SOMI_EINVAL, "conv wgrad: null argument");
+    SOMI_REQUIRE(fwd && dw && aligned16(dw) && workspace, SOMI_EINVAL, "conv wgrad: needs the descriptor, a 16 B aligned dw and the workspace");
     WgradArgs a{};
     int rc = plan(*fwd, a);
     if (rc) return rc;
-    SOMI_REQUIRE(x_cs % 4 == 0 && x_coff % 4 == 0 && dy_cs % 4 == 0 && dy_coff % 4 == 0 && aligned16(x) && aligned16(dy) && aligned16(dw),
-                 SOMI_EINVAL, "conv wgrad: strides / offsets must be multiples of 4 and bases 16 B aligned");
-    SOMI_REQUIRE(x_coff + a.Cin <= x_cs && dy_coff + a.Cout <= dy_cs, SOMI_EINVAL, "conv wgrad: channel slice out of range");
+    SOMI_REQUIRE_SLICES("conv wgrad", {"x", x, x_cs, x_coff, a.Cin}, {"dy", dy, dy_cs, dy_coff, a.Cout});
     SOMI_REQUIRE(workspace_bytes >= somi_conv2d_wgrad_workspace_bytes(fwd), SOMI_EWORKSPACE, "conv wgrad: workspace too small");
     const size_t xb = (size_t)a.B * a.H * a.W * x_cs * 4, yb = (size_t)a.B * a.Ho * a.Wo * dy_cs * 4;
     if (xb > W_MAX_BUF || yb > W_MAX_BUF) {

@@ -317,9 +317,6 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_wgrad_fold_kernel(const floa
         else hipLaunchKernelGGL((KERNEL<5, 2, false>), GRID, dim3(GC_THREADS), 0, STREAM, ARGS);                            \
     } while (0)
 
-static inline int r4(int c) { return (c + 3) / 4 * 4; }
-static inline bool sl_ok(const void *p, int cs, int coff) { return p && cs % 4 == 0 && coff % 4 == 0 && coff >= 0 && aligned16(p); }
-
 static int check_geometry(int C1, int C2, int groups, int k, int stride) {
     SOMI_REQUIRE(k == 1 || k == 3 || k == 5, SOMI_ENOTIMPL, "grouped conv: kernel size %d (1, 3 or 5 only)", k);
     SOMI_REQUIRE(stride == 1 || stride == 2, SOMI_ENOTIMPL, "grouped conv: stride %d (1 or 2 only)", stride);
@@ -343,10 +340,9 @@ extern "C" int somi_gconv2d_nhwc_f32(const float *x, int x_cs, int x_coff, int B
                                      int groups, int k, int stride, float *y, int y_cs, int y_coff, int C2, int Cw, int act, const float *residual,
                                      int res_cs, int res_coff, float *stat_sum, float *stat_sumsq, const float *stat_pivot, somi_stream_t stream) {
     if (int rc = check_geometry(C1, C2, groups, k, stride)) return rc;
-    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && sl_ok(x, x_cs, x_coff) && x_coff + r4(C1) <= x_cs && sl_ok(y, y_cs, y_coff) && Cw % 4 == 0 &&
-                     Cw >= C2 && y_coff + Cw <= y_cs && w && aligned16(w) && w_cs % 4 == 0 && w_cs >= Cw && (!bias || aligned16(bias)),
-                 SOMI_EINVAL, "grouped conv: bad tensors or channel slices");
-    SOMI_REQUIRE(!residual || (sl_ok(residual, res_cs, res_coff) && res_coff + Cw <= res_cs), SOMI_EINVAL, "grouped conv: bad residual slice");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && Cw % 4 == 0 && Cw >= C2 && (!bias || aligned16(bias)), SOMI_EINVAL, "grouped conv: bad sizes or bias");
+    SOMI_REQUIRE(w && aligned16(w) && w_cs % 4 == 0 && w_cs >= Cw, SOMI_EINVAL, "grouped conv: w must be 16 B aligned, its row stride w_cs (%d) a multiple of 4 >= Cw (%d)", w_cs, Cw);
+    SOMI_REQUIRE_SLICES("grouped conv", {"x", x, x_cs, x_coff, r4(C1)}, {"y", y, y_cs, y_coff, Cw}, {"residual", residual, res_cs, res_coff, Cw, kOptional});
     SOMI_REQUIRE(act >= 0 && act <= 4, SOMI_EINVAL, "grouped conv: bad activation");
     SOMI_REQUIRE(!stat_sum == !stat_sumsq && (!stat_sum || (aligned16(stat_sum) && aligned16(stat_sumsq))) && (!stat_pivot || aligned16(stat_pivot)),
                  SOMI_EINVAL, "grouped conv: bad statistics buffers");
@@ -369,12 +365,11 @@ extern "C" int somi_gconv2d_dgrad_nhwc_f32(const float *dy, int dy_cs, int dy_co
     const int P = k / 2;
     SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && Ho == (H + 2 * P - k) / stride + 1 && Wo == (W + 2 * P - k) / stride + 1, SOMI_EINVAL,
                  "grouped conv dgrad: output size does not match the input size");
-    SOMI_REQUIRE(sl_ok(dy, dy_cs, dy_coff) && dy_coff + r4(C2) <= dy_cs && sl_ok(dx, dx_cs, dx_coff) && Cx % 4 == 0 && Cx >= C1 &&
-                     dx_coff + Cx <= dx_cs && w && aligned16(w) && w_cs % 4 == 0 && w_cs >= r4(C2),
-                 SOMI_EINVAL, "grouped conv dgrad: bad tensors or channel slices");
-    SOMI_REQUIRE((!acc1 || (sl_ok(acc1, acc1_cs, acc1_coff) && acc1_coff + Cx <= acc1_cs)) &&
-                     (!acc2 || (sl_ok(acc2, acc2_cs, acc2_coff) && acc2_coff + Cx <= acc2_cs)),
-                 SOMI_EINVAL, "grouped conv dgrad: bad accumulated slices");
+    SOMI_REQUIRE(Cx % 4 == 0 && Cx >= C1, SOMI_EINVAL, "grouped conv dgrad: Cx is C1 rounded up to a multiple of 4, or more");
+    SOMI_REQUIRE(w && aligned16(w) && w_cs % 4 == 0 && w_cs >= r4(C2), SOMI_EINVAL,
+                 "grouped conv dgrad: w must be 16 B aligned, its row stride w_cs (%d) a multiple of 4 >= C2 (%d) rounded up to 4", w_cs, C2);
+    SOMI_REQUIRE_SLICES("grouped conv dgrad", {"dy", dy, dy_cs, dy_coff, r4(C2)}, {"dx", dx, dx_cs, dx_coff, Cx},
+                        {"acc1", acc1, acc1_cs, acc1_coff, Cx, kOptional}, {"acc2", acc2, acc2_cs, acc2_coff, Cx, kOptional});
     DgradArgs a;
     a.dy = dy; a.w = w; a.acc1 = acc1; a.acc2 = acc2; a.dx = dx;
     a.dy_cs = dy_cs; a.dy_coff = dy_coff; a.B = B; a.Ho = Ho; a.Wo = Wo; a.C2 = C2; a.w_cs = w_cs; a.dx_cs = dx_cs; a.dx_coff = dx_coff; a.H = H;
@@ -400,8 +395,8 @@ extern "C" int somi_gconv2d_wgrad_nhwc_f32(const float *x, int x_cs, int x_coff,
     const int P = k / 2;
     SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && Ho == (H + 2 * P - k) / stride + 1 && Wo == (W + 2 * P - k) / stride + 1, SOMI_EINVAL,
                  "grouped conv wgrad: output size does not match the input size");
-    SOMI_REQUIRE(sl_ok(x, x_cs, x_coff) && x_coff + r4(C1) <= x_cs && sl_ok(dy, dy_cs, dy_coff) && dy_coff + r4(C2) <= dy_cs && dw && workspace &&
-                     aligned16(workspace), SOMI_EINVAL, "grouped conv wgrad: bad tensors or channel slices");
+    SOMI_REQUIRE_SLICES("grouped conv wgrad", {"x", x, x_cs, x_coff, r4(C1)}, {"dy", dy, dy_cs, dy_coff, r4(C2)});
+    SOMI_REQUIRE(dw && workspace && aligned16(workspace), SOMI_EINVAL, "grouped conv wgrad: dw and a 16-byte aligned workspace are needed");
     const int cin_g = C1 / groups;
     SOMI_REQUIRE(workspace_floats >= somi_gconv2d_wgrad_workspace_floats(B, Ho, Wo, C2, cin_g, k), SOMI_EWORKSPACE,
                  "grouped conv wgrad: workspace too small");

@@ -836,9 +836,8 @@ extern "C" int somi_dwconv3x3_ln_nhwc_f32(const float *x, const float *w, const 
 }
 
 extern "C" int somi_sppf_pool_nhwc_f32(float *buf, int B, int H, int W, int C, int cs, int x_coff, somi_stream_t stream) {
-    SOMI_REQUIRE(buf && B > 0 && H > 0 && W > 0 && C > 0, SOMI_EINVAL, "sppf: bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && cs % 4 == 0 && x_coff % 4 == 0 && x_coff + 4 * C <= cs && aligned16(buf), SOMI_EINVAL,
-                 "sppf: needs C,cs,x_coff %% 4 == 0 and room for 4*C channels");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, SOMI_EINVAL, "sppf: bad sizes (C a multiple of 4)");
+    SOMI_REQUIRE_SLICES("sppf", {"buf", buf, cs, x_coff, 4 * C});
     hipLaunchKernelGGL(sppf_pool_kernel, dim3(ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream, buf, B,
                        H, W, C, cs, x_coff);
     return launch_status("somi_sppf_pool_nhwc_f32");
@@ -868,9 +867,9 @@ extern "C" int somi_pool_nchunk(int HW) { return (HW + POOL_CHUNK - 1) / POOL_CH
 
 extern "C" int somi_global_pool_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int HW, int C, float *out_avg,
                                          float *out_max, float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE(x && out_avg && workspace && B > 0 && HW > 0 && C > 0, SOMI_EINVAL, "global pool: bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && x_cs % 4 == 0 && x_coff % 4 == 0 && x_coff + C <= x_cs && aligned16(x) && aligned16(workspace),
-                 SOMI_EINVAL, "global pool: C,x_cs,x_coff %% 4 and alignment");
+    SOMI_REQUIRE(out_avg && workspace && aligned16(workspace) && B > 0 && HW > 0 && C % 4 == 0, SOMI_EINVAL,
+                 "global pool: bad arguments (C a multiple of 4, workspace 16-byte aligned)");
+    SOMI_REQUIRE_SLICES("global pool", {"x", x, x_cs, x_coff, C});
     const int nchunk = somi_pool_nchunk(HW);
     float *ps = workspace, *pm = workspace + (size_t)B * nchunk * C;
     hipLaunchKernelGGL(global_pool_stage1<false>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_coff, HW, C, ps, pm, nchunk, 0);
@@ -881,10 +880,9 @@ extern "C" int somi_global_pool_nhwc_f32(const float *x, int x_cs, int x_coff, i
 
 extern "C" int somi_global_pool_act_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int HW, int C, int act, const float *post_scale,
                                              const float *post_shift, float *out_avg, float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE(x && out_avg && workspace && B > 0 && HW > 0 && C > 0 && !post_scale == !post_shift && act >= 0 && act <= SOMI_ACT_SIGMOID,
-                 SOMI_EINVAL, "global pool (act): bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && x_cs % 4 == 0 && x_coff % 4 == 0 && x_coff + C <= x_cs && aligned16(x) && aligned16(workspace),
-                 SOMI_EINVAL, "global pool (act): C,x_cs,x_coff %% 4 and alignment");
+    SOMI_REQUIRE(out_avg && workspace && aligned16(workspace) && B > 0 && HW > 0 && C % 4 == 0 && !post_scale == !post_shift && act >= 0 &&
+                     act <= SOMI_ACT_SIGMOID, SOMI_EINVAL, "global pool (act): bad arguments (C a multiple of 4, workspace 16-byte aligned)");
+    SOMI_REQUIRE_SLICES("global pool (act)", {"x", x, x_cs, x_coff, C});
     const int nchunk = somi_pool_nchunk(HW);
     float *ps = workspace, *pm = workspace + (size_t)B * nchunk * C;
     hipLaunchKernelGGL(global_pool_stage1<true>, dim3(nchunk, B), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_coff, HW, C, ps, pm, nchunk, act);
@@ -914,11 +912,10 @@ extern "C" int somi_affine_silu_pool_nhwc_f32(const float *x, int x_cs, int x_co
                                               somi_stream_t stream) {
     int rows = 0;
     const int gx = asp_grid(B, HW, C, &rows);
-    SOMI_REQUIRE(x && z && scale && shift && out_avg && out_max && workspace && B > 0 && B <= 65535 && HW > 0 && gx > 0, SOMI_EINVAL,
+    SOMI_REQUIRE(scale && shift && out_avg && out_max && workspace && B > 0 && B <= 65535 && HW > 0 && gx > 0, SOMI_EINVAL,
                  "affine + silu + pool: bad arguments (C / 4 must divide 256 or be a multiple of it)");
-    SOMI_REQUIRE(x_cs % 4 == 0 && x_coff % 4 == 0 && z_cs % 4 == 0 && z_coff % 4 == 0 && x_coff + C <= x_cs && z_coff + C <= z_cs && aligned16(x) &&
-                     aligned16(z) && aligned16(scale) && aligned16(shift) && aligned16(workspace), SOMI_EINVAL,
-                 "affine + silu + pool: strides / offsets %% 4 and 16 B alignment");
+    SOMI_REQUIRE(aligned16(scale) && aligned16(shift) && aligned16(workspace), SOMI_EINVAL, "affine + silu + pool: scale, shift, workspace 16 B aligned");
+    SOMI_REQUIRE_SLICES("affine + silu + pool", {"x", x, x_cs, x_coff, C}, {"z", z, z_cs, z_coff, C});
     float *ps = workspace, *pm = workspace + (size_t)B * rows * C;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(affine_silu_pool_kernel, dim3(gx, B), dim3(256), 0, s, x, x_cs, x_coff, scale, shift, z, z_cs, z_coff, HW, C, ps, pm, rows);
@@ -938,9 +935,8 @@ extern "C" int somi_attn_mlp_f32(int mode, const float *avg, const float *mx, co
 
 extern "C" int somi_chan_stats_nhwc_f32(const float *x, int x_cs, int x_coff, const float *ca, float *stats, int B, int HW,
                                         int C, somi_stream_t stream) {
-    SOMI_REQUIRE(x && ca && stats && B > 0 && HW > 0 && C > 0, SOMI_EINVAL, "chan stats: bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && x_cs % 4 == 0 && x_coff % 4 == 0 && aligned16(x) && aligned16(ca), SOMI_EINVAL,
-                 "chan stats: C,x_cs,x_coff %% 4 and alignment");
+    SOMI_REQUIRE(ca && aligned16(ca) && stats && B > 0 && HW > 0 && C % 4 == 0, SOMI_EINVAL, "chan stats: bad arguments (C a multiple of 4, ca 16-byte aligned)");
+    SOMI_REQUIRE_SLICES("chan stats", {"x", x, x_cs, x_coff, C});
     hipLaunchKernelGGL(chan_stats_kernel, dim3(ew_grid((long)B * HW * 64)), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_coff, ca,
                        stats, B, HW, C);
     return launch_status("somi_chan_stats_nhwc_f32");
@@ -958,10 +954,9 @@ extern "C" int somi_spatial_attn_f32(const float *stats, const float *w, const f
 extern "C" int somi_cbam_apply_nhwc_f32(const float *x, int x_cs, int x_coff, const float *ca, const float *stats, const float *w,
                                         const float *bias, float *y, int y_cs, int y_coff, int B, int H, int W, int C, int k,
                                         somi_stream_t stream) {
-    SOMI_REQUIRE(x && ca && stats && w && bias && y && B > 0 && H > 0 && W > 0 && C > 0 && (k == 3 || k == 5 || k == 7), SOMI_EINVAL,
-                 "cbam apply: bad arguments (k in 3,5,7)");
-    SOMI_REQUIRE(C % 4 == 0 && x_cs % 4 == 0 && x_coff % 4 == 0 && y_cs % 4 == 0 && y_coff % 4 == 0 && aligned16(x) && aligned16(y) &&
-                     aligned16(ca), SOMI_EINVAL, "cbam apply: C, strides, offsets %% 4 and 16 B alignment");
+    SOMI_REQUIRE(ca && aligned16(ca) && stats && w && bias && B > 0 && H > 0 && W > 0 && C % 4 == 0 && (k == 3 || k == 5 || k == 7), SOMI_EINVAL,
+                 "cbam apply: bad arguments (C a multiple of 4, ca 16-byte aligned, k in 3,5,7)");
+    SOMI_REQUIRE_SLICES("cbam apply", {"x", x, x_cs, x_coff, C}, {"y", y, y_cs, y_coff, C});
     const long tiles = ((long)B * H * W + 63) / 64;
     hipLaunchKernelGGL(cbam_apply_kernel, dim3((unsigned)(tiles > 256L * 16 ? 256L * 16 : tiles)), dim3(256), 0, (hipStream_t)stream, x,
                        x_cs, x_coff, ca, stats, w, bias, y, y_cs, y_coff, B, H, W, C, k);

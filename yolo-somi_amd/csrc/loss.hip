@@ -642,8 +642,6 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const LossArgs a, floa
     }
 }
 
-static size_t align_up(size_t v, size_t al) { return (v + al - 1) / al * al; }
-
 static int plan(const somi_loss_desc &pd, const somi_loss_level *l5, LossArgs &a) {
     SOMI_REQUIRE(pd.nl >= 1 && pd.nl <= (l5 ? MAXL : 4) && (!l5 || pd.nl == MAXL) && pd.na >= 1 && pd.nc >= 1 && pd.B >= 1 && pd.nt >= 0, SOMI_EINVAL,
                  "loss: bad sizes (1 to 4 levels in the descriptor; a fifth through somi_yolo_loss5_f32 with nl = 5)");

@@ -825,8 +825,6 @@ __global__ void nms_boxes_prep_kernel(const NmsArgs a, uint32_t *sortV, int iden
     a.valA[i] = (uint32_t)i;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace somi
 
 using namespace somi;

@@ -226,12 +226,11 @@ static bool pool2_shape(int H, int W, int stride, int pl, int pr, int pt, int pb
 extern "C" int somi_maxpool2_nhwc_f32(const float *x, float *y, void *codes, int B, int H, int W, int C, int x_cs, int x_coff, int y_cs, int y_coff,
                                       int stride, int pad_l, int pad_r, int pad_t, int pad_b, somi_stream_t stream) {
     int Ho = 0, Wo = 0;
-    SOMI_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0, SOMI_EINVAL, "maxpool2: bad arguments");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C % 4 == 0 && (!codes || aligned16(codes)), SOMI_EINVAL,
+                 "maxpool2: bad sizes (C a multiple of 4), or codes not 16-byte aligned");
     SOMI_REQUIRE(pool2_shape(H, W, stride, pad_l, pad_r, pad_t, pad_b, Ho, Wo), SOMI_EINVAL,
                  "maxpool2: kernel 2 with stride 1 or 2 and a zero pad of 0 or 1 per side only, and the padded map must hold one window");
-    SOMI_REQUIRE(C % 4 == 0 && x_cs % 4 == 0 && x_coff % 4 == 0 && y_cs % 4 == 0 && y_coff % 4 == 0 && x_coff >= 0 && y_coff >= 0 &&
-                     x_coff + C <= x_cs && y_coff + C <= y_cs && aligned16(x) && aligned16(y) && (!codes || aligned16(codes)),
-                 SOMI_EINVAL, "maxpool2: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE_SLICES("maxpool2", {"x", x, x_cs, x_coff, C}, {"y", y, y_cs, y_coff, C});
     const long items = (long)B * Ho * Wo * (C / 4);
     if (small_index(items))
         hipLaunchKernelGGL(maxpool2_fwd_kernel<uint32_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, x, y, (uint8_t *)codes, B, H, W, Ho,
@@ -245,12 +244,11 @@ extern "C" int somi_maxpool2_nhwc_f32(const float *x, float *y, void *codes, int
 extern "C" int somi_maxpool2_bwd_nhwc_f32(const float *dy, const void *codes, float *dx, int B, int H, int W, int C, int dy_cs, int dy_coff, int dx_cs,
                                           int dx_coff, int stride, int pad_l, int pad_r, int pad_t, int pad_b, somi_stream_t stream) {
     int Ho = 0, Wo = 0;
-    SOMI_REQUIRE(dy && codes && dx && B > 0 && H > 0 && W > 0 && C > 0, SOMI_EINVAL, "maxpool2 bwd: bad arguments");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C % 4 == 0 && codes && aligned16(codes), SOMI_EINVAL,
+                 "maxpool2 bwd: bad sizes (C a multiple of 4), or no 16-byte aligned codes");
     SOMI_REQUIRE(pool2_shape(H, W, stride, pad_l, pad_r, pad_t, pad_b, Ho, Wo), SOMI_EINVAL,
                  "maxpool2 bwd: kernel 2 with stride 1 or 2 and a zero pad of 0 or 1 per side only, and the padded map must hold one window");
-    SOMI_REQUIRE(C % 4 == 0 && dy_cs % 4 == 0 && dy_coff % 4 == 0 && dx_cs % 4 == 0 && dx_coff % 4 == 0 && dy_coff >= 0 && dx_coff >= 0 &&
-                     dy_coff + C <= dy_cs && dx_coff + C <= dx_cs && aligned16(dy) && aligned16(dx) && aligned16(codes),
-                 SOMI_EINVAL, "maxpool2 bwd: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE_SLICES("maxpool2 bwd", {"dy", dy, dy_cs, dy_coff, C}, {"dx", dx, dx_cs, dx_coff, C});
     const long items = (long)B * H * W * (C / 4);
     if (small_index(items))
         hipLaunchKernelGGL(maxpool2_bwd_kernel<uint32_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, dy, (const uint8_t *)codes, dx, B, H,
@@ -264,11 +262,10 @@ extern "C" int somi_maxpool2_bwd_nhwc_f32(const float *dy, const void *codes, fl
 extern "C" int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
                                       somi_stream_t stream) {
     SppK kk;
-    SOMI_REQUIRE(buf && B > 0 && H > 0 && W > 0 && C > 0, SOMI_EINVAL, "spp pool: bad arguments");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (!codes || aligned16(codes)), SOMI_EINVAL,
+                 "spp pool: bad sizes (C a multiple of 4), or codes not 16-byte aligned");
     SOMI_REQUIRE(spp_windows_ok(nk, k0, k1, k2, kk), SOMI_EINVAL, "spp pool: 1 to 3 ascending odd window sizes, each 3 <= k <= 13");
-    SOMI_REQUIRE(C % 4 == 0 && cs % 4 == 0 && x_coff % 4 == 0 && x_coff >= 0 && x_coff + (nk + 1) * C <= cs && aligned16(buf) &&
-                     (!codes || aligned16(codes)),
-                 SOMI_EINVAL, "spp pool: needs C, cs, x_coff %% 4 == 0, room for (nk + 1) * C channels and 16-byte aligned tensors");
+    SOMI_REQUIRE_SLICES("spp pool", {"buf", buf, cs, x_coff, (nk + 1) * C});
     const dim3 grid(pool_grid((long)B * H * W * (C / 4)));
     hipStream_t s = (hipStream_t)stream;
 #define SOMI_SPP_FWD(NK, IDX) hipLaunchKernelGGL((spp_pool_fwd_kernel<NK, IDX>), grid, dim3(256), 0, s, buf, (uint8_t *)codes, B, H, W, C, cs, x_coff, kk)
@@ -284,10 +281,10 @@ extern "C" int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int
 extern "C" int somi_spp_pool_bwd_nhwc_f32(const void *codes, float *dbuf, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,
                                           somi_stream_t stream) {
     SppK kk;
-    SOMI_REQUIRE(codes && dbuf && B > 0 && H > 0 && W > 0 && C > 0, SOMI_EINVAL, "spp pool bwd: bad arguments");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && codes && aligned16(codes), SOMI_EINVAL,
+                 "spp pool bwd: bad sizes (C a multiple of 4), or no 16-byte aligned codes");
     SOMI_REQUIRE(spp_windows_ok(nk, k0, k1, k2, kk), SOMI_EINVAL, "spp pool bwd: 1 to 3 ascending odd window sizes, each 3 <= k <= 13");
-    SOMI_REQUIRE(C % 4 == 0 && cs % 4 == 0 && x_coff % 4 == 0 && x_coff >= 0 && x_coff + (nk + 1) * C <= cs && aligned16(dbuf) && aligned16(codes),
-                 SOMI_EINVAL, "spp pool bwd: needs C, cs, x_coff %% 4 == 0, room for (nk + 1) * C channels and 16-byte aligned tensors");
+    SOMI_REQUIRE_SLICES("spp pool bwd", {"dbuf", dbuf, cs, x_coff, (nk + 1) * C});
     const dim3 grid(pool_grid((long)B * H * W * (C / 4)));
     hipStream_t s = (hipStream_t)stream;
 #define SOMI_SPP_BWD(NK, IDX) hipLaunchKernelGGL((spp_pool_bwd_kernel<NK, IDX>), grid, dim3(256), 0, s, (const uint8_t *)codes, dbuf, B, H, W, C, cs, x_coff, kk)

@@ -17,9 +17,6 @@ static inline int ew_grid(long items) {
     long g = (items + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
-static inline bool slice_ok(const void *p, int cs, int coff, int C) {
-    return p && cs % 4 == 0 && coff % 4 == 0 && C % 4 == 0 && coff + C <= cs && aligned16(p);
-}
 
 // dst[b, h, w, dst_coff + c] = src[b, h >> up, w >> up, src_coff + c]   (dst is (B, Hs << up, Ws << up, dst_cs))
 __global__ __launch_bounds__(256) void resample_copy_kernel(const float *__restrict__ src, int src_cs, int src_coff, float *__restrict__ dst,
@@ -196,9 +193,8 @@ extern "C" int somi_tta_descale_f32(float *z, long rows, int no, float scale, in
 
 extern "C" int somi_resample_slice_nhwc_f32(const float *src, int src_cs, int src_coff, float *dst, int dst_cs, int dst_coff, int B, int Hs,
                                             int Ws, int C, int up, int reduce, int accumulate, somi_stream_t stream) {
-    SOMI_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && C > 0 && up >= 0 && up <= 3, SOMI_EINVAL, "resample slice: bad sizes (up <= 3)");
-    SOMI_REQUIRE(slice_ok(src, src_cs, src_coff, C) && slice_ok(dst, dst_cs, dst_coff, C), SOMI_EINVAL,
-                 "resample slice: channel slices have to be 16-byte aligned multiples of 4");
+    SOMI_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && C > 0 && C % 4 == 0 && up >= 0 && up <= 3, SOMI_EINVAL, "resample slice: bad sizes (C a multiple of 4, up <= 3)");
+    SOMI_REQUIRE_SLICES("resample slice", {"src", src, src_cs, src_coff, C}, {"dst", dst, dst_cs, dst_coff, C});
     hipStream_t s = (hipStream_t)stream;
     if (!reduce) {      // src (B,Hs,Ws,.) -> dst (B,Hs<<up,Ws<<up,.)
         SOMI_REQUIRE(!accumulate, SOMI_EINVAL, "resample slice: accumulate is for the reducing direction only");
@@ -213,13 +209,12 @@ extern "C" int somi_resample_slice_nhwc_f32(const float *src, int src_cs, int sr
 
 extern "C" int somi_space_to_depth_nhwc_f32(const float *x, int x_cs, int x_coff, float *y, int y_cs, int y_coff, int B, int Ho, int Wo, int C,
                                             int inverse, somi_stream_t stream) {
-    SOMI_REQUIRE(x && y && B > 0 && Ho > 0 && Wo > 0 && C > 0, SOMI_EINVAL, "space to depth: bad arguments");
+    SOMI_REQUIRE(B > 0 && Ho > 0 && Wo > 0 && C > 0, SOMI_EINVAL, "space to depth: bad arguments");
+    SOMI_REQUIRE_SLICES("space to depth", {"x", x, x_cs, x_coff, inverse ? 4 * C : C}, {"y", y, y_cs, y_coff, inverse ? C : 4 * C});
     if (!inverse) {     // x (B,2Ho,2Wo,x_cs) -> y (B,Ho,Wo,y_cs)
-        SOMI_REQUIRE(x_coff + C <= x_cs && y_coff + 4 * C <= y_cs, SOMI_EINVAL, "space to depth: slices out of range");
         hipLaunchKernelGGL(space_to_depth_kernel, dim3(ew_grid((long)B * Ho * Wo * 4 * C)), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_coff, y, y_cs,
                            y_coff, B, Ho, Wo, C, 0);
     } else {            // x = deep-layout gradient (B,Ho,Wo,x_cs) -> y = image-layout gradient (B,2Ho,2Wo,y_cs): every element written once
-        SOMI_REQUIRE(x_coff + 4 * C <= x_cs && y_coff + C <= y_cs, SOMI_EINVAL, "space to depth: slices out of range");
         hipLaunchKernelGGL(space_to_depth_kernel, dim3(ew_grid((long)B * Ho * Wo * 4 * C)), dim3(256), 0, (hipStream_t)stream, x, y_cs, y_coff, y, x_cs,
                            x_coff, B, Ho, Wo, C, 1);
     }

@@ -457,8 +457,6 @@ static inline int img_grid_c(int B, int HW, int C, int cap) {
     return (int)((g + mult - 1) / mult * mult);
 }
 
-static inline bool sl_ok(const void *p, int cs, int coff, int C) { return p && cs % 4 == 0 && coff % 4 == 0 && coff + C <= cs && aligned16(p); }
-
 }  // namespace somi
 
 using namespace somi;
@@ -468,8 +466,9 @@ extern "C" int somi_img_nchunk(int HW) { return (HW + IMG_CHUNK - 1) / IMG_CHUNK
 extern "C" int somi_cbam_bwd_pixel_argmax_f32(const float *dt2, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
                                               const float *sa, const float *t_max, float *dlogit, int32_t *amaxc, int32_t *amaxp, int B, int HW,
                                               int C, somi_stream_t stream) {
-    SOMI_REQUIRE(sl_ok(dt2, d_cs, d_coff, C) && sl_ok(t, t_cs, t_coff, C) && ca && sa && dlogit && amaxc && t_max && amaxp && B > 0 && HW > 0 &&
-                     C % 4 == 0 && aligned16(ca) && aligned16(t_max), SOMI_EINVAL, "cbam bwd pixel + argmax: bad arguments");
+    SOMI_REQUIRE_SLICES("cbam bwd pixel + argmax", {"dt2", dt2, d_cs, d_coff, C}, {"t", t, t_cs, t_coff, C});
+    SOMI_REQUIRE(ca && sa && dlogit && amaxc && t_max && amaxp && B > 0 && HW > 0 && C % 4 == 0 && aligned16(ca) && aligned16(t_max), SOMI_EINVAL,
+                 "cbam bwd pixel + argmax: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(amaxp, 0x7f, (size_t)B * C * sizeof(int32_t), s);          // 0x7f7f7f7f: above every pixel index, the integer min's identity here
     hipLaunchKernelGGL(cbam_bwd_pixel_kernel, dim3(ew_grid((long)B * HW * 64)), dim3(256), 0, s, dt2, d_cs, d_coff, t, t_cs, t_coff, ca, sa, dlogit,
@@ -504,8 +503,9 @@ extern "C" int somi_spatial_attn_bwd_f32(const float *dlogit, const float *stats
 extern "C" int somi_cbam_bwd_chan_f32(float *dt2_inout, int d_cs, int d_coff, const float *t, int t_cs, int t_coff, const float *ca,
                                       const float *sa, const float *dstats, const int32_t *amaxc, float *dca, float *workspace, int B, int HW,
                                       int C, somi_stream_t stream) {
-    SOMI_REQUIRE(sl_ok(dt2_inout, d_cs, d_coff, C) && sl_ok(t, t_cs, t_coff, C) && ca && sa && dstats && amaxc && dca && workspace && B > 0 &&
-                     HW > 0 && C % 4 == 0 && aligned16(ca) && aligned16(workspace), SOMI_EINVAL, "cbam bwd chan: bad arguments");
+    SOMI_REQUIRE_SLICES("cbam bwd chan", {"dt2_inout", dt2_inout, d_cs, d_coff, C}, {"t", t, t_cs, t_coff, C});
+    SOMI_REQUIRE(ca && sa && dstats && amaxc && dca && workspace && B > 0 && HW > 0 && C % 4 == 0 && aligned16(ca) && aligned16(workspace), SOMI_EINVAL,
+                 "cbam bwd chan: bad arguments");
     const int nchunk = somi_img_nchunk(HW);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cbam_bwd_chan_kernel, dim3(nchunk, B), dim3(256), 0, s, dt2_inout, d_cs, d_coff, t, t_cs, t_coff, ca, sa, dstats, amaxc,
@@ -532,8 +532,8 @@ extern "C" int somi_attn_mlp_bwd_f32(int mode, const float *dout, const float *o
 
 extern "C" int somi_pool_bwd_add_nhwc_f32(float *dt_inout, int d_cs, int d_coff, const float *davg, const float *dmax, const int32_t *amaxp,
                                           int B, int HW, int C, somi_stream_t stream) {
-    SOMI_REQUIRE(sl_ok(dt_inout, d_cs, d_coff, C) && davg && (!dmax || amaxp) && B > 0 && HW > 0 && C % 4 == 0 && aligned16(davg), SOMI_EINVAL,
-                 "pool bwd add: bad arguments");
+    SOMI_REQUIRE_SLICES("pool bwd add", {"dt_inout", dt_inout, d_cs, d_coff, C});
+    SOMI_REQUIRE(davg && (!dmax || amaxp) && B > 0 && HW > 0 && C % 4 == 0 && aligned16(davg), SOMI_EINVAL, "pool bwd add: bad arguments");
     SOMI_REQUIRE(B <= 65535, SOMI_EINVAL, "pool bwd add: batch beyond the grid's y range");
     hipLaunchKernelGGL(pool_bwd_add_kernel, dim3(img_grid_c(B, HW, C, 7 * 256), B), dim3(256), 0, (hipStream_t)stream, dt_inout, d_cs, d_coff, davg,
                        dmax, amaxp, B, HW, C);
@@ -876,9 +876,9 @@ extern "C" int somi_detect_raw_bwd_f32(const float *draw, float *dbox, int box_c
 
 extern "C" int somi_sppf_pool_bwd_nhwc_f32(const float *buf, float *dbuf, void *workspace, int B, int H, int W, int C, int cs, int x_coff,
                                            somi_stream_t stream) {
-    SOMI_REQUIRE(dbuf && workspace && B > 0 && H > 0 && W > 0 && C > 0 && x_coff + 4 * C <= cs, SOMI_EINVAL, "sppf bwd: bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && cs % 4 == 0 && x_coff % 4 == 0 && aligned16(buf) && aligned16(dbuf) && (reinterpret_cast<uintptr_t>(workspace) & 3u) == 0,
-                 SOMI_EINVAL, "sppf bwd: channels / strides must be multiples of 4, tensors 16-byte aligned");
+    SOMI_REQUIRE(workspace && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, SOMI_EINVAL,
+                 "sppf bwd: bad arguments (C a multiple of 4, the codes 4-byte aligned)");
+    SOMI_REQUIRE_SLICES("sppf bwd", {"dbuf", dbuf, cs, x_coff, 4 * C}, {"buf", buf, cs, x_coff, 4 * C, kOptional});
     hipStream_t s = (hipStream_t)stream;
     uint8_t *arg = static_cast<uint8_t *>(workspace);                    // 3*B*H*W*C bytes
     if (buf)                                                             // buf == NULL: the workspace holds the codes somi_sppf_pool_codes_nhwc_f32 left
@@ -889,9 +889,9 @@ extern "C" int somi_sppf_pool_bwd_nhwc_f32(const float *buf, float *dbuf, void *
 }
 
 extern "C" int somi_sppf_pool_codes_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, somi_stream_t stream) {
-    SOMI_REQUIRE(buf && codes && B > 0 && H > 0 && W > 0 && C > 0 && x_coff + 4 * C <= cs, SOMI_EINVAL, "sppf (codes): bad arguments");
-    SOMI_REQUIRE(C % 4 == 0 && cs % 4 == 0 && x_coff % 4 == 0 && aligned16(buf) && (reinterpret_cast<uintptr_t>(codes) & 3u) == 0, SOMI_EINVAL,
-                 "sppf (codes): channels / strides must be multiples of 4, the tensor 16-byte aligned");
+    SOMI_REQUIRE(codes && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (reinterpret_cast<uintptr_t>(codes) & 3u) == 0, SOMI_EINVAL,
+                 "sppf (codes): bad arguments (C a multiple of 4, the codes 4-byte aligned)");
+    SOMI_REQUIRE_SLICES("sppf (codes)", {"buf", buf, cs, x_coff, 4 * C});
     for (int l = 0; l < 3; ++l)
         hipLaunchKernelGGL(sppf_pool5_codes_kernel, dim3(ew_grid((long)B * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream, buf,
                            static_cast<uint8_t *>(codes), B, H, W, C, cs, x_coff, l);

@@ -823,8 +823,6 @@ static void launch_bwd_apply(const float *dz, int dz_cs, int dz_coff, const floa
                            shift, mean, cA, cB, cC, act, order, dx, dx_cs, dx_coff, npix, C);
 }
 
-static inline bool slice_ok(const void *p, int cs, int coff, int C) { return p && cs % 4 == 0 && coff % 4 == 0 && coff + C <= cs && aligned16(p); }
-
 }  // namespace somi
 
 using namespace somi;
@@ -841,8 +839,8 @@ extern "C" int somi_bn_stats_nhwc_f32(const float *x, int x_cs, int x_coff, long
 extern "C" int somi_bn_stats_act_nhwc_f32(const float *x, int x_cs, int x_coff, int act, long npix, int C, float eps, float momentum,
                                           const float *gamma, const float *beta, float *mean, float *rstd, float *scale, float *shift,
                                           float *running_mean, float *running_var, float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(x, x_cs, x_coff, C) && npix > 0 && C > 0 && C % 4 == 0 && mean && rstd && scale && shift && workspace && act >= 0 &&
-                     act <= 4, SOMI_EINVAL, "bn stats: bad arguments");
+    SOMI_REQUIRE_SLICES("bn stats", {"x", x, x_cs, x_coff, C});
+    SOMI_REQUIRE(npix > 0 && C % 4 == 0 && mean && rstd && scale && shift && workspace && act >= 0 && act <= 4, SOMI_EINVAL, "bn stats: bad arguments");
     SOMI_REQUIRE(!running_mean == !running_var, SOMI_EINVAL, "bn stats: running_mean and running_var go together");
     const int nchunk = somi_red_nchunk(npix);
     float *p1 = workspace, *p2 = workspace + (size_t)nchunk * C;
@@ -879,9 +877,9 @@ extern "C" int somi_bn_stats_partials_f32(const float *part_sum, const float *pa
 extern "C" int somi_chan_affine_act_nhwc_f32(const float *x, int x_cs, int x_coff, const float *scale, const float *shift, int act,
                                              int order, float *z, int z_cs, int z_coff, long npix, int C, const float *residual,
                                              int res_cs, int res_coff, somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(x, x_cs, x_coff, C) && slice_ok(z, z_cs, z_coff, C) && scale && shift && npix > 0 && C % 4 == 0 &&
-                     (order == 0 || order == 1) && aligned16(scale) && aligned16(shift), SOMI_EINVAL, "chan affine act: bad arguments");
-    SOMI_REQUIRE(!residual || slice_ok(residual, res_cs, res_coff, C), SOMI_EINVAL, "chan affine act: bad residual slice");
+    SOMI_REQUIRE_SLICES("chan affine act", {"x", x, x_cs, x_coff, C}, {"z", z, z_cs, z_coff, C}, {"residual", residual, res_cs, res_coff, C, kOptional});
+    SOMI_REQUIRE(scale && shift && npix > 0 && C % 4 == 0 && (order == 0 || order == 1) && aligned16(scale) && aligned16(shift), SOMI_EINVAL,
+                 "chan affine act: bad arguments");
     launch_affine_act(x, x_cs, x_coff, scale, shift, act, order, z, z_cs, z_coff, npix, C, residual, res_cs, res_coff, (hipStream_t)stream);
     return launch_status("somi_chan_affine_act_nhwc_f32");
 }
@@ -890,8 +888,9 @@ extern "C" int somi_bn_act_backward_nhwc_f32(const float *dz, int dz_cs, int dz_
                                              const float *rstd, const float *scale, const float *shift, int act, int order,
                                              int batch_stats, float *dx, int dx_cs, int dx_coff, float *dgamma, float *dbeta, long npix,
                                              int C, float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(dz, dz_cs, dz_coff, C) && slice_ok(x, x_cs, x_coff, C) && slice_ok(dx, dx_cs, dx_coff, C) && mean && rstd && scale &&
-                     shift && workspace && npix > 0 && C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL, "bn act backward: bad arguments");
+    SOMI_REQUIRE_SLICES("bn act backward", {"dz", dz, dz_cs, dz_coff, C}, {"x", x, x_cs, x_coff, C}, {"dx", dx, dx_cs, dx_coff, C});
+    SOMI_REQUIRE(mean && rstd && scale && shift && workspace && npix > 0 && C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL,
+                 "bn act backward: bad arguments");
     const int nchunk = somi_red_nchunk(npix);
     const size_t cpad = ((size_t)C + 3) / 4 * 4;
     float *p1 = workspace, *p2 = p1 + (size_t)nchunk * C, *cA = p2 + (size_t)nchunk * C, *cB = cA + cpad, *cC = cB + cpad;
@@ -913,8 +912,8 @@ extern "C" int somi_bn_act_backward_pooled_nhwc_f32(const float *dz, int dz_cs, 
                                                     const float *rstd, const float *scale, const float *shift, int act, int order,
                                                     const float *davg, const float *dmax, const int32_t *amaxp, float *dx, int dx_cs, int dx_coff,
                                                     float *dgamma, float *dbeta, int B, int HW, int C, float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE((!dz || slice_ok(dz, dz_cs, dz_coff, C)) && slice_ok(x, x_cs, x_coff, C) && slice_ok(dx, dx_cs, dx_coff, C) && mean && rstd && scale &&
-                     shift && workspace && B > 0 && HW > 0 && C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL,
+    SOMI_REQUIRE_SLICES("bn act backward (pooled)", {"dz", dz, dz_cs, dz_coff, C, kOptional}, {"x", x, x_cs, x_coff, C}, {"dx", dx, dx_cs, dx_coff, C});
+    SOMI_REQUIRE(mean && rstd && scale && shift && workspace && B > 0 && HW > 0 && C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL,
                  "bn act backward (pooled): bad arguments");
     SOMI_REQUIRE(davg && !dmax == !amaxp && aligned16(davg) && (!dmax || (aligned16(dmax) && aligned16(amaxp))) && aligned16(mean) && aligned16(scale) &&
                      aligned16(shift),
@@ -942,15 +941,15 @@ extern "C" int somi_bn_act_backward_pooled_nhwc_f32(const float *dz, int dz_cs, 
     return launch_status("somi_bn_act_backward_pooled_nhwc_f32");
 }
 
-static bool cbam_bn_args(CbamBnArgs &a, const float *d, int d_cs, int d_coff, const float *y, int y_cs, int y_coff, const float *scale, const float *shift,
-                         const float *mean, const float *ca, const float *sa, const float *dstats, const int32_t *amaxc, const int32_t *amaxp, int B, int HW,
-                         int C) {
-    if (!(slice_ok(d, d_cs, d_coff, C) && slice_ok(y, y_cs, y_coff, C) && scale && shift && mean && ca && sa && dstats && amaxc && amaxp && B > 0 &&
-          B <= 65535 && HW > 0 && (long)B * HW < (1L << 31) && C % 4 == 0 && aligned16(scale) && aligned16(shift) && aligned16(mean) && aligned16(ca) &&
-          aligned16(amaxp) && ((uintptr_t)dstats & 7) == 0))
-        return false;
+static int cbam_bn_args(const char *who, CbamBnArgs &a, const float *d, int d_cs, int d_coff, const float *y, int y_cs, int y_coff, const float *scale, const float *shift,
+                        const float *mean, const float *ca, const float *sa, const float *dstats, const int32_t *amaxc, const int32_t *amaxp, int B, int HW,
+                        int C) {
+    SOMI_REQUIRE_SLICES(who, {"d", d, d_cs, d_coff, C}, {"y", y, y_cs, y_coff, C});
+    SOMI_REQUIRE(scale && shift && mean && ca && sa && dstats && amaxc && amaxp && B > 0 && B <= 65535 && HW > 0 && (long)B * HW < (1L << 31) &&
+                     C % 4 == 0 && aligned16(scale) && aligned16(shift) && aligned16(mean) && aligned16(ca) && aligned16(amaxp) &&
+                     ((uintptr_t)dstats & 7) == 0, SOMI_EINVAL, "%s: bad arguments", who);
     a = CbamBnArgs{d, d_cs, d_coff, y, y_cs, y_coff, scale, shift, mean, ca, sa, dstats, amaxc, amaxp, HW, C};
-    return true;
+    return 0;
 }
 
 extern "C" size_t somi_cbam_bn_bwd_workspace_floats(int B, int HW, int C) {
@@ -963,8 +962,8 @@ extern "C" int somi_cbam_bn_bwd_reduce_f32(const float *d, int d_cs, int d_coff,
                                            const int32_t *amaxc, const int32_t *amaxp, float *dca, float *workspace, int B, int HW, int C,
                                            somi_stream_t stream) {
     CbamBnArgs a;
-    SOMI_REQUIRE(cbam_bn_args(a, d, d_cs, d_coff, y, y_cs, y_coff, scale, shift, mean, ca, sa, dstats, amaxc, amaxp, B, HW, C) && dca && workspace,
-                 SOMI_EINVAL, "cbam bn bwd reduce: bad arguments");
+    if (int e = cbam_bn_args("cbam bn bwd reduce", a, d, d_cs, d_coff, y, y_cs, y_coff, scale, shift, mean, ca, sa, dstats, amaxc, amaxp, B, HW, C)) return e;
+    SOMI_REQUIRE(dca && workspace, SOMI_EINVAL, "cbam bn bwd reduce: bad arguments");
     const int chunk = red_chunk_img(B, HW), nimg = (HW + chunk - 1) / chunk;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cbam_bn_bwd_reduce_kernel, dim3(nimg, B), dim3(256), 0, s, a, workspace, chunk);
@@ -978,9 +977,9 @@ extern "C" int somi_cbam_bn_bwd_apply_f32(const float *d, int d_cs, int d_coff, 
                                           float *dx, int dx_cs, int dx_coff, float *dgamma, float *dbeta, float *workspace, int B, int HW, int C,
                                           somi_stream_t stream) {
     CbamBnArgs a;
-    SOMI_REQUIRE(cbam_bn_args(a, d, d_cs, d_coff, y, y_cs, y_coff, scale, shift, mean, ca, sa, dstats, amaxc, amaxp, B, HW, C) && rstd && davg && dmax &&
-                     aligned16(davg) && aligned16(dmax) && slice_ok(dx, dx_cs, dx_coff, C) && workspace,
-                 SOMI_EINVAL, "cbam bn bwd apply: bad arguments");
+    if (int e = cbam_bn_args("cbam bn bwd apply", a, d, d_cs, d_coff, y, y_cs, y_coff, scale, shift, mean, ca, sa, dstats, amaxc, amaxp, B, HW, C)) return e;
+    SOMI_REQUIRE_SLICES("cbam bn bwd apply", {"dx", dx, dx_cs, dx_coff, C});
+    SOMI_REQUIRE(rstd && davg && dmax && aligned16(davg) && aligned16(dmax) && workspace, SOMI_EINVAL, "cbam bn bwd apply: bad arguments");
     const int chunk = red_chunk_img(B, HW), nimg = (HW + chunk - 1) / chunk, rows = B * nimg;
     const size_t cpad = ((size_t)C + 3) / 4 * 4;
     float *cA = workspace + (size_t)7 * rows * C, *cB = cA + cpad, *cC = cB + cpad;
@@ -1008,7 +1007,7 @@ extern "C" int somi_bn_local_sums_f64(const float *x, int x_cs, int x_coff, long
             p1 = o1; p2 = o2;
         }
     } else {
-        SOMI_REQUIRE(slice_ok(x, x_cs, x_coff, C), SOMI_EINVAL, "bn local sums: bad slice");
+        SOMI_REQUIRE_SLICES("bn local sums", {"x", x, x_cs, x_coff, C});
         nchunk = somi_red_nchunk(npix);
         float *o1 = workspace, *o2 = workspace + (size_t)nchunk * C;
         hipLaunchKernelGGL(bn_stats_stage1, dim3(nchunk), dim3(256), 0, s, x, x_cs, x_coff, npix, C, pivot, o1, o2, red_chunk(npix), (int)SOMI_ACT_NONE);
@@ -1031,8 +1030,9 @@ extern "C" int somi_bn_stats_from_sums_f64(const double *all_sums, int nranks, i
 extern "C" int somi_bn_act_backward_sums_f64(const float *dz, int dz_cs, int dz_coff, const float *x, int x_cs, int x_coff, const float *mean,
                                              const float *scale, const float *shift, int act, int order, long npix, int C, double *sums,
                                              float *workspace, somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(dz, dz_cs, dz_coff, C) && slice_ok(x, x_cs, x_coff, C) && mean && scale && shift && sums && workspace && npix > 0 &&
-                     C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL, "bn act backward sums: bad arguments");
+    SOMI_REQUIRE_SLICES("bn act backward sums", {"dz", dz, dz_cs, dz_coff, C}, {"x", x, x_cs, x_coff, C});
+    SOMI_REQUIRE(mean && scale && shift && sums && workspace && npix > 0 && C % 4 == 0 && (order == 0 || order == 1), SOMI_EINVAL,
+                 "bn act backward sums: bad arguments");
     const int nchunk = somi_red_nchunk(npix);
     float *p1 = workspace, *p2 = p1 + (size_t)nchunk * C;
     hipStream_t s = (hipStream_t)stream;
@@ -1046,9 +1046,9 @@ extern "C" int somi_bn_act_backward_apply_sync_f32(const float *dz, int dz_cs, i
                                                    int order, const double *local_sums, const double *all_sums, int nranks, float *dx, int dx_cs,
                                                    int dx_coff, float *dgamma, float *dbeta, long npix, int C, float *workspace,
                                                    somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(dz, dz_cs, dz_coff, C) && slice_ok(x, x_cs, x_coff, C) && slice_ok(dx, dx_cs, dx_coff, C) && mean && rstd && scale &&
-                     shift && local_sums && all_sums && nranks > 0 && workspace && npix > 0 && C % 4 == 0 && (order == 0 || order == 1),
-                 SOMI_EINVAL, "bn act backward apply (sync): bad arguments");
+    SOMI_REQUIRE_SLICES("bn act backward apply (sync)", {"dz", dz, dz_cs, dz_coff, C}, {"x", x, x_cs, x_coff, C}, {"dx", dx, dx_cs, dx_coff, C});
+    SOMI_REQUIRE(mean && rstd && scale && shift && local_sums && all_sums && nranks > 0 && workspace && npix > 0 && C % 4 == 0 &&
+                     (order == 0 || order == 1), SOMI_EINVAL, "bn act backward apply (sync): bad arguments");
     const size_t cpad = ((size_t)C + 3) / 4 * 4;
     float *cA = workspace, *cB = cA + cpad, *cC = cB + cpad;
     hipStream_t s = (hipStream_t)stream;
@@ -1060,7 +1060,8 @@ extern "C" int somi_bn_act_backward_apply_sync_f32(const float *dz, int dz_cs, i
 
 extern "C" int somi_chan_sum_nhwc_f32(const float *x, int x_cs, int x_coff, long npix, int C, float *out_accumulate, float *workspace,
                                       somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(x, x_cs, x_coff, C) && out_accumulate && workspace && npix > 0 && C % 4 == 0, SOMI_EINVAL, "chan sum: bad arguments");
+    SOMI_REQUIRE_SLICES("chan sum", {"x", x, x_cs, x_coff, C});
+    SOMI_REQUIRE(out_accumulate && workspace && npix > 0 && C % 4 == 0, SOMI_EINVAL, "chan sum: bad arguments");
     const int nchunk = somi_red_nchunk(npix);
     float *p1 = workspace, *p2 = workspace + (size_t)nchunk * C;
     hipLaunchKernelGGL(chan_sum_stage1, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_coff, npix, C, p1, p2, red_chunk(npix));
@@ -1070,8 +1071,8 @@ extern "C" int somi_chan_sum_nhwc_f32(const float *x, int x_cs, int x_coff, long
 
 extern "C" int somi_add_nhwc_f32(const float *a, int a_cs, int a_coff, const float *b, int b_cs, int b_coff, float *out, int o_cs,
                                  int o_coff, long npix, int C, somi_stream_t stream) {
-    SOMI_REQUIRE(slice_ok(a, a_cs, a_coff, C) && slice_ok(b, b_cs, b_coff, C) && slice_ok(out, o_cs, o_coff, C) && npix > 0 && C % 4 == 0,
-                 SOMI_EINVAL, "add: bad arguments");
+    SOMI_REQUIRE_SLICES("add", {"a", a, a_cs, a_coff, C}, {"b", b, b_cs, b_coff, C}, {"out", out, o_cs, o_coff, C});
+    SOMI_REQUIRE(npix > 0 && C % 4 == 0, SOMI_EINVAL, "add: bad arguments");
     hipLaunchKernelGGL(add_kernel, dim3(ew_grid_c(npix, C, WG_ADD)), dim3(256), 0, (hipStream_t)stream, a, a_cs, a_coff, b, b_cs, b_coff, out, o_cs,
                        o_coff, npix, C);
     return launch_status("somi_add_nhwc_f32");

@@ -363,18 +363,15 @@ __global__ __launch_bounds__(256) void dysample_bwd_off_kernel(const float *__re
     }
 }
 
-static bool slice_ok(const void *p, int c, int cs, int coff) { return p && aligned16(p) && c > 0 && c % 4 == 0 && cs % 4 == 0 && coff % 4 == 0 && coff >= 0 && coff + c <= cs; }
-
 }  // namespace somi
 
 using namespace somi;
 
 extern "C" int somi_carafe_nhwc_f32(const float *x, const float *logits, float *out, float *weights, int B, int H, int W, int C, int k_up, int x_cs,
                                     int x_coff, int l_cs, int l_coff, int o_cs, int o_coff, somi_stream_t stream) {
-    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && (k_up == 3 || k_up == 5), SOMI_EINVAL, "carafe: bad shape, or k_up not 3 or 5");
-    SOMI_REQUIRE(slice_ok(x, C, x_cs, x_coff) && slice_ok(logits, 4 * k_up * k_up, l_cs, l_coff) && slice_ok(out, C, o_cs, o_coff) &&
-                     (!weights || aligned16(weights)),
-                 SOMI_EINVAL, "carafe: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C % 4 == 0 && (k_up == 3 || k_up == 5) && (!weights || aligned16(weights)), SOMI_EINVAL,
+                 "carafe: bad shape, C not a multiple of 4, k_up not 3 or 5, or weights not 16-byte aligned");
+    SOMI_REQUIRE_SLICES("carafe", {"x", x, x_cs, x_coff, C}, {"logits", logits, l_cs, l_coff, 4 * k_up * k_up}, {"out", out, o_cs, o_coff, C});
     const int tH = cdiv(H, kUpTile), tW = cdiv(W, kUpTile);
     SOMI_REQUIRE((long)B * tH * tW < (1L << 31), SOMI_EINVAL, "carafe: too many tiles for one launch");
     const dim3 grid((unsigned)((long)B * tH * tW));
@@ -390,10 +387,10 @@ extern "C" int somi_carafe_nhwc_f32(const float *x, const float *logits, float *
 extern "C" int somi_carafe_bwd_nhwc_f32(const float *dout, const float *x, const float *weights, float *dx, float *dlogits, int B, int H, int W, int C,
                                         int k_up, int d_cs, int d_coff, int x_cs, int x_coff, int dx_cs, int dx_coff, int dl_cs, int dl_coff,
                                         somi_stream_t stream) {
-    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && (k_up == 3 || k_up == 5), SOMI_EINVAL, "carafe bwd: bad shape, or k_up not 3 or 5");
-    SOMI_REQUIRE(slice_ok(dout, C, d_cs, d_coff) && slice_ok(x, C, x_cs, x_coff) && slice_ok(dx, C, dx_cs, dx_coff) &&
-                     slice_ok(dlogits, 4 * k_up * k_up, dl_cs, dl_coff) && weights && aligned16(weights),
-                 SOMI_EINVAL, "carafe bwd: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE(B > 0 && H > 0 && W > 0 && C % 4 == 0 && (k_up == 3 || k_up == 5) && weights && aligned16(weights), SOMI_EINVAL,
+                 "carafe bwd: bad shape, C not a multiple of 4, k_up not 3 or 5, or no 16-byte aligned weights");
+    SOMI_REQUIRE_SLICES("carafe bwd", {"dout", dout, d_cs, d_coff, C}, {"x", x, x_cs, x_coff, C}, {"dx", dx, dx_cs, dx_coff, C},
+                        {"dlogits", dlogits, dl_cs, dl_coff, 4 * k_up * k_up});
     const int tH = cdiv(H, kUpTile), tW = cdiv(W, kUpTile);
     SOMI_REQUIRE((long)B * tH * tW < (1L << 31), SOMI_EINVAL, "carafe bwd: too many tiles for one launch");
     const dim3 grid((unsigned)((long)B * tH * tW));
@@ -418,8 +415,8 @@ extern "C" int somi_dysample_nhwc_f32(const float *x, const float *offset, const
                                       int x_cs, int x_coff, int f_cs, int f_coff, int o_cs, int o_coff, somi_stream_t stream) {
     SOMI_REQUIRE(dysample_shape_ok(B, H, W, C, groups), SOMI_EINVAL,
                  "dysample: needs C %% groups == 0, (C / groups) %% 4 == 0 and fewer than 2^32 (pixel, channel quad) items");
-    SOMI_REQUIRE(slice_ok(x, C, x_cs, x_coff) && slice_ok(offset, 8 * groups, f_cs, f_coff) && slice_ok(out, C, o_cs, o_coff) && init_pos, SOMI_EINVAL,
-                 "dysample: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE_SLICES("dysample", {"x", x, x_cs, x_coff, C}, {"offset", offset, f_cs, f_coff, 8 * groups}, {"out", out, o_cs, o_coff, C});
+    SOMI_REQUIRE(init_pos, SOMI_EINVAL, "dysample: init_pos is NULL");
     hipLaunchKernelGGL(dysample_fwd_kernel, dim3(up_grid((long)B * H * W * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, offset, init_pos, out, B, H, W, C,
                        groups, x_cs, x_coff, f_cs, f_coff, o_cs, o_coff);
     return launch_status("somi_dysample_nhwc_f32");
@@ -430,9 +427,9 @@ extern "C" int somi_dysample_bwd_nhwc_f32(const float *dout, const float *x, con
                                           int f_coff, int dx_cs, int dx_coff, int df_cs, int df_coff, somi_stream_t stream) {
     SOMI_REQUIRE(dysample_shape_ok(B, H, W, C, groups), SOMI_EINVAL,
                  "dysample bwd: needs C %% groups == 0, (C / groups) %% 4 == 0 and fewer than 2^32 (pixel, channel quad) items");
-    SOMI_REQUIRE(slice_ok(dout, C, d_cs, d_coff) && slice_ok(x, C, x_cs, x_coff) && slice_ok(offset, 8 * groups, f_cs, f_coff) &&
-                     slice_ok(dx, C, dx_cs, dx_coff) && slice_ok(doffset, 8 * groups, df_cs, df_coff) && init_pos && far_count,
-                 SOMI_EINVAL, "dysample bwd: channels / strides / offsets must be multiples of 4 inside their tensors, tensors 16-byte aligned");
+    SOMI_REQUIRE_SLICES("dysample bwd", {"dout", dout, d_cs, d_coff, C}, {"x", x, x_cs, x_coff, C}, {"offset", offset, f_cs, f_coff, 8 * groups},
+                        {"dx", dx, dx_cs, dx_coff, C}, {"doffset", doffset, df_cs, df_coff, 8 * groups});
+    SOMI_REQUIRE(init_pos && far_count, SOMI_EINVAL, "dysample bwd: init_pos or far_count is NULL");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(dysample_bwd_dx_kernel, dim3(up_grid((long)B * H * W * (C / 4))), dim3(256), 0, s, dout, offset, init_pos, dx, B, H, W, C, groups, d_cs,
                        d_coff, f_cs, f_coff, dx_cs, dx_coff);
