@@ -602,6 +602,35 @@ int somi_psa_attention_backward_f32(const float *qkv, int qkv_cs, int qkv_coff, 
                                     const float *dv_add, float *workspace, somi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Swin window attention (WindowAttention inside SwinTransformerLayer, models/common.py:1184-1358; C3STR :1632-1637).  fp32, window 8 x 8 and
+ * head_dim 32 fixed (scale 32^-0.5): C != heads * 32 is SOMI_ENOTIMPL.  Whole contiguous tensors: qkv and dqkv (B,H,W,3C) as the bias-free qkv
+ * Linear wrote it (channel = which * C + head * 32 + d, which = 0 q / 1 k / 2 v), o and dout (B,H,W,C); 16-byte aligned.
+ * table: the relative_position_bias_table parameter as stored, (225, heads).  shift: 0 or 4.  region_ids: int32 (Wp, Hp) with Wp, Hp = W, H
+ * rounded up to 8 - the reference's img_mask (its frame is transposed: rows run along W), required when shift > 0; scores of token pairs with
+ * different ids get -100.  The cyclic shift, the zero padding to the window grid (padding tokens have q = k = v = 0 and still are keys), the
+ * window partition and the crop are index arithmetic; neither a rolled / padded / partitioned tensor nor a score matrix reaches memory.
+ * Deterministic: fixed-order sums, no float atomics.
+ *
+ * Forward: lse (optional, somi_swin_attention_lse_floats floats) receives each score row's log-sum-exp for the backward.
+ * Backward: dq, dk, dv of every pixel written into dqkv; the table's gradient is ACCUMULATED into dtable_accumulate (225, heads) from
+ * per-workgroup partial sums in workspace (somi_swin_attention_bwd_workspace_floats floats), added in a fixed order. */
+size_t somi_swin_attention_lse_floats(int B, int H, int W, int heads);
+int somi_swin_attention_f32(const float *qkv, const float *table, const int32_t *region_ids, int B, int H, int W, int C, int heads, int shift,
+                            float *o, float *lse, somi_stream_t stream);
+size_t somi_swin_attention_bwd_workspace_floats(int B, int H, int W, int heads);
+int somi_swin_attention_backward_f32(const float *qkv, const float *table, const int32_t *region_ids, const float *dout, const float *lse,
+                                     int B, int H, int W, int C, int heads, int shift, float *dqkv, float *dtable_accumulate,
+                                     float *workspace, somi_stream_t stream);
+/* Backward of a plain LayerNorm over C (no activation behind it: norm1 / norm2 of SwinTransformerLayer), contiguous (npix, C): du from dy,
+ * `add` (optional, (npix, C)) added to du - the gradient of the residual branch around the norm; dgamma / dbeta are ACCUMULATED, in a fixed
+ * order.  workspace: somi_layernorm_bwd_workspace_floats(npix, C) floats.  And the backward of an exact GELU over n = 4k contiguous floats:
+ * du = dy * gelu'(u) (Mlp's activation, :1157; du may alias dy). */
+size_t somi_layernorm_bwd_workspace_floats(long npix, int C);
+int somi_layernorm_bwd_nhwc_f32(const float *u, const float *gamma, float eps, const float *dy, const float *add, float *du,
+                                float *dgamma_accumulate, float *dbeta_accumulate, float *workspace, long npix, int C, somi_stream_t stream);
+int somi_gelu_bwd_f32(const float *u, const float *dy, float *du, long n, somi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stock YOLOv5 module set (north_star "CSP/Darknet backbone, PANet/FPN neck, anchor-based detection head"; BASELINE configs[0]).
  * Bottleneck / C3 / SPP (models/common.py:1494-1509,1541-1565,1806-1826) are compositions of the convolution entry points above
  * (C3's torch.cat never materialises: cv2 and the last bottleneck write the two halves of cv3's input; SPP's parallel 5/9/13

@@ -169,6 +169,13 @@ SIGNATURES = {
     'somi_gconv2d_wgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, P, Z, S]),
     'somi_psa_attention_f32': (I, [P, I, I, I, I, I, P, I, I, P, P, S]),
     'somi_psa_attention_backward_f32': (I, [P, I, I, P, I, I, P, I, I, P, I, I, I, P, I, I, P, P, S]),
+    'somi_swin_attention_lse_floats': (Z, [I, I, I, I]),
+    'somi_swin_attention_f32': (I, [P, P, P, I, I, I, I, I, I, P, P, S]),
+    'somi_swin_attention_bwd_workspace_floats': (Z, [I, I, I, I]),
+    'somi_swin_attention_backward_f32': (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, S]),
+    'somi_layernorm_bwd_workspace_floats': (Z, [C.c_long, I]),
+    'somi_layernorm_bwd_nhwc_f32': (I, [P, P, F, P, P, P, P, P, P, C.c_long, I, S]),
+    'somi_gelu_bwd_f32': (I, [P, P, P, C.c_long, S]),
     'somi_axpby_f32': (I, [P, P, C.c_long, F, F, S]),
     'somi_nms_workspace_bytes': (Z, [I, I, I, I]),
     'somi_nms_f32': (I, [P, I, I, I, F, F, I, I, P, I, P, P, P, Z, S]),

@@ -1850,6 +1850,289 @@ class PSA(nn.Module):
         return self.cv1.backward(dcat, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
+# ------------------------------------------------------------------------------------------------ Swin (C3STR)
+def swin_region_ids(hp, wp, window_size=8, shift_size=4):
+    """The region ids a shifted layer masks by: create_mask's img_mask (models/common.py:1295-1306) on the padded map, (hp, wp) in the
+    reference's frame - hp is ITS axis 1, which runs along the map's W (SwinTransformerLayer.forward names b, c, w, h = x.shape and permutes to
+    (b, h, w, c), :1317-1318).  The first entry of the reference's h_slices is the tuple (0, -window_size), not a slice: an index list, so
+    along that axis only rows 0 and hp - window_size take the first group's ids - the latter overwritten by the second group - and the rows
+    between keep 0.  Reproduced as written.  -> int32 (hp, wp)."""
+    m = torch.zeros(hp, wp, dtype=torch.int32)
+    rows = ([0, hp - window_size], slice(hp - window_size, hp - shift_size), slice(hp - shift_size, hp))
+    cols = (slice(0, wp - window_size), slice(wp - window_size, wp - shift_size), slice(wp - shift_size, wp))
+    cnt = 0
+    for r in rows:
+        for c in cols:
+            m[r, c] = cnt
+            cnt += 1
+    return m
+
+
+def _whole(a, c, what):
+    if a.coff != 0 or a.c != c or a.t.shape[3] != c:
+        raise NotImplementedError(f'{what} takes a whole (B,H,W,{c}) tensor, got channels [{a.coff}, {a.coff + a.c}) of {a.t.shape[3]}')
+    return a.t
+
+
+def _linear_backward(lin, src, dy, wt):
+    """Backward of an nn.Linear run as a 1x1 NHWC convolution over the whole tensor `src`: weight and bias gradients into .grad (the weight's
+    straight into a contiguous fp32 .grad - the optimizer's flat view - by the wgrad kernel), -> the data gradient.  wt: weight.t(), contiguous."""
+    c2, c1 = lin.weight.shape
+    g = lin.weight.grad
+    if g is not None and g.is_contiguous() and g.dtype == torch.float32 and g.device == dy.device:
+        ops.conv2d_wgrad_nhwc(src, dy, kh=1, kw=1, cin=c1, cout=c2, out=g, accumulate=g)
+    else:
+        _acc_grad(lin.weight, ops.conv2d_wgrad_nhwc(src, dy, kh=1, kw=1, cin=c1, cout=c2))
+    if lin.bias is not None:
+        (db,), fin = _grad_targets(lin.bias)
+        ops.chan_sum_(dy, c2, 0, db)
+        fin()
+    B, H, W, _ = src.shape
+    return ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1, kh=1, kw=1, cout=c2)
+
+
+def _f32dev(t, dev):
+    return t.detach().float().contiguous().to(dev)
+
+
+class WindowAttention(_Packed):
+    """proj(window attention(qkv(x))) (models/common.py:1184-1264) with the reference's constructor, parameter and buffer names.  It runs on the
+    NHWC map, not on partitioned windows: forward(x, shift, region_ids) takes the normalised (B,H,W,C) tensor; the cyclic shift, the padding,
+    the window partition and their inverses happen inside the attention kernels (swin.hip).  Window 8x8, head_dim 32, no qkv bias, no dropout."""
+
+    def __init__(self, dim, window_size, num_heads, qkv_bias=True, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.dim, self.window_size, self.num_heads = dim, tuple(window_size), num_heads
+        if self.window_size != (8, 8):
+            raise NotImplementedError(f'WindowAttention: window {self.window_size}: the attention kernels have window 8x8')
+        if num_heads < 1 or dim != 32 * num_heads:
+            raise NotImplementedError(f'WindowAttention({dim}, heads {num_heads}): the attention kernels need head_dim 32 (dim = 32 * num_heads; '
+                                      f'C3STR: hidden width c_ a multiple of 32)')
+        if qkv_bias or attn_drop or proj_drop:
+            raise NotImplementedError('WindowAttention: qkv_bias / dropout are not on the path (C3STR uses neither)')
+        self.scale = (dim // num_heads) ** -0.5
+        self.relative_position_bias_table = nn.Parameter(torch.zeros(15 * 15, num_heads))
+        co = torch.stack(torch.meshgrid([torch.arange(8), torch.arange(8)], indexing='ij')).flatten(1)
+        rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0).contiguous() + 7
+        self.register_buffer('relative_position_index', rel[:, :, 0] * 15 + rel[:, :, 1])   # kept for state dicts; the kernels compute it
+        self.qkv = nn.Linear(dim, dim * 3, bias=False)
+        self.proj = nn.Linear(dim, dim)
+        nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack(self, dev):
+        pk = dict(wqkv=_f32dev(self.qkv.weight, dev), wproj=_f32dev(self.proj.weight, dev), bproj=_f32dev(self.proj.bias, dev),
+                  table=_f32dev(self.relative_position_bias_table, dev))
+        if self.training:
+            pk.update(wqkv_t=_f32dev(self.qkv.weight.t(), dev), wproj_t=_f32dev(self.proj.weight.t(), dev))
+        return pk
+
+    def forward(self, x, shift=0, region_ids=None, residual=None):
+        """x: the (B,H,W,C) tensor behind norm1; residual: a tensor added in proj's pass (the layer's shortcut)."""
+        pk = self._packed(x.device)
+        qkv = ops.conv2d_nhwc(x, pk['wqkv'], None, kh=1, kw=1)
+        o, lse = ops.window_attention(qkv, pk['table'], self.num_heads, shift, region_ids, lse=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (x, qkv, o, lse, shift, region_ids, pk)
+        return ops.conv2d_nhwc(o, pk['wproj'], pk['bproj'], kh=1, kw=1, residual=residual)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('WindowAttention writes its own input gradient')
+        x, qkv, o, lse, shift, region_ids, pk = self.__dict__.pop('_ctx')
+        do = _linear_backward(self.proj, o, dout, pk['wproj_t'])
+        (gt,), fin = _grad_targets(self.relative_position_bias_table)
+        dqkv = ops.window_attention_backward(qkv, pk['table'], do, lse, self.num_heads, shift, region_ids, dtable=gt)
+        fin()
+        return _linear_backward(self.qkv, x, dqkv, pk['wqkv_t'])
+
+
+class Mlp(_Packed):
+    """fc2(GELU(fc1(x))) (models/common.py:1147-1168), the Linear layers as 1x1 NHWC convolutions.  Eval: GELU rides fc1's epilogue; training
+    keeps fc1's output (the GELU backward reads it) and applies the GELU in a pass of its own."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        if act_layer is not nn.GELU or drop:
+            raise NotImplementedError('Mlp: exact GELU and no dropout on the path')
+        self.fc1 = nn.Linear(in_features, hidden_features or in_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack(self, dev):
+        pk = dict(w1=_f32dev(self.fc1.weight, dev), b1=_f32dev(self.fc1.bias, dev), w2=_f32dev(self.fc2.weight, dev), b2=_f32dev(self.fc2.bias, dev))
+        if self.training:
+            hid = self.fc1.out_features
+            pk.update(w1_t=_f32dev(self.fc1.weight.t(), dev), w2_t=_f32dev(self.fc2.weight.t(), dev), one=torch.ones(hid, device=dev),
+                      zero=torch.zeros(hid, device=dev))
+        return pk
+
+    def forward(self, x, residual=None, out=None):
+        """x: a whole (B,H,W,C) tensor; residual: added in fc2's pass; out: the Act (channel slice) fc2 writes."""
+        pk = self._packed(x.device)
+        hid, c2 = self.fc1.out_features, self.fc2.out_features
+        if self.training:
+            u = ops.conv2d_nhwc(x, pk['w1'], pk['b1'], kh=1, kw=1)
+            g = ops.chan_affine_act(u, hid, 0, pk['one'], pk['zero'], 'gelu', 0, torch.empty_like(u))
+            self.__dict__['_ctx'] = (x, u, g, pk)
+        else:
+            g = ops.conv2d_nhwc(x, pk['w1'], pk['b1'], kh=1, kw=1, act='gelu')
+        if out is None:
+            return ops.conv2d_nhwc(g, pk['w2'], pk['b2'], kh=1, kw=1, residual=residual)
+        ops.conv2d_nhwc(g, pk['w2'], pk['b2'], kh=1, kw=1, residual=residual, out=out.t, cout=c2, y_coff=out.coff)
+        return out.t
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('Mlp writes its own input gradient')
+        x, u, g, pk = self.__dict__.pop('_ctx')
+        dg = _linear_backward(self.fc2, g, dout, pk['w2_t'])
+        return _linear_backward(self.fc1, x, ops.gelu_backward_(u, dg), pk['w1_t'])
+
+
+class SwinTransformerLayer(_Packed):
+    """x + attn(norm1(x)), then + mlp(norm2(.)) on 8x8 windows, shifted by shift_size (models/common.py:1267-1358), on the NHWC map.  Both
+    residual sums ride the output passes of attn.proj and mlp.fc2; in backward they ride the two LayerNorm backward passes.  Stochastic depth
+    (drop_path = 0.1 when num_heads > 10, :1273-1274) is the identity in eval and not implemented for training."""
+
+    def __init__(self, c, num_heads, window_size=7, shift_size=0, mlp_ratio=4, qkv_bias=False, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        if num_heads > 10:
+            drop_path = 0.1
+        if norm_layer is not nn.LayerNorm:
+            raise NotImplementedError('SwinTransformerLayer: nn.LayerNorm only')
+        if shift_size not in (0, 4):
+            raise NotImplementedError(f'SwinTransformerLayer: shift {shift_size} (0 or 4: window 8)')
+        self.window_size, self.shift_size, self.mlp_ratio, self.drop_path_rate = window_size, shift_size, mlp_ratio, float(drop_path)
+        self.norm1 = norm_layer(c)
+        self.attn = WindowAttention(c, window_size=(window_size, window_size), num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop,
+                                    proj_drop=drop)
+        self.norm2 = norm_layer(c)
+        self.mlp = Mlp(in_features=c, hidden_features=int(c * mlp_ratio), act_layer=act_layer, drop=drop)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack_params(self):
+        return [self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias]
+
+    def _pack(self, dev):
+        return tuple(_f32dev(p, dev) for p in self._pack_params())
+
+    def _region_ids(self, H, W, dev):
+        """The shift mask's region ids for an (H, W) map: (Wp, Hp), the reference's transposed frame (swin_region_ids)."""
+        if not self.shift_size:
+            return None
+        key = (H, W, dev)
+        cache = self.__dict__.setdefault('_ids', {})
+        if key not in cache:
+            cache[key] = swin_region_ids((W + 7) // 8 * 8, (H + 7) // 8 * 8, self.window_size, self.shift_size).to(dev)
+        return cache[key]
+
+    def forward(self, x, out=None):
+        c = self.norm1.normalized_shape[0]
+        if self.training and self.drop_path_rate > 0:
+            raise NotImplementedError(f'SwinTransformerLayer with {self.attn.num_heads} heads trains with stochastic depth (drop_path = '
+                                      f'{self.drop_path_rate}, num_heads > 10), which is not on the path; eval works')
+        xt = _whole(x, c, 'SwinTransformerLayer')
+        g1, b1, g2, b2 = self._packed(xt.device)
+        B, H, W, _ = xt.shape
+        n1 = ops.layernorm_act(xt, g1, b1, self.norm1.eps)
+        x1 = self.attn(n1, self.shift_size, self._region_ids(H, W, xt.device), residual=xt)
+        n2 = ops.layernorm_act(x1, g2, b2, self.norm2.eps)
+        y = self.mlp(n2, residual=x1, out=out)
+        if self.training:
+            self.__dict__['_ctx'] = (xt, x1, g1, g2)
+        return out if out is not None else Act(y, 0, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('SwinTransformerLayer writes its own input gradient')
+        xt, x1, g1, g2 = self.__dict__.pop('_ctx')
+        c = xt.shape[3]
+        if dout.coff != 0 or dout.t.shape[3] != c:                # a channel slice (C3STR: half of cv3's data gradient): one copy
+            d = torch.empty_like(xt)
+            ops.resample_slice(dout.t, dout.coff, d, 0, c)
+        else:
+            d = dout.t
+        dn2 = self.mlp.backward(d)
+        (gw, gb), fin = _grad_targets(self.norm2.weight, self.norm2.bias)
+        dx1 = ops.layernorm_backward(x1, g2, self.norm2.eps, dn2, gw, gb, add=d)
+        fin()
+        dn1 = self.attn.backward(dx1)
+        (gw, gb), fin = _grad_targets(self.norm1.weight, self.norm1.bias)
+        dx = ops.layernorm_backward(xt, g1, self.norm1.eps, dn1, gw, gb, add=dx1)
+        fin()
+        return Act(dx, 0, c)
+
+
+class SwinTransformerBlock(nn.Module):
+    """num_layers SwinTransformerLayers, shift 0 for even and window_size // 2 for odd ones (models/common.py:1361-1378)."""
+
+    def __init__(self, c1, c2, num_heads, num_layers, window_size=8):
+        super().__init__()
+        self.conv = None
+        if c1 != c2:
+            self.conv = Conv(c1, c2)
+        self.window_size = window_size
+        self.shift_size = window_size // 2
+        self.tr = nn.Sequential(*(SwinTransformerLayer(c2, num_heads=num_heads, window_size=window_size,
+                                                       shift_size=0 if (i % 2 == 0) else self.shift_size) for i in range(num_layers)))
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x, out=None):
+        """out: the Act (channel slice) the last layer writes."""
+        if self.conv is not None:
+            x = self.conv(x)
+        n = len(self.tr)
+        for i, layer in enumerate(self.tr):
+            x = layer(x, out=out if i == n - 1 else None)
+        return x
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('SwinTransformerBlock writes its own input gradient')
+        for layer in reversed(self.tr):
+            dout = layer.backward(dout)
+        return dout if self.conv is None else self.conv.backward(dout, need_dx=need_dx)
+
+
+class C3STR(C3):
+    """C3 whose bottlenecks are one SwinTransformerBlock(c_, c_, c_ // 32, n) (models/common.py:1632-1637).  The last Swin layer's fc2 and cv2
+    write the two halves of cv3's input."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        if c_ % 32 or c_ == 0:
+            raise NotImplementedError(f'C3STR with hidden width {c_}: the window attention kernels need head_dim 32, i.e. c_ a multiple of 32')
+        self.m = SwinTransformerBlock(c_, c_, c_ // 32, n)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x):
+        c_ = self.cv1.conv.out_channels
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, 2 * c_)
+        self.m(self.cv1(x), out=cat.slice(0, c_))
+        self.cv2(x, out=cat.slice(c_, c_))
+        return self.cv3(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('C3STR writes its own input gradient')
+        c_ = self.cv1.conv.out_channels
+        dcat = self.cv3.backward(dout)
+        dx = self.cv2.backward(dcat.slice(c_, c_), need_dx=need_dx)
+        d = self.m.backward(dcat.slice(0, c_))
+        self.cv1.backward(d, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return dx
+
+
 class Concat(nn.Module):
     """torch.cat(x, 1) (models/common.py:2085-2097) of NHWC channel slices; an input that is a 2x nearest-upsampled view
     (`Upsample` only sets a flag) is expanded by the same copy.  Backward hands out slices of the incoming gradient (no copy) and

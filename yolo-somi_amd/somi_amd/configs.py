@@ -144,6 +144,15 @@ def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0', upsam
                 backbone=copy.deepcopy(bb), head=_swap_upsample(copy.deepcopy(hd), upsample))
 
 
+def yolov5_swin_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
+    """The layer table of models/hub/yolov5s-transformer.yaml (yolov5s with the Focus stem and SPP(5,9,13), a transformer C3 as the last
+    backbone row) with C3STR - the Swin variant, models/common.py:1632-1637 - where that file has C3TR (row 9).  The reference registers C3STR
+    in its parser (models/yolo.py:1476,1487) but ships no yaml that names it; C3TR itself stays outside the path.  Defaults are the yaml's."""
+    cfg = yolov5_cfg(width, depth, nc, anchors, version='5.0')
+    cfg['backbone'][9][2] = 'C3STR'
+    return cfg
+
+
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
     C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""

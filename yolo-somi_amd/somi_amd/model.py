@@ -7,8 +7,8 @@ raw_l = (B,na,ny,nx,no).  Input is the reference's `(B,3,H,W)` NCHW batch, eithe
 section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, Concat, Detect - BASELINE configs[0]) and the Ghost set
 of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv), the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
 C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny, yolov5-fpn / -panet / -p6 / -p7): BottleneckCSP,
-nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; and the two learned
-drop-ins for the neck's nn.Upsample rows, CARAFE and DySample.
+nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; the two learned
+drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; and C3STR, the Swin-transformer C3 (C3TR stays outside).
 """
 import math
 from copy import deepcopy
@@ -28,8 +28,8 @@ def make_divisible(x, divisor):
 _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bottleneck': B.Bottleneck, 'C3': B.C3, 'SPP': B.SPP,
        'Focus': B.Focus, 'GhostConv': B.GhostConv, 'GhostBottleneck': B.GhostBottleneck, 'DWConv': B.DWConv,
        'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA,
-       'BottleneckCSP': B.BottleneckCSP}                          # models/yolo.py:1472-1479
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP')  # models/yolo.py:1487-1492
+       'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR}        # models/yolo.py:1472-1479
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR')  # models/yolo.py:1487-1492
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
 

@@ -879,6 +879,67 @@ def psa_attention_backward(qkv, o, dout, lse, heads, *, qkv_coff=0, o_coff=0, do
     return out
 
 
+# ---------------------------------------------------------------------------------------------- Swin window attention
+# fp32 always, window 8 / head_dim 32 (swin.hip).  Whole contiguous tensors.
+def _swin_args(qkv, table, heads, shift, region_ids, what):
+    B, H, W, c3 = qkv.shape
+    if c3 % 3 or c3 // 3 != 32 * heads:
+        raise NotImplementedError(f'{what}: head_dim 32 only, got {c3 // 3} channels for {heads} heads')
+    if tuple(table.shape) != (225, heads):
+        raise RuntimeError(f'{what}: the bias table must be (225, {heads}), got {tuple(table.shape)}')
+    if shift:
+        hp, wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
+        if region_ids is None or region_ids.dtype != torch.int32 or tuple(region_ids.shape) != (wp, hp) or not region_ids.is_contiguous():
+            raise RuntimeError(f'{what}: a shifted layer needs a contiguous int32 region-id map of shape ({wp}, {hp})')
+    return B, H, W, c3 // 3
+
+
+def window_attention(qkv, table, heads, shift=0, region_ids=None, *, lse=False):
+    """8x8-window multi-head attention of SwinTransformerLayer over the bias-free qkv Linear's output (B,H,W,3C) (channel = which*C + head*32
+    + d), with the relative-position bias `table` (225, heads), the cyclic `shift` (0 or 4), the zero padding up to the window grid and the
+    shift mask from `region_ids` (int32 (Wp,Hp), blocks.swin_region_ids) -> (o (B,H,W,C), lse or None): the log-sum-exp the backward needs."""
+    B, H, W, C_ = _swin_args(qkv, table, heads, shift, region_ids, 'window attention')
+    L = _lib.lib()
+    out = torch.empty(B, H, W, C_, device=qkv.device, dtype=torch.float32)
+    lt = torch.empty(L.somi_swin_attention_lse_floats(B, H, W, heads), device=qkv.device, dtype=torch.float32) if lse else None
+    check(L.somi_swin_attention_f32(_ptr(_f32c(qkv, 'qkv')), _ptr(_f32c(table, 'bias table')), _ptr(region_ids if shift else None), B, H, W, C_,
+                                    heads, shift, _ptr(out), _ptr(lt), _stream()), 'window_attention')
+    return out, lt
+
+
+def window_attention_backward(qkv, table, dout, lse, heads, shift=0, region_ids=None, *, dtable):
+    """Gradient of window_attention w.r.t. q, k and v -> (B,H,W,3C) in the qkv layout; the bias table's gradient is accumulated into
+    `dtable` (225, heads), in a fixed order."""
+    B, H, W, C_ = _swin_args(qkv, table, heads, shift, region_ids, 'window attention backward')
+    if tuple(dout.shape) != (B, H, W, C_) or tuple(dtable.shape) != (225, heads):
+        raise RuntimeError(f'window attention backward: dout must be ({B}, {H}, {W}, {C_}) and dtable (225, {heads})')
+    L = _lib.lib()
+    out = torch.empty_like(qkv)
+    ws = torch.empty(L.somi_swin_attention_bwd_workspace_floats(B, H, W, heads), device=qkv.device, dtype=torch.float32)
+    check(L.somi_swin_attention_backward_f32(_ptr(_f32c(qkv, 'qkv')), _ptr(_f32c(table, 'bias table')), _ptr(region_ids if shift else None),
+                                             _ptr(_f32c(dout, 'gradient')), _ptr(_f32c(lse, 'lse')), B, H, W, C_, heads, shift, _ptr(out),
+                                             _ptr(_f32c(dtable, 'table gradient')), _ptr(ws), _stream()), 'window_attention_backward')
+    return out
+
+
+def layernorm_backward(u, gamma, eps, dy, dgamma, dbeta, add=None):
+    """y = LayerNorm(u) over the last dim -> du (+ add, the gradient of a residual branch around the norm); dgamma / dbeta are accumulated."""
+    C_ = u.shape[-1]
+    n = u.numel() // C_
+    du = torch.empty_like(u)
+    L = _lib.lib()
+    ws = torch.empty(L.somi_layernorm_bwd_workspace_floats(n, C_), device=u.device, dtype=torch.float32)
+    check(L.somi_layernorm_bwd_nhwc_f32(_ptr(_f32c(u)), _ptr(gamma), float(eps), _ptr(_f32c(dy)), _ptr(None if add is None else _f32c(add)),
+                                        _ptr(du), _ptr(dgamma), _ptr(dbeta), _ptr(ws), n, C_, _stream()), 'layernorm_backward')
+    return du
+
+
+def gelu_backward_(u, dy):
+    """dy *= gelu'(u) in place (exact GELU)."""
+    check(_lib.lib().somi_gelu_bwd_f32(_ptr(_f32c(u)), _ptr(_f32c(dy)), _ptr(dy), u.numel(), _stream()), 'gelu_backward')
+    return dy
+
+
 # ---------------------------------------------------------------------------------------------- training-mode helpers
 def _npix(t):
     return t.shape[0] * t.shape[1] * t.shape[2]

@@ -83,6 +83,9 @@ class FusedAdamEMA:
         for plist, wd in ((g0, 0.0), (g1, weight_decay), (g2, 0.0)):
             plist = [p for p in plist if id(p) not in seen and not seen.add(id(p))]
             groups.append((plist, wd))
+        # a Parameter that is neither a `.weight` nor a `.bias` (WindowAttention.relative_position_bias_table) is in no group of the reference's
+        # either (train.py:125-133): its gradient is computed, no step moves it, it stays outside the flat buffers and the EMA shadow equals it
+        self._ungrouped = [p for p in model.parameters() if id(p) not in seen]
         # Conv+BN blocks keep their weight master in the kernels' forward packing: nothing to repack per step, and the
         # weight gradient is accumulated into the gradient buffer by the wgrad kernel itself
         from .blocks import Conv
@@ -152,6 +155,8 @@ class FusedAdamEMA:
     def zero_grad(self, set_to_none=False):
         for st in self._flat:
             st['g'].data.zero_()
+        for p in self._ungrouped:
+            p.grad = None
 
     def step(self):
         self.steps += 1
