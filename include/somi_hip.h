@@ -51,7 +51,16 @@ size_t somi_sizeof_desc(int which);
 /* ------------------------------------------------------------------------------------------
  * Activations used in fused epilogues.
  */
-enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_ACT_RELU = 3, SOMI_ACT_SIGMOID = 4 };
+enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_ACT_RELU = 3, SOMI_ACT_SIGMOID = 4,
+                SOMI_ACT_LEAKY = 5 /* LeakyReLU(0.1), add_conv of models/common.py:5322-5343: the dense conv epilogue, somi_chan_affine_act_* and the
+                                      somi_bn_act_backward_* family take it; somi_linear_f32 keeps reading 5 as its softmax */ };
+
+/* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc).  An input slice is only read. */
+typedef struct somi_slice {
+    float *p;
+    int32_t cs, coff;
+} somi_slice;
 
 /* ------------------------------------------------------------------------------------------
  * Dense convolution as NHWC implicit GEMM on MFMA with a fused epilogue.
@@ -270,6 +279,11 @@ int somi_sppf_pool_codes_nhwc_f32(float *buf, void *codes, int B, int H, int W, 
  *   from x = slice [x_coff, x_coff + C) of buf (B,H,W,cs) the slices at x_coff + (i + 1) * C = pool_k[i](x), in place, in one walk over the largest window.
  *   codes: nk*B*H*W*C bytes, window-major.  The backward ADDS the routed gradients of dbuf's slices 1..nk into its slice 0 (which holds x's direct
  *   gradient from the concat's consumer). */
+/* maxpool3s2: F.max_pool2d(x, 3, stride=2, padding=1) (ASFF level 0, models/common.py:5536).  The pad is an implicit -inf (it never wins; maxpool2's
+ *   pad value is 0).  x (B,H,W,.) -> y (B,Ho,Wo,.), Ho = (H + 2 - 3) / 2 + 1, any H, W >= 1; codes: B*Ho*Wo*C bytes, r * 3 + q each.  The backward
+ *   WRITES dx (B,H,W,.): an element gathers from the up to four windows that cover it, nothing else writes it. */
+int somi_maxpool3s2_nhwc_f32(const somi_slice *x, const somi_slice *y, void *codes, int B, int H, int W, int C, somi_stream_t stream);
+int somi_maxpool3s2_bwd_nhwc_f32(const somi_slice *dy, const void *codes, const somi_slice *dx, int B, int H, int W, int C, somi_stream_t stream);
 int somi_maxpool2_nhwc_f32(const float *x, float *y, void *codes, int B, int H, int W, int C, int x_cs, int x_coff, int y_cs, int y_coff, int stride,
                            int pad_l, int pad_r, int pad_t, int pad_b, somi_stream_t stream);
 int somi_maxpool2_bwd_nhwc_f32(const float *dy, const void *codes, float *dx, int B, int H, int W, int C, int dy_cs, int dy_coff, int dx_cs, int dx_coff,
@@ -302,6 +316,36 @@ int somi_dysample_nhwc_f32(const float *x, const float *offset, const float *ini
 int somi_dysample_bwd_nhwc_f32(const float *dout, const float *x, const float *offset, const float *init_pos, float *dx, float *doffset, void *far_count,
                                int B, int H, int W, int C, int groups, int d_cs, int d_coff, int x_cs, int x_coff, int f_cs, int f_coff, int dx_cs,
                                int dx_coff, int df_cs, int df_coff, somi_stream_t stream);
+
+/* Adaptive spatial feature fusion (ASFF.forward, models/common.py:5551-5560; asff.hip), the data-dependent cousin of the BiFPN fusion below.
+ * Per pixel of the (B,H,W) output:  L = w . cat(v_0, v_1, v_2) + bias (the 48 -> 3 1x1 `weight_levels` conv),  p = softmax(L) with the maximum
+ * subtracted,  fused = sum_i p_i * r_i.  Source r_i (C channels) and weight map v_i (16 channels) are each read at (h >> up, w >> up) with their own
+ * up in {0, 1, 2}: r_i is a (B, H >> r_up[i], W >> r_up[i], .) slice, v_i a (B, H >> v_up[i], W >> v_up[i], .) slice; H and W are multiples of the
+ * largest factor.  No upsampled, concatenated or per-source product tensor is formed.
+ * forward  (somi_asff_fuse_nhwc_f32): writes `out` = fused and, when p is given (training), p (B,H,W,3) contiguous - all backward needs beyond its inputs.
+ * backward (somi_asff_fuse_bwd_nhwc_f32): `out` holds dfused (read).  dL_i = p_i (<dfused, r_i> - sum_j p_j <dfused, r_j>);
+ *   dr[i] = p_i * dfused in r_i's layout - the owner of a low-resolution element sums its 4 or 16 children in row-major order; dr[i].p NULL skips it,
+ *   dr_accumulate[i] adds to what dr[i] holds;  dv[i] = w^T dL in v_i's layout, summed over the children likewise (written);  dw[3][48] and db[3]
+ *   ACCUMULATED: one partial per workgroup in `workspace` (somi_asff_fuse_bwd_workspace_floats(B, H, W) floats, 16-byte aligned), then one
+ *   fixed-order reduce.  No float atomics: two launches are bit-identical. */
+typedef struct somi_asff_desc {
+    somi_slice r[3], v[3];     /* the sources (width C) and the weight maps (width 16) */
+    int32_t r_up[3], v_up[3];
+    const float *w;            /* [3][48], 16-byte aligned */
+    const float *bias;         /* [3] */
+    somi_slice out;            /* forward: fused, written; backward: dfused, read (B,H,W,.) */
+    float *p;                  /* (B,H,W,3): forward writes it when non-NULL, backward reads it */
+    somi_slice dr[3], dv[3];   /* backward only */
+    int32_t dr_accumulate[3];
+    int32_t B, H, W, C;
+    float *dw, *db;            /* backward only, accumulated */
+    float *workspace;
+    uint64_t workspace_floats;
+} somi_asff_desc;
+size_t somi_asff_desc_bytes(void);   /* sizeof(somi_asff_desc) as the library was compiled: lets a binding check its mirror */
+size_t somi_asff_fuse_bwd_workspace_floats(int B, int H, int W);
+int somi_asff_fuse_nhwc_f32(const somi_asff_desc *d, somi_stream_t stream);
+int somi_asff_fuse_bwd_nhwc_f32(const somi_asff_desc *d, somi_stream_t stream);
 
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed

@@ -91,6 +91,7 @@ __device__ __forceinline__ float apply_act(float v) {
     else if constexpr (ACT == SOMI_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     else if constexpr (ACT == SOMI_ACT_RELU) return fmaxf(v, 0.0f);
     else if constexpr (ACT == SOMI_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
+    else if constexpr (ACT == SOMI_ACT_LEAKY) return v > 0.0f ? v : 0.1f * v;
     else return v;
 }
 
@@ -100,6 +101,7 @@ __device__ __forceinline__ float apply_act_rt(float v, int act) {
         case SOMI_ACT_GELU: return apply_act<SOMI_ACT_GELU>(v);
         case SOMI_ACT_RELU: return apply_act<SOMI_ACT_RELU>(v);
         case SOMI_ACT_SIGMOID: return apply_act<SOMI_ACT_SIGMOID>(v);
+        case SOMI_ACT_LEAKY: return apply_act<SOMI_ACT_LEAKY>(v);
         default: return v;
     }
 }

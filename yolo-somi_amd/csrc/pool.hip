@@ -1,5 +1,5 @@
 // Max-pooling outside SPPF's chained 5x5 (layers.hip / train_blocks.hip): the strided 2x2 pool of nn.MaxPool2d(2, s, 0) with an optional ZERO pad folded
-// into the read (yolov3-tiny: nn.ZeroPad2d([0, 1, 0, 1]) + nn.MaxPool2d(2, 1, 0)), and the PARALLEL stride-1 windows of SPP(k) for any ascending set of
+// into the read (yolov3-tiny: nn.ZeroPad2d([0, 1, 0, 1]) + nn.MaxPool2d(2, 1, 0)), ASFF's F.max_pool2d(x, 3, 2, 1) with its -inf pad, and the PARALLEL stride-1 windows of SPP(k) for any ascending set of
 // odd k in 3..13 (yolov3-spp, yolov5-p6 (3, 5, 7), yolov5-p7 (3, 5)).  NHWC fp32, channel slices (cs, coff), a lane owns one channel quad of one pixel:
 // 16-byte loads and stores, contiguous across the wave.  No LDS: every tap of a window is another lane's own pixel one row or column over, so the
 // re-reads hit L1 / L2, and the kernels move one read of x and one write per output slice through HBM.
@@ -97,6 +97,78 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float *__restri
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (((code >> (8 * e)) & 0xFFu) == (uint32_t)(r * 2 + q)) acc[e] += d[e];
+            }
+        }
+        *reinterpret_cast<f32x4 *>(dx + pix * dx_cs + dx_coff + c) = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 3x3, stride 2, implicit -inf pad of 1
+// F.max_pool2d(x, 3, stride=2, padding=1) (ASFF level 0, models/common.py:5536): y[b, ho, wo] = max over (r, q) in 3x3 of x[b, 2 ho - 1 + r, 2 wo - 1 + q],
+// positions outside x never win (the pad is -inf, unlike maxpool2's zero border).  The centre tap (1, 1) is always inside x.
+template <typename IDX>
+__global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, uint8_t *__restrict__ codes, int B, int H,
+                                                             int W, int Ho, int Wo, int C, int x_cs, int x_coff, int y_cs, int y_coff) {
+    const int C4 = C >> 2;
+    const IDX items = (IDX)B * Ho * Wo * C4;
+    for (IDX it = (IDX)blockIdx.x * 256 + threadIdx.x; it < items; it += (IDX)gridDim.x * 256) {
+        const int c = (int)(it % (IDX)C4) * 4;
+        const IDX pixi = it / (IDX)C4, rowi = pixi / (IDX)Wo;
+        const int wo = (int)(pixi - rowi * Wo), ho = (int)(rowi % (IDX)Ho);
+        const long pix = (long)pixi, b = (long)(rowi / (IDX)Ho);
+        const float ninf = -__builtin_huge_valf();
+        f32x4 m = {ninf, ninf, ninf, ninf};
+        int mi[4] = {4, 4, 4, 4};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int hi = ho * 2 - 1 + r;
+            if ((unsigned)hi >= (unsigned)H) continue;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int wi = wo * 2 - 1 + q;
+                if ((unsigned)wi >= (unsigned)W) continue;
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(x + ((b * H + hi) * W + wi) * x_cs + x_coff + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (v[e] > m[e]) { m[e] = v[e]; mi[e] = r * 3 + q; }
+            }
+        }
+        *reinterpret_cast<f32x4 *>(y + pix * y_cs + y_coff + c) = m;
+        if (codes) *reinterpret_cast<uint32_t *>(codes + pix * C + c) = pack_codes(mi);
+    }
+}
+
+// dx[b, h, w] = sum over the up to four windows (ho, wo) that hold (h, w) at tap (r, q) and whose code is r * 3 + q, the WINDOWS in row-major order (taps
+// descending) - the order in which torch's CPU backward adds them, so the sums agree bit for bit.  Written by the element's owner only.
+template <typename IDX>
+__global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const float *__restrict__ dy, const uint8_t *__restrict__ codes, float *__restrict__ dx, int B,
+                                                             int H, int W, int Ho, int Wo, int C, int dy_cs, int dy_coff, int dx_cs, int dx_coff) {
+    const int C4 = C >> 2;
+    const IDX items = (IDX)B * H * W * C4;
+    for (IDX it = (IDX)blockIdx.x * 256 + threadIdx.x; it < items; it += (IDX)gridDim.x * 256) {
+        const int c = (int)(it % (IDX)C4) * 4;
+        const IDX pixi = it / (IDX)C4, rowi = pixi / (IDX)W;
+        const int wv = (int)(pixi - rowi * W), hv = (int)(rowi % (IDX)H);
+        const long pix = (long)pixi, b = (long)(rowi / (IDX)H);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 2; r >= 0; --r) {
+            const int th = hv + 1 - r;
+            if (th < 0 || (th & 1)) continue;
+            const int ho = th >> 1;
+            if (ho >= Ho) continue;
+#pragma unroll
+            for (int q = 2; q >= 0; --q) {
+                const int tw = wv + 1 - q;
+                if (tw < 0 || (tw & 1)) continue;
+                const int wo = tw >> 1;
+                if (wo >= Wo) continue;
+                const long o = (b * Ho + ho) * Wo + wo;
+                const uint32_t code = *reinterpret_cast<const uint32_t *>(codes + o * C + c);
+                const f32x4 d = *reinterpret_cast<const f32x4 *>(dy + o * dy_cs + dy_coff + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (((code >> (8 * e)) & 0xFFu) == (uint32_t)(r * 3 + q)) acc[e] += d[e];
             }
         }
         *reinterpret_cast<f32x4 *>(dx + pix * dx_cs + dx_coff + c) = acc;
@@ -257,6 +329,37 @@ extern "C" int somi_maxpool2_bwd_nhwc_f32(const float *dy, const void *codes, fl
         hipLaunchKernelGGL(maxpool2_bwd_kernel<uint64_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, dy, (const uint8_t *)codes, dx, B, H,
                            W, Ho, Wo, C, dy_cs, dy_coff, dx_cs, dx_coff, stride, pad_l, pad_t);
     return launch_status("somi_maxpool2_bwd_nhwc_f32");
+}
+
+extern "C" int somi_maxpool3s2_nhwc_f32(const somi_slice *x, const somi_slice *y, void *codes, int B, int H, int W, int C, somi_stream_t stream) {
+    SOMI_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && (!codes || aligned16(codes)), SOMI_EINVAL,
+                 "maxpool3s2: bad sizes (C a multiple of 4), or codes not 16-byte aligned");
+    SOMI_REQUIRE_SLICES("maxpool3s2", {"x", x->p, x->cs, x->coff, C}, {"y", y->p, y->cs, y->coff, C});
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long items = (long)B * Ho * Wo * (C / 4);
+    if (small_index(items))
+        hipLaunchKernelGGL(maxpool3s2_fwd_kernel<uint32_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, (const float *)x->p, y->p,
+                           (uint8_t *)codes, B, H, W, Ho, Wo, C, x->cs, x->coff, y->cs, y->coff);
+    else
+        hipLaunchKernelGGL(maxpool3s2_fwd_kernel<uint64_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, (const float *)x->p, y->p,
+                           (uint8_t *)codes, B, H, W, Ho, Wo, C, x->cs, x->coff, y->cs, y->coff);
+    return launch_status("somi_maxpool3s2_nhwc_f32");
+}
+
+extern "C" int somi_maxpool3s2_bwd_nhwc_f32(const somi_slice *dy, const void *codes, const somi_slice *dx, int B, int H, int W, int C,
+                                            somi_stream_t stream) {
+    SOMI_REQUIRE(dy && dx && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && codes && aligned16(codes), SOMI_EINVAL,
+                 "maxpool3s2 bwd: bad sizes (C a multiple of 4), or no 16-byte aligned codes");
+    SOMI_REQUIRE_SLICES("maxpool3s2 bwd", {"dy", dy->p, dy->cs, dy->coff, C}, {"dx", dx->p, dx->cs, dx->coff, C});
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long items = (long)B * H * W * (C / 4);
+    if (small_index(items))
+        hipLaunchKernelGGL(maxpool3s2_bwd_kernel<uint32_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, (const float *)dy->p,
+                           (const uint8_t *)codes, dx->p, B, H, W, Ho, Wo, C, dy->cs, dy->coff, dx->cs, dx->coff);
+    else
+        hipLaunchKernelGGL(maxpool3s2_bwd_kernel<uint64_t>, dim3(pool_grid(items)), dim3(256), 0, (hipStream_t)stream, (const float *)dy->p,
+                           (const uint8_t *)codes, dx->p, B, H, W, Ho, Wo, C, dy->cs, dy->coff, dx->cs, dx->coff);
+    return launch_status("somi_maxpool3s2_bwd_nhwc_f32");
 }
 
 extern "C" int somi_spp_pool_nhwc_f32(float *buf, void *codes, int B, int H, int W, int C, int cs, int x_coff, int nk, int k0, int k1, int k2,

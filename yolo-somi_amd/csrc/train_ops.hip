@@ -30,6 +30,7 @@ __device__ __forceinline__ float act_grad(float u, int act) {
         case SOMI_ACT_GELU: return 0.5f * (1.f + erff(u * 0.70710678118654752440f)) + u * 0.39894228040143267794f * expf(-0.5f * u * u);
         case SOMI_ACT_RELU: return u > 0.f ? 1.f : 0.f;
         case SOMI_ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-u)); return s * (1.f - s); }
+        case SOMI_ACT_LEAKY: return u > 0.f ? 1.f : 0.1f;
         default: return 1.f;
     }
 }

@@ -48,6 +48,19 @@ class LossBoxRule(C.Structure):
                 ('wiou_mean', C.c_void_p), ('wiou_train', C.c_int32)]
 
 
+class Slice(C.Structure):
+    """struct somi_slice (include/somi_hip.h): a channel slice as one argument."""
+    _fields_ = [('p', C.c_void_p), ('cs', C.c_int32), ('coff', C.c_int32)]
+
+
+class AsffDesc(C.Structure):
+    """struct somi_asff_desc (include/somi_hip.h)."""
+    _fields_ = [('r', Slice * 3), ('v', Slice * 3), ('r_up', C.c_int32 * 3), ('v_up', C.c_int32 * 3), ('w', C.c_void_p), ('bias', C.c_void_p),
+                ('out', Slice), ('p', C.c_void_p), ('dr', Slice * 3), ('dv', Slice * 3), ('dr_accumulate', C.c_int32 * 3),
+                ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('dw', C.c_void_p), ('db', C.c_void_p),
+                ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -191,6 +204,12 @@ SIGNATURES = {
     'somi_yolo_loss_rule_f32': (I, [C.POINTER(LossDesc), C.POINTER(LossLevel), C.POINTER(LossBoxRule), P, P, Z, S]),
     'somi_maxpool2_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_maxpool2_bwd_nhwc_f32': (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_maxpool3s2_nhwc_f32': (I, [C.POINTER(Slice), C.POINTER(Slice), P, I, I, I, I, S]),
+    'somi_maxpool3s2_bwd_nhwc_f32': (I, [C.POINTER(Slice), P, C.POINTER(Slice), I, I, I, I, S]),
+    'somi_asff_desc_bytes': (Z, []),
+    'somi_asff_fuse_bwd_workspace_floats': (Z, [I, I, I]),
+    'somi_asff_fuse_nhwc_f32': (I, [C.POINTER(AsffDesc), S]),
+    'somi_asff_fuse_bwd_nhwc_f32': (I, [C.POINTER(AsffDesc), S]),
     'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
@@ -240,7 +259,7 @@ def lib():
         if L.somi_abi_version() != ABI_VERSION and not lax:
             raise RuntimeError('libsomi_hip.so ABI version mismatch')
         if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)
-                        or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule)):
+                        or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

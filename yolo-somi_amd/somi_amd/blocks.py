@@ -252,6 +252,10 @@ def _act_name(m):
         return 'relu'
     if isinstance(m, nn.GELU):
         return 'gelu'
+    if isinstance(m, nn.LeakyReLU):
+        if m.negative_slope != 0.1:
+            raise NotImplementedError(f'LeakyReLU({m.negative_slope}) is not on the SOMI path (negative slope 0.1 only, SOMI_ACT_LEAKY)')
+        return 'leaky'
     raise NotImplementedError(f'activation {type(m).__name__} is not on the SOMI path')
 
 
@@ -2224,6 +2228,215 @@ class Detect(nn.Module):
         widths = self.__dict__.pop('_ctx')
         return [run.backward(ops.detect_plain_raw_backward(draws[i].contiguous(), widths[i], self.na, self.nc))
                 for i, run in enumerate(self._runners)]
+
+
+# ================================================================================================ ASFF head
+class ConvBNLeaky(Conv):
+    """add_conv (models/common.py:5322-5343): Conv2d(bias=False, pad (k - 1) // 2) -> BatchNorm2d -> LeakyReLU(0.1), with the reference's child names
+    (`conv`, `batch_norm`, `leaky`) so its state dicts load.  Everything else is Conv: eval with the BatchNorm folded and the activation in the
+    conv epilogue, training through Conv's one BatchNorm path, the packed weight master of the optimizer."""
+
+    def __init__(self, in_ch, out_ch, ksize, stride, leaky=True):
+        nn.Module.__init__(self)
+        if not leaky:
+            raise NotImplementedError('add_conv(leaky=False) (ReLU6) is not on the SOMI path (LeakyReLU(0.1) only)')
+        if ksize not in (1, 3) or stride not in (1, 2):
+            raise NotImplementedError(f'add_conv with ksize={ksize}, stride={stride} is not on the SOMI path (ksize 1 or 3, stride 1 or 2)')
+        self.conv = nn.Conv2d(in_ch, out_ch, ksize, stride, (ksize - 1) // 2, bias=False)
+        self.batch_norm = nn.BatchNorm2d(out_ch)
+        self.leaky = nn.LeakyReLU(0.1)
+
+    bn = property(lambda self: self.batch_norm)                   # the names Conv's code reads
+    act = property(lambda self: self.leaky)
+    # never a layer of the parsed graph (it lives inside ASFF, which calls backward(dx_out=, accumulate=) itself): what the graph walk reads is off
+    accumulates = folds_pooled = False
+
+
+def add_conv(in_ch, out_ch, ksize, stride, leaky=True):
+    return ConvBNLeaky(in_ch, out_ch, ksize, stride, leaky)
+
+
+class MaxPool3s2(nn.Module):
+    """F.max_pool2d(x, 3, stride=2, padding=1) (models/common.py:5536), the pad an implicit -inf.  No parameters; ASFF keeps it out of its state dict."""
+
+    def forward(self, x):
+        if x.c % 4 or x.up:
+            raise NotImplementedError('max_pool2d(3, 2, 1) needs a real tensor with a channel count that is a multiple of 4')
+        B, H, W, _ = x.shape
+        out = new_act(x.t, ops.maxpool3s2_out_size(H), ops.maxpool3s2_out_size(W), x.c)
+        r = ops.maxpool3s2(x.t, x.c, x.coff, out=out.t, codes=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (r[1], H, W, x.c)
+        return out
+
+    def backward(self, dout, dx_out=None, accumulate=False):
+        codes, H, W, c = self.__dict__.pop('_ctx')
+        if dx_out is not None and not accumulate:
+            ops.maxpool3s2_backward(dout.t, codes, c, H, W, dout.coff, out=dx_out.t, dx_coff=dx_out.coff)
+            return dx_out
+        dx = Act(ops.maxpool3s2_backward(dout.t, codes, c, H, W, dout.coff), 0, c)
+        if dx_out is None:
+            return dx
+        ops.add_(dx_out.t, dx_out.coff, dx.t, 0, c)
+        return dx_out
+
+
+class ASFF(nn.Module):
+    """Adaptive spatial feature fusion at one level (models/common.py:5500-5567): the three pyramid maps are brought to this level's width and size
+    (x0 = P5, x1 = P4, x2 = P3: a 3x3 stride-2 conv down, max_pool2d(3, 2, 1) + conv two levels down, a 1x1 conv + nearest upsampling up), three
+    1x1 convs make 16-channel weight maps of them, a 48 -> 3 1x1 conv and a softmax turn those into per-pixel weights, and the weighted sum goes
+    through a 3x3 `expand` conv.  Here a 1x1-compressed map stays at its LOW resolution: the fusion kernels (ops.asff_fuse) read it, and its
+    weight map, at (h >> up, w >> up), so neither the upsampled maps, nor the concat, nor the softmax's logits, nor the products reach memory.
+    `weight_level_i` of an upsampled map runs at the low resolution too - a 1x1 conv commutes with nearest upsampling, the batch mean and the
+    biased variance are the same over the replicated pixels, the gradient of a low-resolution element is the sum over its children (formed in
+    the fusion backward) - and only the running variance's unbiased correction n / (n - 1) has to use the high-resolution pixel count."""
+    DIM = (512, 256, 128)
+
+    def __init__(self, level, rfb=False, vis=False):
+        super().__init__()
+        if rfb:
+            raise NotImplementedError('ASFF(rfb=True) (8-channel weight maps) is not on the SOMI path: the fusion kernels take 16-channel weight maps')
+        if vis:
+            raise NotImplementedError('ASFF(vis=True) (returning the weights and the channel sum) is not on the SOMI path: the weights stay in the kernel')
+        if level not in (0, 1, 2):
+            raise NotImplementedError(f'ASFF level {level}: three levels only')
+        self.level = level
+        self.dim = list(self.DIM)
+        self.inter_dim = self.dim[level]
+        if level == 0:
+            self.stride_level_1 = add_conv(256, self.inter_dim, 3, 2)
+            self.stride_level_2 = add_conv(128, self.inter_dim, 3, 2)
+            self.expand = add_conv(self.inter_dim, 512, 3, 1)
+        elif level == 1:
+            self.compress_level_0 = add_conv(512, self.inter_dim, 1, 1)
+            self.stride_level_2 = add_conv(128, self.inter_dim, 3, 2)
+            self.expand = add_conv(self.inter_dim, 256, 3, 1)
+        else:
+            self.compress_level_0 = add_conv(512, self.inter_dim, 1, 1)
+            self.compress_level_1 = add_conv(256, self.inter_dim, 1, 1)
+            self.expand = add_conv(self.inter_dim, 128, 3, 1)
+        compress_c = 16
+        self.weight_level_0 = add_conv(self.inter_dim, compress_c, 1, 1)
+        self.weight_level_1 = add_conv(self.inter_dim, compress_c, 1, 1)
+        self.weight_level_2 = add_conv(self.inter_dim, compress_c, 1, 1)
+        self.weight_levels = nn.Conv2d(compress_c * 3, 3, kernel_size=1, stride=1, padding=0)
+        self.vis = vis
+        self.__dict__['_pool'] = MaxPool3s2()                     # parameter-free, outside the state dict
+
+    accumulates, folds_pooled, reduction = False, False, 1       # three inputs: backward(dout) returns the list of their gradients
+
+    def invalidate(self):
+        for m in self.children():
+            if hasattr(m, 'invalidate'):
+                m.invalidate()
+
+    def _resizers(self):
+        """Per input: (the modules that bring it to this level - None: the input itself -, the factor log2 it is read at)."""
+        if self.level == 0:
+            return [(None, 0), ((self.stride_level_1,), 0), ((self._pool, self.stride_level_2), 0)]
+        if self.level == 1:
+            return [((self.compress_level_0,), 1), (None, 0), ((self.stride_level_2,), 0)]
+        return [((self.compress_level_0,), 2), ((self.compress_level_1,), 1), (None, 0)]
+
+    def _weight_map(self, conv, r, up):
+        """weight_level_i at the resolution `r` is stored at; in training the running variance gets the unbiased correction of the replicated map."""
+        v = conv(r)
+        if self.training and up:
+            bn, rstd = conv.bn, conv.__dict__['_ctx'][3]
+            world = ops.SYNC_BN.get_world_size(ops.SYNC_BN_GROUP) if ops.SYNC_BN is not None else 1
+            nl = v.shape[0] * v.shape[1] * v.shape[2] * world
+            nh = nl << (2 * up)
+            with torch.no_grad():                                 # the kernel used nl / (nl - 1); var_biased = 1 / rstd^2 - eps
+                bn.running_var.add_((1.0 / (rstd[:bn.num_features] * rstd[:bn.num_features]) - bn.eps) *
+                                    (bn.momentum * (nh / (nh - 1) - (nl / (nl - 1) if nl > 1 else 1.0))))
+        return v
+
+    def forward(self, x_level_0, x_level_1, x_level_2):
+        xs = (x_level_0, x_level_1, x_level_2)
+        w, b = self.weight_levels.weight.detach(), self.weight_levels.bias.detach()
+        if not w.is_cuda:
+            raise RuntimeError('somi_amd ASFF runs on the MI355X only (no CPU fallback)')
+        self._pool.train(self.training)
+        rs, ups = [], []
+        for x, c, (mods, up) in zip(xs, self.dim, self._resizers()):
+            if x.up or x.c != c:
+                raise RuntimeError(f'ASFF level {self.level}: the inputs are real maps of {self.dim} channels (P5, P4, P3), got {x.c} (up={x.up})')
+            for m in mods or ():
+                x = m(x)
+            rs.append(x)
+            ups.append(up)
+        vs = [self._weight_map(conv, r, up) for conv, r, up in zip((self.weight_level_0, self.weight_level_1, self.weight_level_2), rs, ups)]
+        B, H, W = rs[0].shape[0], rs[0].shape[1] << ups[0], rs[0].shape[2] << ups[0]
+        fused = new_act(rs[0].t, H, W, self.inter_dim)
+        r = ops.asff_fuse([(a.t, a.coff) for a in rs], [(a.t, a.coff) for a in vs], ups, ups, w.view(3, 48), b, self.inter_dim, out=fused.t,
+                          weights=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (rs, vs, ups, r[1])
+        return self.expand(fused)
+
+    def backward(self, dout, dx_out=None, accumulate=False):
+        """-> the gradients of (x_level_0, x_level_1, x_level_2).  dx_out: three entries, each None (a tensor of its own) or a whole padded contiguous
+        Act the gradient is written into, or added to with `accumulate`."""
+        rs, vs, ups, p = self.__dict__.pop('_ctx')
+        dx_out = (None, None, None) if dx_out is None else dx_out
+        dfused = self.expand.backward(dout)
+        res = self._resizers()
+        direct = [mods is None for mods, _ in res]
+        # the source that IS an input takes its gradient straight in the caller's tensor; the others get low-resolution tensors of their own
+        drs = [(dx_out[i].t, dx_out[i].coff) if direct[i] and dx_out[i] is not None else None for i in range(3)]
+        (dw, db), fin = _grad_targets(self.weight_levels.weight, self.weight_levels.bias)
+        drt, dvt = ops.asff_fuse_backward(dfused.t, [(a.t, a.coff) for a in rs], [(a.t, a.coff) for a in vs], ups, ups,
+                                          self.weight_levels.weight.detach().view(3, 48), self.weight_levels.bias.detach(), p, self.inter_dim,
+                                          dw.view(3, 48), db, do_coff=dfused.coff, drs=drs,
+                                          accumulate=[accumulate and d is not None for d in drs])
+        fin()
+        outs = []
+        for i, conv in enumerate((self.weight_level_0, self.weight_level_1, self.weight_level_2)):
+            dr = Act(drt[i], drs[i][1] if drs[i] is not None else 0, self.inter_dim)
+            conv.backward(Act(dvt[i], 0, 16), dx_out=dr, accumulate=True)       # the weight map's share joins the source's gradient
+            mods = res[i][0]
+            if mods is None:
+                outs.append(dr)
+                continue
+            for m in reversed(mods[1:]):
+                dr = m.backward(dr)
+            outs.append(mods[0].backward(dr, dx_out=dx_out[i], accumulate=accumulate and dx_out[i] is not None))
+        return outs
+
+
+class ASFF_Detect(Detect):
+    """The stock anchor head behind three ASFF blocks (models/yolo.py:172-184).  The reference rewrites its input list in place while it walks it, so
+    with x = [P5, P4, P3]:  f0 = asff0(P5, P4, P3),  f1 = asff1(f0, P4, P3),  f2 = asff2(f0, f1, P3)  - later levels fuse the already fused coarser
+    maps - and Detect runs on [f2, f1, f0].  Reproduced as it is.  backward runs the chain in reverse: every ASFF adds its input gradients into the
+    tensors the later consumers already wrote."""
+
+    def __init__(self, nc=80, anchors=(), ch=(), inplace=False):
+        if len(ch) != 3 or tuple(ch) != (128, 256, 512):
+            raise NotImplementedError(f'ASFF_Detect is built for three levels of (128, 256, 512) channels - the reference hard-codes ASFF.dim = '
+                                      f'[512, 256, 128] (yolov5s width) - got {len(ch)} levels of {tuple(ch)} channels')
+        super().__init__(nc, anchors, ch, inplace)
+        if self.nl != 3:
+            raise NotImplementedError(f'ASFF_Detect is built for three levels of (128, 256, 512) channels, got {self.nl} anchor rows')
+        self.asffs = nn.ModuleList(ASFF(i) for i in range(self.nl))
+
+    def invalidate(self):
+        super().invalidate()
+        for m in self.asffs.modules():
+            if m is not self.asffs and hasattr(m, 'invalidate'):
+                m.invalidate()
+
+    def forward(self, xs):
+        x = list(xs)[::-1]
+        for i in range(self.nl):
+            x[i] = self.asffs[i](*x)
+        return super().forward(x[::-1])
+
+    def backward(self, draws):
+        d2, d1, d0 = super().backward(draws)                      # the gradients of f2, f1, f0: whole tensors of their own
+        _, _, dp3 = self.asffs[2].backward(d2, dx_out=(d0, d1, None), accumulate=True)
+        _, dp4, _ = self.asffs[1].backward(d1, dx_out=(d0, None, dp3), accumulate=True)
+        dp5, _, _ = self.asffs[0].backward(d0, dx_out=(None, dp4, dp3), accumulate=True)
+        return [dp3, dp4, dp5]
 
 
 # ================================================================================================ DCNv3 wired into a graph

@@ -8,7 +8,8 @@ section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, C
 of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv), the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
 C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny, yolov5-fpn / -panet / -p6 / -p7): BottleneckCSP,
 nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; the two learned
-drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; and C3STR, the Swin-transformer C3 (C3TR stays outside).
+drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-transformer C3 (C3TR stays outside); and ASFF_Detect, the plain
+Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck).
 """
 import math
 from copy import deepcopy
@@ -31,6 +32,7 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR}        # models/yolo.py:1472-1479
 _REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR')  # models/yolo.py:1487-1492
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
+_HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
 
 
@@ -84,8 +86,8 @@ def parse_model(d, ch):
         elif name == 'Concat':                                    # models/yolo.py:1589-1591
             m = B.Concat
             c2 = sum(ch[x] for x in f)
-        elif name in ('DecoupledDetect', 'Detect'):               # models/yolo.py:1606-1610, 1616-1619
-            m = B.DecoupledDetect if name == 'DecoupledDetect' else B.Detect
+        elif name in _HEADS:                                      # models/yolo.py:1606-1619
+            m = _HEADS[name]
             args.append([ch[x] for x in f])
             if isinstance(args[1], int):
                 args[1] = [list(range(args[1] * 2))] * len(f)
@@ -93,7 +95,7 @@ def parse_model(d, ch):
             raise NotImplementedError(f'module {name!r} is outside the SOMI hot path (SURVEY.md section 8a)')
         if n > 1 and (name not in _CH or isinstance(f, (list, tuple))):
             raise NotImplementedError(f'{n} repeats of {name!r} as an nn.Sequential are not on the path (single-input (c1, c2, ...) modules only)')
-        if name in ('DecoupledDetect', 'Detect') and len(f) > 5:
+        if name in _HEADS and len(f) > 5:
             raise NotImplementedError(f'at most 5 detection levels, got {len(f)}')
         m_ = B.Repeat(*(m(*args) for _ in range(n))) if n > 1 else m(*args)                 # models/yolo.py:1650
         m_.i, m_.f, m_.type = i, f, name
@@ -133,7 +135,7 @@ class Model(nn.Module):
         self.inplace = self.yaml.get('inplace', False)
         det = self.model[-1]
         if not isinstance(det, (B.DecoupledDetect, B.Detect)):
-            raise NotImplementedError('only the DecoupledDetect and plain Detect heads are on the path')
+            raise NotImplementedError('only the DecoupledDetect, plain Detect and ASFF_Detect heads are on the path')
         # the reference probes strides with a 256x256 zero image (models/yolo.py:1197-1216); the graph's strides
         # follow from its stride-2 layers, computed here without a device
         det.stride = torch.tensor(self._probe_strides())
@@ -143,7 +145,7 @@ class Model(nn.Module):
             det.anchors /= det.stride.view(-1, 1, 1)
             self.stride = det.stride
             self._initialize_dh_biases()
-        else:                                                    # models/yolo.py:1196-1207: scaling, then order check
+        else:                                                    # models/yolo.py:1196-1207: scaling, then order check (Detect and ASFF_Detect)
             det.anchors /= det.stride.view(-1, 1, 1)
             self._check_anchor_order(det)
             self.stride = det.stride

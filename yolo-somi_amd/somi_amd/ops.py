@@ -38,7 +38,8 @@ class _timed:
         return False
 
 
-ACT = {'none': 0, None: 0, 'silu': 1, 'gelu': 2, 'relu': 3, 'sigmoid': 4, 'softmax': 5}
+ACT = {'none': 0, None: 0, 'silu': 1, 'gelu': 2, 'relu': 3, 'sigmoid': 4, 'leaky': 5,       # enum somi_act; leaky = LeakyReLU(0.1)
+       'softmax': 5}                # somi_linear_f32 only, which reads 5 as a softmax over its outputs
 
 
 _CONV_WS = {}
@@ -350,6 +351,96 @@ def maxpool2_backward(dy, codes, c, H, W, dy_coff=0, *, stride=2, pad=(0, 0, 0, 
     check(_lib.lib().somi_maxpool2_bwd_nhwc_f32(_ptr(_f32c(dy)), _ptr(codes), _ptr(_f32c(out)), B, H, W, c, dy.shape[3], dy_coff, out.shape[3], dx_coff,
                                                 int(stride), pl, pr, pt, pb, _stream()), 'maxpool2_backward')
     return out
+
+
+def _slice(t, coff):
+    return _lib.Slice(_ptr(_f32c(t)), t.shape[3], coff)
+
+
+def maxpool3s2_out_size(size):
+    """Output size of F.max_pool2d(., 3, stride=2, padding=1), floor mode."""
+    return (size - 1) // 2 + 1
+
+
+def maxpool3s2(x, c, x_coff=0, *, out=None, y_coff=0, codes=False):
+    """F.max_pool2d(., 3, stride=2, padding=1) of slice [x_coff, x_coff + c) of x (B,H,W,cs), the pad an implicit -inf -> out (B,Ho,Wo,*) slice at
+    y_coff.  codes=True (training): -> (out, codes), one byte per pooled element for maxpool3s2_backward."""
+    B, H, W, _ = x.shape
+    Ho, Wo = maxpool3s2_out_size(H), maxpool3s2_out_size(W)
+    if out is None:
+        out = torch.empty(B, Ho, Wo, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise RuntimeError(f'maxpool3s2: output must be ({B}, {Ho}, {Wo}, .), got {tuple(out.shape)}')
+    arg = torch.empty(B * Ho * Wo * c, device=x.device, dtype=torch.uint8) if codes else None
+    check(_lib.lib().somi_maxpool3s2_nhwc_f32(C.byref(_slice(x, x_coff)), C.byref(_slice(out, y_coff)), _ptr(arg), B, H, W, c, _stream()), 'maxpool3s2')
+    return (out, arg) if codes else out
+
+
+def maxpool3s2_backward(dy, codes, c, H, W, dy_coff=0, *, out=None, dx_coff=0):
+    """dx (B,H,W,*) slice at dx_coff = the gradient of maxpool3s2's input, written (not added): every element gathers the windows whose code points at it."""
+    B = dy.shape[0]
+    Ho, Wo = maxpool3s2_out_size(H), maxpool3s2_out_size(W)
+    if out is None:
+        out = torch.empty(B, H, W, c, device=dy.device, dtype=torch.float32)
+    if tuple(dy.shape[:3]) != (B, Ho, Wo) or tuple(out.shape[:3]) != (B, H, W) or codes.dtype != torch.uint8 or codes.numel() != B * Ho * Wo * c:
+        raise RuntimeError(f'maxpool3s2_backward: dy must be ({B}, {Ho}, {Wo}, .), dx ({B}, {H}, {W}, .), codes {B * Ho * Wo * c} bytes')
+    check(_lib.lib().somi_maxpool3s2_bwd_nhwc_f32(C.byref(_slice(dy, dy_coff)), _ptr(codes), C.byref(_slice(out, dx_coff)), B, H, W, c, _stream()),
+          'maxpool3s2_backward')
+    return out
+
+
+def _asff_desc(rs, vs, r_ups, v_ups, w, bias, c, what):
+    """The descriptor of both fusion launches.  rs / vs: three (tensor, channel offset) each; -> (descriptor, (B, H, W))."""
+    if tuple(w.shape) != (3, 48) or tuple(bias.shape) != (3,):
+        raise RuntimeError(f'{what}: the weight_levels conv is (3, 48) with 3 biases, got {tuple(w.shape)} and {tuple(bias.shape)}')
+    B = rs[0][0].shape[0]
+    H, W = rs[0][0].shape[1] << r_ups[0], rs[0][0].shape[2] << r_ups[0]
+    for (t, _), up in list(zip(rs, r_ups)) + list(zip(vs, v_ups)):
+        if up not in (0, 1, 2) or H % (1 << up) or W % (1 << up) or tuple(t.shape[:3]) != (B, H >> up, W >> up):
+            raise RuntimeError(f'{what}: an input read at up={up} must be ({B}, {H >> up}, {W >> up}, .), got {tuple(t.shape)}')
+    d = _lib.AsffDesc()
+    for i in range(3):
+        d.r[i], d.v[i] = _slice(*rs[i]), _slice(*vs[i])
+        d.r_up[i], d.v_up[i] = r_ups[i], v_ups[i]
+    d.w, d.bias = _ptr(_f32c(w)), _ptr(_f32c(bias))
+    d.B, d.H, d.W, d.C = B, H, W, c
+    return d, (B, H, W)
+
+
+def asff_fuse(rs, vs, r_ups, v_ups, w, bias, c, *, out=None, o_coff=0, weights=False):
+    """ASFF's fusion: fused = sum_i softmax(w . cat(v) + bias)_i * r_i per output pixel; source r_i = rs[i] = (tensor, channel offset), c channels, and
+    weight map v_i = vs[i], 16 channels, are read at (h >> up, w >> up) with their own up.  -> out (B,H,W,*) slice at o_coff; weights=True (training):
+    -> (out, p) with p (B,H,W,3) the softmax, all asff_fuse_backward needs beyond the inputs."""
+    d, (B, H, W) = _asff_desc(rs, vs, r_ups, v_ups, w, bias, c, 'asff_fuse')
+    if out is None:
+        out = torch.empty(B, H, W, c, device=w.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'asff_fuse: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    p = torch.empty(B, H, W, 3, device=w.device, dtype=torch.float32) if weights else None
+    d.out, d.p = _slice(out, o_coff), _ptr(p)
+    check(_lib.lib().somi_asff_fuse_nhwc_f32(C.byref(d), _stream()), 'asff_fuse')
+    return (out, p) if weights else out
+
+
+def asff_fuse_backward(dout, rs, vs, r_ups, v_ups, w, bias, p, c, dw, db, *, do_coff=0, drs=(None, None, None), accumulate=(False, False, False),
+                       dvs=None):
+    """From dout = d fused (slice at do_coff) and the forward's inputs and p: the source gradients dr_i in the sources' own (low-resolution)
+    layouts - drs[i] = (tensor, channel offset) to write into, or add to with accumulate[i]; a tensor of its own when None -, the weight maps'
+    gradients dv_i likewise (written), and dw (3, 48) / db (3) ACCUMULATED.  -> ([dr_i tensors], [dv_i tensors])."""
+    d, (B, H, W) = _asff_desc(rs, vs, r_ups, v_ups, w, bias, c, 'asff_fuse_backward')
+    if tuple(dout.shape[:3]) != (B, H, W) or tuple(p.shape) != (B, H, W, 3):
+        raise RuntimeError(f'asff_fuse_backward: dout must be ({B}, {H}, {W}, .) and p ({B}, {H}, {W}, 3)')
+    dev = dout.device
+    drs = [(torch.empty(*rs[i][0].shape[:3], c, device=dev, dtype=torch.float32), 0) if drs[i] is None else drs[i] for i in range(3)]
+    dvs = [(torch.empty(*vs[i][0].shape[:3], 16, device=dev, dtype=torch.float32), 0) for i in range(3)] if dvs is None else dvs
+    for i in range(3):
+        if tuple(drs[i][0].shape[:3]) != tuple(rs[i][0].shape[:3]) or tuple(dvs[i][0].shape[:3]) != tuple(vs[i][0].shape[:3]):
+            raise RuntimeError('asff_fuse_backward: a gradient tensor does not have its input\'s map size')
+        d.dr[i], d.dv[i], d.dr_accumulate[i] = _slice(*drs[i]), _slice(*dvs[i]), int(accumulate[i])
+    ws = torch.empty(_lib.lib().somi_asff_fuse_bwd_workspace_floats(B, H, W), device=dev, dtype=torch.float32)
+    d.out, d.p, d.dw, d.db, d.workspace, d.workspace_floats = _slice(dout, do_coff), _ptr(_f32c(p)), _ptr(_f32c(dw)), _ptr(_f32c(db)), _ptr(ws), ws.numel()
+    check(_lib.lib().somi_asff_fuse_bwd_nhwc_f32(C.byref(d), _stream()), 'asff_fuse_backward')
+    return [t for t, _ in drs], [t for t, _ in dvs]
 
 
 def _spp_k(k):
