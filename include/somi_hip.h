@@ -53,10 +53,12 @@ size_t somi_sizeof_desc(int which);
  */
 enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_ACT_RELU = 3, SOMI_ACT_SIGMOID = 4,
                 SOMI_ACT_LEAKY = 5 /* LeakyReLU(0.1), add_conv of models/common.py:5322-5343: the dense conv epilogue, somi_chan_affine_act_* and the
-                                      somi_bn_act_backward_* family take it; somi_linear_f32 keeps reading 5 as its softmax */ };
+                                      somi_bn_act_backward_* family take it; somi_linear_f32 keeps reading 5 as its softmax */,
+                SOMI_ACT_HSWISH = 6 /* h_swish, x * relu6(x + 3) / 6 (models/common.py:1381-1398), the activation between bn1 and conv_h / conv_w of
+                                       coordinate attention: taken wherever SOMI_ACT_LEAKY is */ };
 
 /* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
- * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc).  An input slice is only read. */
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc).  An input slice is only read. */
 typedef struct somi_slice {
     float *p;
     int32_t cs, coff;
@@ -346,6 +348,46 @@ size_t somi_asff_desc_bytes(void);   /* sizeof(somi_asff_desc) as the library wa
 size_t somi_asff_fuse_bwd_workspace_floats(int B, int H, int W);
 int somi_asff_fuse_nhwc_f32(const somi_asff_desc *d, somi_stream_t stream);
 int somi_asff_fuse_bwd_nhwc_f32(const somi_asff_desc *d, somi_stream_t stream);
+
+/* Coordinate attention (CoorAttention, models/common.py:1399-1450; CABottleneck, :4884-4922; coordatt.hip): the four passes over the map
+ * x (B,H,W,.) that the attention makes; the small tensors between them (conv1, bn1, h-swish, conv_h / conv_w, sigmoid, B * (H + W) rows) run on
+ * the conv and BatchNorm entries.  Every tensor is a channel slice of width C (a multiple of 4).  A "row tensor" (a_h, a_w, r_h, r_w) is a
+ * (B, rows, .) tensor with `*_rows` rows per image: [b][h] is read or written for h < H (a_h, r_h), [b][w] for w < W (a_w, r_w).  With rows = H
+ * and W they are the plain (B,H,C) and (B,W,C) tensors; with rows = H + W and the second pointer advanced by H rows they are the two halves of
+ * one tensor in `pool`'s layout - how the blocks run conv_h and conv_w as one 1x1 conv over conv1's output.
+ * means     (somi_coordatt_means_nhwc_f32):     pool (B, H + W, .): rows [0,H) = the mean over W per (b,h,c), rows [H,H+W) = the mean over H per
+ *           (b,w,c) - the reference's cat([x_h, x_w.permute], dim=2), so conv1 runs on it as a (B, H + W, 1, C) map.  One pass over x.
+ * apply     (somi_coordatt_apply_nhwc_f32):     y = [res +] x * a_h[b,h,c] * a_w[b,w,c], the gates already sigmoided; res (optional) is the
+ *           bottleneck's shortcut.  No expanded gate and no x * a_w product reaches memory.
+ * bwd gates (somi_coordatt_bwd_gates_nhwc_f32): y holds dout (read).  r_h[b,h,c] = sum_w dout x a_w, r_w[b,w,c] = sum_h dout x a_h, WRITTEN;
+ *           dout and x are read once for both.
+ * bwd input (somi_coordatt_bwd_input_nhwc_f32): y holds dout (read), r_h / r_w the gradients of the two means (read: the two halves of conv1's
+ *           input gradient).  dx = dout a_h a_w + r_h[b,h,c] / W + r_w[b,w,c] / H, written, or added to what dx holds with `accumulate`; x is
+ *           not read.
+ * So forward and backward each make two passes over the (B,H,W,C) tensors.  means and bwd gates sum through per-workgroup partials in
+ * `workspace` (somi_coordatt_workspace_floats(B, H, W, C) floats, 16-byte aligned) and a fixed-order second stage.  No float atomics: two
+ * launches are bit-identical. */
+typedef struct somi_coordatt_desc {
+    somi_slice x;              /* the attended map x1 (B,H,W,.), read (unused by bwd input) */
+    somi_slice y;              /* apply: the output, written; both backward passes: dout, read; unused by means */
+    somi_slice res;            /* apply only; res.p NULL: no shortcut */
+    somi_slice pool;           /* means only: (B, H + W, .), written */
+    somi_slice a_h, a_w;       /* the gates, read (all but means) */
+    int32_t a_h_rows, a_w_rows;
+    somi_slice r_h, r_w;       /* bwd gates: da_h, da_w, written; bwd input: gh, gw, read */
+    int32_t r_h_rows, r_w_rows;
+    somi_slice dx;             /* bwd input only */
+    int32_t accumulate;        /* bwd input: add to what dx holds */
+    int32_t B, H, W, C;
+    float *workspace;          /* means and bwd gates */
+    uint64_t workspace_floats;
+} somi_coordatt_desc;
+size_t somi_coordatt_desc_bytes(void);   /* sizeof(somi_coordatt_desc) as the library was compiled: lets a binding check its mirror */
+size_t somi_coordatt_workspace_floats(int B, int H, int W, int C);
+int somi_coordatt_means_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
+int somi_coordatt_apply_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
+int somi_coordatt_bwd_gates_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
+int somi_coordatt_bwd_input_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
 
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed

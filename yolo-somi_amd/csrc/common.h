@@ -92,6 +92,7 @@ __device__ __forceinline__ float apply_act(float v) {
     else if constexpr (ACT == SOMI_ACT_RELU) return fmaxf(v, 0.0f);
     else if constexpr (ACT == SOMI_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
     else if constexpr (ACT == SOMI_ACT_LEAKY) return v > 0.0f ? v : 0.1f * v;
+    else if constexpr (ACT == SOMI_ACT_HSWISH) return v * fminf(fmaxf(v + 3.0f, 0.0f), 6.0f) * (1.0f / 6.0f);
     else return v;
 }
 
@@ -102,6 +103,7 @@ __device__ __forceinline__ float apply_act_rt(float v, int act) {
         case SOMI_ACT_RELU: return apply_act<SOMI_ACT_RELU>(v);
         case SOMI_ACT_SIGMOID: return apply_act<SOMI_ACT_SIGMOID>(v);
         case SOMI_ACT_LEAKY: return apply_act<SOMI_ACT_LEAKY>(v);
+        case SOMI_ACT_HSWISH: return apply_act<SOMI_ACT_HSWISH>(v);
         default: return v;
     }
 }

@@ -748,7 +748,7 @@ static int conv_launch(const somi_conv_desc *dp, somi_stream_t stream, int dgrad
                         {dgrad ? "accumulate" : "residual", d.residual, d.res_cs, d.res_coff, d.Cout, kOptional},
                         {"residual2", d.residual2, d.res2_cs, d.res2_coff, d.Cout, kOptional});
     SOMI_REQUIRE(!d.post_scale == !d.post_shift, SOMI_EINVAL, "conv: post_scale and post_shift go together");
-    SOMI_REQUIRE(d.act >= SOMI_ACT_NONE && d.act <= SOMI_ACT_LEAKY, SOMI_EINVAL, "conv: unknown activation %d", d.act);
+    SOMI_REQUIRE(d.act >= SOMI_ACT_NONE && d.act <= SOMI_ACT_HSWISH, SOMI_EINVAL, "conv: unknown activation %d", d.act);
     SOMI_REQUIRE((long)d.B * d.Ho * d.Wo < (1L << 31), SOMI_EINVAL, "conv: too many output pixels");
     if (d.a_chan_scale) SOMI_REQUIRE(aligned16(d.a_chan_scale), SOMI_EINVAL, "conv: a_chan_scale must be 16 B aligned");
     SOMI_REQUIRE((!d.bias || aligned16(d.bias)) && (!d.post_scale || (aligned16(d.post_scale) && aligned16(d.post_shift))),

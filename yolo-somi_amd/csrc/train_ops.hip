@@ -31,6 +31,7 @@ __device__ __forceinline__ float act_grad(float u, int act) {
         case SOMI_ACT_RELU: return u > 0.f ? 1.f : 0.f;
         case SOMI_ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-u)); return s * (1.f - s); }
         case SOMI_ACT_LEAKY: return u > 0.f ? 1.f : 0.1f;
+        case SOMI_ACT_HSWISH: return u <= -3.f ? 0.f : (u >= 3.f ? 1.f : (2.f * u + 3.f) * (1.f / 6.f));
         default: return 1.f;
     }
 }

@@ -61,6 +61,14 @@ class AsffDesc(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
 
 
+class CoordAttDesc(C.Structure):
+    """struct somi_coordatt_desc (include/somi_hip.h)."""
+    _fields_ = [('x', Slice), ('y', Slice), ('res', Slice), ('pool', Slice), ('a_h', Slice), ('a_w', Slice), ('a_h_rows', C.c_int32),
+                ('a_w_rows', C.c_int32), ('r_h', Slice), ('r_w', Slice), ('r_h_rows', C.c_int32), ('r_w_rows', C.c_int32), ('dx', Slice),
+                ('accumulate', C.c_int32), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('workspace', C.c_void_p),
+                ('workspace_floats', C.c_uint64)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -210,6 +218,12 @@ SIGNATURES = {
     'somi_asff_fuse_bwd_workspace_floats': (Z, [I, I, I]),
     'somi_asff_fuse_nhwc_f32': (I, [C.POINTER(AsffDesc), S]),
     'somi_asff_fuse_bwd_nhwc_f32': (I, [C.POINTER(AsffDesc), S]),
+    'somi_coordatt_desc_bytes': (Z, []),
+    'somi_coordatt_workspace_floats': (Z, [I, I, I, I]),
+    'somi_coordatt_means_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
+    'somi_coordatt_apply_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
+    'somi_coordatt_bwd_gates_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
+    'somi_coordatt_bwd_input_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
     'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
@@ -259,7 +273,8 @@ def lib():
         if L.somi_abi_version() != ABI_VERSION and not lax:
             raise RuntimeError('libsomi_hip.so ABI version mismatch')
         if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)
-                        or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)):
+                        or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)
+                        or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

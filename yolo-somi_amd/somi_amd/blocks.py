@@ -2137,6 +2137,175 @@ class C3STR(C3):
         return dx
 
 
+class _CoordGates(_Packed):
+    """The coordinate attention both CoorAttention and CABottleneck carry (models/common.py:1425-1450, 4902-4922), on the children `conv1`, `bn1`,
+    `conv_h`, `conv_w` of the class that mixes this in:  out = [res +] x1 * a_h[b,h,c] * a_w[b,w,c]  with
+    a_h, a_w = sigmoid(conv_h / conv_w (h_swish(bn1(conv1(cat(mean over W, mean over H)))))).
+    Two passes over x1 forward (ops.coordatt_means, ops.coordatt_apply) and two over (dout, x1) backward (ops.coordatt_backward_gates,
+    ops.coordatt_backward_input).  The small tensors in between have B * (H + W) rows: conv1 runs on the means as a (B, H + W, 1, C) map, bn1
+    through the one BatchNorm train path with h-swish as its activation (eval: folded into conv1, h-swish in the conv epilogue), and conv_h and
+    conv_w as ONE 1x1 conv with their weights stacked, (B, H + W, 1, 2C): a_h is rows [0, H) of channels [0, C), a_w rows [H, H + W) of
+    channels [C, 2C).  The other two quadrants are computed and never read; their gradient is zero."""
+
+    def _init_gates(self, c1, c2, mip):
+        self.conv1 = nn.Conv2d(c1, mip, kernel_size=1, stride=1, padding=0)
+        self.bn1 = nn.BatchNorm2d(mip)
+        self.conv_h = nn.Conv2d(mip, c2, kernel_size=1, stride=1, padding=0)
+        self.conv_w = nn.Conv2d(mip, c2, kernel_size=1, stride=1, padding=0)
+
+    def _pack_params(self):
+        return [*self.conv1.parameters(), *self.bn1.parameters(), *self.conv_h.parameters(), *self.conv_w.parameters()]
+
+    def _pack(self, dev):
+        c, mip = self.conv_h.out_channels, self.conv1.out_channels
+        mp = pad4(mip)
+        wg = torch.cat([self.conv_h.weight, self.conv_w.weight]).detach().float()
+        bg = torch.cat([self.conv_h.bias, self.conv_w.bias]).detach().float().to(dev)
+        pk = dict(wg=pack_conv_weight(wg, cin_pad=mp).to(dev), bg=bg)
+        if not self.training:                                    # bn1 folded into conv1 (utils/torch_utils.py:202-222)
+            w1, b1 = _fold_conv_bn(self.conv1, self.bn1)
+            pk['w1'], pk['b1'] = pack_conv_weight(w1, cin_pad=c, cout_pad=mp).to(dev), torch.zeros(mp, device=dev)
+            pk['b1'][:mip] = b1.to(dev)
+            return pk
+        w1 = self.conv1.weight.detach().float()
+        pk['w1'], pk['b1'] = pack_conv_weight(w1, cin_pad=c, cout_pad=mp).to(dev), torch.zeros(mp, device=dev)
+        pk['b1'][:mip] = self.conv1.bias.detach().float().to(dev)
+        pk['wt1'] = pack_dgrad_weight(w1, cin_pad=c, cout_pad=mp).to(dev)
+        pk['wtg'] = pack_dgrad_weight(wg, cin_pad=mp, cout_pad=2 * c).to(dev)
+        pk['one'], pk['zero'] = torch.ones(2 * c, device=dev), torch.zeros(2 * c, device=dev)
+        pk.update(_bn_vectors(self.bn1, dev, mp))
+        return pk
+
+    def _gates_forward(self, x1, res, out):
+        """x1: the attended map (Act, c % 4 == 0); res: the shortcut (Act) or None; out: the Act to write (a new one when None)."""
+        c, mip = self.conv_h.out_channels, self.conv1.out_channels
+        if x1.c != c or self.conv1.in_channels != c:
+            raise RuntimeError(f'coordinate attention over {c} channels got a map of {x1.c} (conv1 reads {self.conv1.in_channels})')
+        if c % 4 or x1.up:
+            raise NotImplementedError('coordinate attention needs a real tensor with a channel count that is a multiple of 4')
+        if not x1.t.is_cuda:
+            raise RuntimeError('somi_amd coordinate attention runs on the MI355X only (no CPU fallback)')
+        pk = self._packed(x1.t.device)
+        B, H, W, _ = x1.shape
+        mp = pad4(mip)
+        pool = ops.coordatt_means(x1.t, c, x1.coff)
+        if out is None:
+            out = new_act(x1.t, H, W, c)
+            if out.t.shape[3] != c:
+                out.t.zero_()                                     # pad channels of a tensor of its own
+        conv = dict(kh=1, kw=1, stride=1, pad=0)
+        if not self.training:
+            t = ops.conv2d_nhwc(pool, pk['w1'], pk['b1'], act='hswish', cin=c, cout=mp, alg_cout=mip, **conv)
+            g = ops.conv2d_nhwc(t, pk['wg'], pk['bg'], act='sigmoid', cin=mp, cout=2 * c, alg_cin=mip, **conv)
+        else:
+            y1 = ops.conv2d_nhwc(pool, pk['w1'], pk['b1'], act='none', cin=c, cout=mp, alg_cout=mip, **conv)
+            st, commit = _bn_train(self.bn1, mp, y1, vec=pk)
+            commit()
+            t = ops.chan_affine_act(y1, mp, 0, st[2], st[3], 'hswish', 0, torch.empty_like(y1))
+            pre = ops.conv2d_nhwc(t, pk['wg'], pk['bg'], act='none', cin=mp, cout=2 * c, alg_cin=mip, **conv)
+            g = ops.chan_affine_act(pre, 2 * c, 0, pk['one'], pk['zero'], 'sigmoid', 0, torch.empty_like(pre))
+            self.__dict__['_gctx'] = (x1, pool, y1, st, t, pre, g, pk)
+        ops.coordatt_apply(x1.t, (g, 0, 0), (g, c, H), c, x1.coff, res=None if res is None else res.t, res_coff=0 if res is None else res.coff,
+                           out=out.t, o_coff=out.coff)
+        return Act(out.t, out.coff, c)
+
+    def _gates_backward(self, dout, dx_out=None, accumulate=False):
+        """dout: the gradient of the product x1 * a_h * a_w (the shortcut's share is the caller's).  -> the gradient of x1 as an Act: a whole padded
+        tensor of its own (pad channels zero) when dx_out is None, else written into dx_out, added to it with `accumulate`.  The parameter
+        gradients of conv1, bn1, conv_h and conv_w are accumulated into .grad."""
+        x1, pool, y1, st, t, pre, g, pk = self.__dict__.pop('_gctx')
+        c, mip = self.conv_h.out_channels, self.conv1.out_channels
+        mp = pad4(mip)
+        B, H, W, _ = x1.shape
+        dev = x1.t.device
+        conv = dict(kh=1, kw=1, stride=1, pad=0)
+        a_h, a_w = (g, 0, 0), (g, c, H)
+        dg = torch.zeros_like(g)                                  # the two quadrants nobody reads keep a zero gradient
+        ops.coordatt_backward_gates(dout.t, x1.t, a_h, a_w, c, dout.coff, x1.coff, da_h=(dg, 0, 0), da_w=(dg, c, H))
+        # through the sigmoid: a BatchNorm-activation backward with frozen unit statistics; its dbeta is the stacked bias gradient
+        dbg = torch.zeros(2 * c, device=dev)
+        ops.bn_act_backward(dg, 0, pre, 0, 2 * c, pk['zero'], pk['one'], pk['one'], pk['zero'], 'sigmoid', 0, False, dg, 0, None, dbg)
+        _acc_grad(self.conv_h.bias, dbg[:c])
+        _acc_grad(self.conv_w.bias, dbg[c:])
+        dwg = ops.conv2d_wgrad_nhwc(t, dg, cin=mp, cout=2 * c, **conv).view(2 * c, mp)[:, :mip]
+        _acc_grad(self.conv_h.weight, dwg[:c].reshape(c, mip, 1, 1))
+        _acc_grad(self.conv_w.weight, dwg[c:].reshape(c, mip, 1, 1))
+        dt = ops.conv2d_dgrad_nhwc(dg, pk['wtg'], B=B, H=H + W, W=1, cin=mp, cout=2 * c, **conv)
+        dy1 = _bn_backward(self.bn1, dt, 0, y1, st, 'hswish', torch.empty_like(y1), mp)
+        db1 = torch.zeros(mp, device=dev)
+        ops.chan_sum_(dy1, mp, 0, db1)
+        _acc_grad(self.conv1.bias, db1[:mip])
+        dw1 = ops.conv2d_wgrad_nhwc(pool, dy1, cin=c, cout=mp, **conv).view(mp, c)[:mip]
+        _acc_grad(self.conv1.weight, dw1.reshape(mip, c, 1, 1))
+        dpool = ops.conv2d_dgrad_nhwc(dy1, pk['wt1'], B=B, H=H + W, W=1, cin=c, cout=mp, **conv)
+        if dx_out is None:
+            dx_out = new_act(x1.t, H, W, c)
+            if dx_out.t.shape[3] != c:
+                dx_out.t.zero_()
+            accumulate = False
+        ops.coordatt_backward_input(dout.t, a_h, a_w, (dpool, 0, 0), (dpool, 0, H), c, dout.coff, out=dx_out.t, dx_coff=dx_out.coff,
+                                    accumulate=accumulate)
+        return dx_out
+
+
+class CoorAttention(_CoordGates):
+    """Coordinate attention as a layer of its own (models/common.py:1399-1450): out = x * a_w * a_h, every pixel gated by its row and by its column."""
+
+    def __init__(self, inp, oup, reduction=32):
+        super().__init__()
+        if inp != oup:
+            raise NotImplementedError(f'CoorAttention({inp}, {oup}): the gates have oup channels and multiply the inp-channel input; the '
+                                      f'reference\'s product does not broadcast either unless inp == oup')
+        self._init_gates(inp, oup, max(8, inp // reduction))
+
+    accumulates, folds_pooled, reduction = False, False, 1       # like Bottleneck: takes dx_out / accumulate, not walked that way
+
+    def forward(self, x, out=None):
+        return self._gates_forward(x, None, out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        return self._gates_backward(dout, dx_out, accumulate)
+
+
+class CABottleneck(_CoordGates):
+    """cv1 (1x1) -> cv2 (3x3) -> coordinate attention (+x) (models/common.py:4884-4922); the shortcut rides the attention's apply pass (forward)
+    and cv1's dgrad epilogue (backward).  mip comes from c1, as in the reference."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5, ratio=32):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_, c2, 3, 1, g=g)
+        self.add = shortcut and c1 == c2
+        self._init_gates(c1, c2, max(8, c1 // ratio))             # conv1 reads cv2's c2-channel output with c1 inputs: c1 == c2, or forward raises
+
+    accumulates, folds_pooled, reduction = False, False, 1       # like Bottleneck: takes dx_out / accumulate, not walked that way
+
+    def forward(self, x, out=None):
+        return self._gates_forward(self.cv2(self.cv1(x)), x if self.add else None, out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = self.cv2.backward(self._gates_backward(dout))
+        c1 = self.cv1.conv.in_channels
+        fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0
+        dx = self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if self.add and not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class C3_CA(C3):
+    """C3 whose bottlenecks are CABottleneck(c_, c_, shortcut, g, e=1.0) (models/common.py:4925-4931).  The reference's parser does not repeat
+    it inside (models/yolo.py:1487-1490): a yaml row with n > 1 is a Repeat of n C3_CA blocks with one bottleneck each."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(CABottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
+
+    accumulates, folds_pooled, reduction = False, False, 1       # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
+
+
 class Concat(nn.Module):
     """torch.cat(x, 1) (models/common.py:2085-2097) of NHWC channel slices; an input that is a 2x nearest-upsampled view
     (`Upsample` only sets a flag) is expanded by the same copy.  Backward hands out slices of the incoming gradient (no copy) and

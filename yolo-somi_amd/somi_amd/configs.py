@@ -160,6 +160,26 @@ def yolov5_swin_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     return cfg
 
 
+def yolov5_ca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
+    """yolov5s 6.0 with coordinate attention (models/common.py:1399-1450, 4884-4931).  The reference registers C3_CA and CoorAttention in its
+    parser (models/yolo.py:1477, 1630-1634) but ships no yaml that names them.  where='c3': the four backbone C3 rows become C3_CA - which the
+    reference does not repeat inside, so the rows with n > 1 are n whole blocks in a row; where='row': a [-1, 1, 'CoorAttention', [1024]] row
+    behind SPPF, the head's absolute indices one up."""
+    if where not in ('c3', 'row'):
+        raise ValueError(f"where must be 'c3' or 'row', got {where!r}")
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    if where == 'c3':
+        for row in cfg['backbone']:
+            if row[2] == 'C3':
+                row[2] = 'C3_CA'
+        return cfg
+    cfg['backbone'].append([-1, 1, 'CoorAttention', [1024]])
+    for row in cfg['head']:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+    return cfg
+
+
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
     C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""

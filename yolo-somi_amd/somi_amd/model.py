@@ -8,8 +8,9 @@ section 8a, the stock YOLOv5 set north_star names (Bottleneck, C3, SPP, Focus, C
 of models/hub/yolov5s-ghost.yaml (GhostConv, GhostBottleneck, C3Ghost, DWConv), the YOLOv10 set of models/hub/yolov10.yaml (C2f, SCDown,
 C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny, yolov5-fpn / -panet / -p6 / -p7): BottleneckCSP,
 nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; the two learned
-drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-transformer C3 (C3TR stays outside); and ASFF_Detect, the plain
-Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck).
+drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-transformer C3 (C3TR stays outside); ASFF_Detect, the plain
+Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck); and coordinate
+attention, as the C3_CA block and as a CoorAttention row of its own.
 """
 import math
 from copy import deepcopy
@@ -29,8 +30,10 @@ def make_divisible(x, divisor):
 _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bottleneck': B.Bottleneck, 'C3': B.C3, 'SPP': B.SPP,
        'Focus': B.Focus, 'GhostConv': B.GhostConv, 'GhostBottleneck': B.GhostBottleneck, 'DWConv': B.DWConv,
        'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA,
-       'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR}        # models/yolo.py:1472-1479
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR')  # models/yolo.py:1487-1492
+       'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR,        # models/yolo.py:1472-1479
+       'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention}        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
+# models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
@@ -56,6 +59,9 @@ def parse_model(d, ch):
             if name in _REPEAT_INSIDE:
                 args.insert(2, n)
                 n = 1
+            elif name == 'C3_CA' and n > 1 and c1 != c2:
+                raise NotImplementedError(f'{n} repeats of C3_CA from {c1} to {c2} channels: the reference repeats the whole block with the same '
+                                          f'(c1, c2) (models/yolo.py:1487-1490, 1650), so its second block gets {c2} channels where it expects {c1}')
         elif name == 'ODConv_3rd':
             m = B.ODConv_3rd
             c1, c2 = ch[f], args[0]

@@ -39,6 +39,7 @@ class _timed:
 
 
 ACT = {'none': 0, None: 0, 'silu': 1, 'gelu': 2, 'relu': 3, 'sigmoid': 4, 'leaky': 5,       # enum somi_act; leaky = LeakyReLU(0.1)
+       'hswish': 6,                 # x * relu6(x + 3) / 6
        'softmax': 5}                # somi_linear_f32 only, which reads 5 as a softmax over its outputs
 
 
@@ -441,6 +442,97 @@ def asff_fuse_backward(dout, rs, vs, r_ups, v_ups, w, bias, p, c, dw, db, *, do_
     d.out, d.p, d.dw, d.db, d.workspace, d.workspace_floats = _slice(dout, do_coff), _ptr(_f32c(p)), _ptr(_f32c(dw)), _ptr(_f32c(db)), _ptr(ws), ws.numel()
     check(_lib.lib().somi_asff_fuse_bwd_nhwc_f32(C.byref(d), _stream()), 'asff_fuse_backward')
     return [t for t, _ in drs], [t for t, _ in dvs]
+
+
+def _row_tensor(spec, B, n, what):
+    """A row tensor of the coordinate-attention kernels -> (Slice, rows per image).  spec: a (B, rows, cs) or (B, rows, 1, cs) tensor, or
+    (tensor, channel offset[, first row]): rows [first row, first row + n) of every image are the ones addressed."""
+    t, coff, row0 = (tuple(spec) + (0, 0))[:3] if isinstance(spec, (tuple, list)) else (spec, 0, 0)
+    if t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[2] != 1) or t.shape[0] != B or row0 < 0 or row0 + n > t.shape[1]:
+        raise RuntimeError(f'{what}: a ({B}, >= {row0 + n}, cs) row tensor is expected, got {tuple(t.shape)}')
+    cs = t.shape[-1]
+    return _lib.Slice(_ptr(_f32c(t)) + 4 * row0 * cs, cs, coff), t.shape[1]
+
+
+def _coordatt_desc(B, H, W, c, a_h=None, a_w=None, what='coordatt'):
+    d = _lib.CoordAttDesc()
+    d.B, d.H, d.W, d.C = B, H, W, c
+    if a_h is not None:
+        d.a_h, d.a_h_rows = _row_tensor(a_h, B, H, what + ': a_h')
+        d.a_w, d.a_w_rows = _row_tensor(a_w, B, W, what + ': a_w')
+    return d
+
+
+def _coordatt_workspace(d, dev):
+    ws = torch.empty(max(_lib.lib().somi_coordatt_workspace_floats(d.B, d.H, d.W, d.C), 4), device=dev, dtype=torch.float32)
+    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return ws
+
+
+def coordatt_means(x, c, x_coff=0, *, out=None, o_coff=0):
+    """The two directional means of slice [x_coff, x_coff + c) of x (B,H,W,cs) -> out (B, H + W, 1, *) slice at o_coff: rows [0, H) the mean over W
+    per (b, h, channel), rows [H, H + W) the mean over H per (b, w, channel) - the map coordinate attention's conv1 reads."""
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H + W, 1, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H + W, 1):
+        raise RuntimeError(f'coordatt_means: output must be ({B}, {H + W}, 1, .), got {tuple(out.shape)}')
+    d = _coordatt_desc(B, H, W, c)
+    d.x, d.pool = _slice(x, x_coff), _slice(out, o_coff)
+    ws = _coordatt_workspace(d, x.device)                         # noqa: F841  (alive until the launch is enqueued)
+    check(_lib.lib().somi_coordatt_means_nhwc_f32(C.byref(d), _stream()), 'coordatt_means')
+    return out
+
+
+def coordatt_apply(x, a_h, a_w, c, x_coff=0, *, res=None, res_coff=0, out=None, o_coff=0):
+    """out = [res +] x * a_h[b,h,:] * a_w[b,w,:] over c channels; a_h / a_w: sigmoided gates as row tensors (_row_tensor)."""
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W) or (res is not None and tuple(res.shape[:3]) != (B, H, W)):
+        raise RuntimeError(f'coordatt_apply: output and shortcut must be ({B}, {H}, {W}, .)')
+    d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_apply')
+    d.x, d.y = _slice(x, x_coff), _slice(out, o_coff)
+    if res is not None:
+        d.res = _slice(res, res_coff)
+    check(_lib.lib().somi_coordatt_apply_nhwc_f32(C.byref(d), _stream()), 'coordatt_apply')
+    return out
+
+
+def coordatt_backward_gates(dout, x, a_h, a_w, c, do_coff=0, x_coff=0, *, da_h=None, da_w=None):
+    """da_h[b,h,:] = sum_w dout x a_w and da_w[b,w,:] = sum_h dout x a_h, written into the row tensors da_h / da_w ((B,H,c) and (B,W,c) tensors
+    of their own when None).  -> (da_h tensor, da_w tensor)."""
+    B, H, W, _ = x.shape
+    if tuple(dout.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'coordatt_backward_gates: dout must be ({B}, {H}, {W}, .), got {tuple(dout.shape)}')
+    da_h = torch.empty(B, H, c, device=x.device, dtype=torch.float32) if da_h is None else da_h
+    da_w = torch.empty(B, W, c, device=x.device, dtype=torch.float32) if da_w is None else da_w
+    d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_backward_gates')
+    d.x, d.y = _slice(x, x_coff), _slice(dout, do_coff)
+    d.r_h, d.r_h_rows = _row_tensor(da_h, B, H, 'coordatt_backward_gates: da_h')
+    d.r_w, d.r_w_rows = _row_tensor(da_w, B, W, 'coordatt_backward_gates: da_w')
+    ws = _coordatt_workspace(d, x.device)                         # noqa: F841
+    check(_lib.lib().somi_coordatt_bwd_gates_nhwc_f32(C.byref(d), _stream()), 'coordatt_backward_gates')
+    first = lambda s: s[0] if isinstance(s, (tuple, list)) else s    # noqa: E731
+    return first(da_h), first(da_w)
+
+
+def coordatt_backward_input(dout, a_h, a_w, gh, gw, c, do_coff=0, *, out=None, dx_coff=0, accumulate=False):
+    """dx = dout * a_h * a_w + gh[b,h,:] / W + gw[b,w,:] / H over c channels (gh / gw: the gradients of the two means, row tensors), written into
+    out's slice at dx_coff, or added to it with `accumulate`."""
+    B, H, W, _ = dout.shape
+    if out is None:
+        if accumulate:
+            raise RuntimeError('coordatt_backward_input: accumulate needs the tensor to add to')
+        out = torch.empty(B, H, W, c, device=dout.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'coordatt_backward_input: dx must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_backward_input')
+    d.y, d.dx, d.accumulate = _slice(dout, do_coff), _slice(out, dx_coff), int(accumulate)
+    d.r_h, d.r_h_rows = _row_tensor(gh, B, H, 'coordatt_backward_input: gh')
+    d.r_w, d.r_w_rows = _row_tensor(gw, B, W, 'coordatt_backward_input: gw')
+    check(_lib.lib().somi_coordatt_bwd_input_nhwc_f32(C.byref(d), _stream()), 'coordatt_backward_input')
+    return out
 
 
 def _spp_k(k):
