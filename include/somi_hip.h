@@ -124,6 +124,9 @@ int somi_conv2d_stat_rows(const somi_conv_desc *d);
 /* Data gradient of the convolution whose FORWARD geometry `fwd` describes (x (B,H,W,Cin) -> y (B,Ho,Wo,Cout); the pointer
  * fields of `fwd` are ignored):  dx[b,h,w,ci] = sum_{r,q,co} dy[b,(h+p-r)/s,(w+p-q)/s,co] * W[co][ci][r][q]
  * over the taps for which the divisions are exact and in range (autograd of F.conv2d, train.py:270 `backward()`).
+ * With fwd->dil = d > 1 (stride 1 only):  dx[b,h,w,ci] = sum_{r,q,co} dy[b, h+p-r*d, w+p-q*d, co] * W[co][ci][r][q];
+ * fwd->Ho / Wo must be the dilated output size (H + 2p - (d*(kh-1)+1))/s + 1.  d > 1 together with s > 1 returns
+ * SOMI_ENOTIMPL: the taps that reach a pixel would then depend on (h+p-r*d) % s, which the parity classes do not model.
  * Runs the same MFMA implicit-GEMM kernel with rows = forward-input pixels.  `w_dgrad` is packed [Cin][kh*kw*Cout],
  * k = (r*kw+q)*Cout + co.  `accumulate` (optional, may alias dx) is added to the result (skip connections).
  * fwd->workspace / workspace_bytes are honoured as in somi_conv2d_nhwc_f32; fwd->residual2 (with res2_cs / res2_coff), if set,
@@ -134,7 +137,8 @@ int somi_conv2d_dgrad_nhwc_f32(const somi_conv_desc *fwd, const float *dy, int d
                                somi_stream_t stream);
 
 /* Weight gradient of the convolution whose FORWARD geometry `fwd` describes:
- *   dw[co][(r*kw+q)*Cin + ci] = sum_{b,ho,wo} dy[b,ho,wo,co] * x[b, ho*s-p+r, wo*s-p+q, ci]     (same packing as the forward weights)
+ *   dw[co][(r*kw+q)*Cin + ci] = sum_{b,ho,wo} dy[b,ho,wo,co] * x[b, ho*s-p+r*d, wo*s-p+q*d, ci]  (same packing as the forward weights)
+ * with d = fwd->dil >= 1 at any stride; fwd->Ho / Wo (and the workspace size) follow the dilated extent d*(kh-1)+1.
  * MFMA GEMM with the reduction over pixels, split over workgroups; the split partials live in `workspace`
  * (somi_conv2d_wgrad_workspace_bytes) and are summed in a fixed order, on top of `accumulate` if given (may alias dw).
  * per_sample_w: one gradient per image, dw is [B][Cout][K]. Cin, Cout multiples of 4. */

@@ -205,7 +205,9 @@ template <int BM, int BN, int WAVES, bool MODULATE, bool FAST, int NS>
 constexpr int conv_waves_per_simd() {
     return WAVES == 8 && BM + BN <= 192 && !MODULATE && FAST && NS == 0 ? 6 : WAVES / 2;
 }
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool MODULATE, bool FAST, int NS = 0>
+// DILBWD: the data gradient of a DILATED conv (stride 1: one parity class): the backwards tap walk steps by d.dil pixels.  An instantiation of
+// its own, so that every other launch - the forward at any dilation and the data gradient at dil == 1 - runs the code it always ran.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool MODULATE, bool FAST, int NS = 0, bool DILBWD = false>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN, WAVES_M * WAVES_N, MODULATE, FAST, NS>())) void conv_igemm_f32_kernel(const ConvArgs a) {
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;   // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;             // 32x32 MFMA tiles per wave
@@ -215,6 +217,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
     // operands go global -> LDS directly (the DMA's LDS base travels in M0[15:0]: both buffers must lie below 64 KB)
     constexpr bool DMA = FAST && !MODULATE && NS == 0 && 2 * TILE * sizeof(float) <= 65536;
     static_assert(NS == 0 || (FAST && !MODULATE), "the bf16 forms exist for the plain FAST path only");
+    static_assert(!DILBWD || !MODULATE, "a data gradient has no modulated operand");
     static_assert((WAVES_M * WAVES_N == 4 || WAVES_M * WAVES_N == 8) && TM >= 1 && TN >= 1 && A_ROWS >= 1 && B_ROWS >= 1, "bad tiling");
 
     __shared__ __attribute__((aligned(16))) float lds[TileLds<BM, BN, WAVES_M, WAVES_N>::FLOATS];
@@ -240,6 +243,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
     const int h0 = cls ? ((ph - d.pad) % d.stride + d.stride) % d.stride : 0;
     const int w0 = cls ? ((pw - d.pad) % d.stride + d.stride) % d.stride : 0;
     const int cstep = cls ? d.stride : 1;
+    const int bstep = DILBWD ? -d.dil : -1;                           // data gradient: pixels per tap step, walking backwards
     const int Hc = cls ? (d.Ho - h0 + cstep - 1) / cstep : d.Ho, Wc = cls ? (d.Wo - w0 + cstep - 1) / cstep : d.Wo;
     const int nr_c = cls ? (d.kh - ph + cstep - 1) / cstep : d.kh, nq_c = cls ? (d.kw - pw + cstep - 1) / cstep : d.kw;
     const int HoWo = Hc * Wc;
@@ -324,8 +328,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
                 unsigned mk = 0;
                 for (int t = 0; t < ntap; ++t) {
                     const int tr = t / nq_c, tq = t % nq_c;                  // class-local tap index (dgrad: r = ph + s*tr)
-                    const int hh = a_hi0[i] + (cls ? -tr : tr * d.dil);
-                    const int ww = a_wi0[i] + (cls ? -tq : tq * d.dil);
+                    const int hh = a_hi0[i] + (cls ? (DILBWD ? tr * bstep : -tr) : tr * d.dil);
+                    const int ww = a_wi0[i] + (cls ? (DILBWD ? tq * bstep : -tq) : tq * d.dil);
                     mk |= ((unsigned)hh < (unsigned)d.H && (unsigned)ww < (unsigned)d.W) ? (1u << t) : 0u;
                 }
                 a_mask[i] = mk;
@@ -349,7 +353,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         f32x4 ra[A_ROWS], rb[B_ROWS];
         auto fetch_tile = [&](int kt_next) {
             if constexpr (FAST) {
-                const int dpix = cls ? -(r_u * d.W + q_u) : (r_u * d.W + q_u) * d.dil;
+                const int dpix = cls ? (DILBWD ? (r_u * d.W + q_u) * bstep : -(r_u * d.W + q_u)) : (r_u * d.W + q_u) * d.dil;
                 const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = 1u << tp_u;
 #pragma unroll
                 for (int i = 0; i < A_ROWS; ++i) {
@@ -368,7 +372,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
                 return;
             }
             const bool kin = k < a.K;
-            const int dh = a.dgrad ? -(r / d.stride) : r * d.dil, dw = a.dgrad ? -(q / d.stride) : q * d.dil;
+            const int dh = a.dgrad ? (DILBWD ? r * bstep : -(r / d.stride)) : r * d.dil, dw = a.dgrad ? (DILBWD ? q * bstep : -(q / d.stride)) : q * d.dil;
             const int dpix = dh * d.W + dw;
             const int delta = dpix * d.x_cs + c;
             const int rpar = a.dgrad ? ((r % d.stride) | ((q % d.stride) << 8)) : 0;
@@ -432,7 +436,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         // the same fetch as LDS-DMA: each wave instruction lands 8 rows x 128 B at a wave-uniform LDS base + 16 B x lane
         auto dma_tile = [&](float *buf) {
             if constexpr (DMA) {
-                const int dpix = cls ? -(r_u * d.W + q_u) : (r_u * d.W + q_u) * d.dil;
+                const int dpix = cls ? (DILBWD ? (r_u * d.W + q_u) * bstep : -(r_u * d.W + q_u)) : (r_u * d.W + q_u) * d.dil;
                 const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = 1u << tp_u;
                 float *wrow = buf + wave * 8 * OP_LD;
 #pragma unroll
@@ -707,6 +711,24 @@ static int launch(const ConvArgs &a, const TilePlan &tp, hipStream_t s) {
     auto fixup = [&] {
         if (sk) hipLaunchKernelGGL((conv_streamk_fixup_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(sk_grid - 1), dim3(WAVES_M * WAVES_N * 64), 0, s, args, sk_grid);
     };
+    if (a.dgrad && a.d.dil > 1) {                                  // dilated data gradient (stride 1, never modulated): the DILBWD instantiations
+        if constexpr (WAVES_M * WAVES_N == 8) {
+            if (a.ns == 1 && fast)
+                hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 1, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+            else if (a.ns == 2 && fast)
+                hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 2, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+            else if (fast)
+                hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 0, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+            else
+                hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, false, 0, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+        } else if (fast) {
+            hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 0, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+        } else {
+            hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, false, 0, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+        }
+        fixup();
+        return launch_status("somi_conv2d_dgrad_nhwc_f32 (dilated)");
+    }
     if constexpr (WAVES_M * WAVES_N == 8) {
         if (a.ns && fast && !mod) {                                // reduced-precision forms (opt-in): same schedule, fix-up and epilogue
             if (a.ns == 1)
@@ -814,6 +836,7 @@ extern "C" int somi_conv2d_nhwc_f32(const somi_conv_desc *dp, somi_stream_t stre
 
 // Data gradient of the convolution described by `f` (forward geometry: x (B,H,W,Cin) -> y (B,Ho,Wo,Cout)):
 //   dx[b,h,w,ci] = sum_{r,q,co} dy[b, (h+p-r)/s, (w+p-q)/s, co] * W[co][ci][r][q]   over taps with (h+p-r) % s == 0 etc.
+// and, with dilation d > 1 (stride 1 only), dx[b,h,w,ci] = sum_{r,q,co} dy[b, h+p-r*d, w+p-q*d, co] * W[co][ci][r][q].
 // The same implicit-GEMM kernel runs with rows = forward-input pixels and the reduction over (tap, co); `wt` is the
 // dgrad packing [Cin][kh*kw*Cout] (k = (r*kw+q)*Cout + co), see somi_pack_dgrad_weights_f32.
 extern "C" int somi_conv2d_dgrad_nhwc_f32(const somi_conv_desc *f, const float *dy, int dy_cs, int dy_coff, const float *wt,
@@ -821,14 +844,18 @@ extern "C" int somi_conv2d_dgrad_nhwc_f32(const somi_conv_desc *f, const float *
                                           somi_stream_t stream) {
     using namespace somi;
     SOMI_REQUIRE(f && wt, SOMI_EINVAL, "conv dgrad: null descriptor or weights");
-    SOMI_REQUIRE(f->dil == 1, SOMI_ENOTIMPL, "conv dgrad: dilation 1 only");
-    SOMI_REQUIRE(f->Ho == (f->H + 2 * f->pad - f->kh) / f->stride + 1 && f->Wo == (f->W + 2 * f->pad - f->kw) / f->stride + 1,
+    SOMI_REQUIRE(f->kh > 0 && f->kw > 0 && f->stride > 0 && f->dil > 0 && f->pad >= 0, SOMI_EINVAL, "conv dgrad: bad geometry");
+    SOMI_REQUIRE(f->Ho == (f->H + 2 * f->pad - (f->dil * (f->kh - 1) + 1)) / f->stride + 1 &&
+                     f->Wo == (f->W + 2 * f->pad - (f->dil * (f->kw - 1) + 1)) / f->stride + 1,
                  SOMI_EINVAL, "conv dgrad: Ho/Wo do not match the forward geometry");
+    // at stride s a dilated tap r reaches pixel h iff (h + p - r*d) % s == 0: the parity classes would depend on d as well
+    SOMI_REQUIRE(f->dil == 1 || f->stride == 1, SOMI_ENOTIMPL, "conv dgrad: dilation %d with stride %d: a dilated data gradient runs at stride 1 only",
+                 f->dil, f->stride);
     somi_conv_desc g{};
     g.x = dy; g.w = wt; g.y = dx; g.residual = accumulate;
     g.B = f->B; g.H = f->Ho; g.W = f->Wo; g.Cin = f->Cout; g.x_cs = dy_cs; g.x_coff = dy_coff;      // source = dy
     g.Ho = f->H; g.Wo = f->W; g.Cout = f->Cin; g.y_cs = dx_cs; g.y_coff = dx_coff;                  // rows = forward-input pixels
-    g.kh = f->kh; g.kw = f->kw; g.stride = f->stride; g.pad = f->pad; g.dil = 1;
+    g.kh = f->kh; g.kw = f->kw; g.stride = f->stride; g.pad = f->pad; g.dil = f->dil;
     g.res_cs = acc_cs; g.res_coff = acc_coff; g.act = SOMI_ACT_NONE; g.per_sample_w = f->per_sample_w;
     g.workspace = f->workspace; g.workspace_bytes = f->workspace_bytes; g.prec = f->prec;
     g.residual2 = f->residual2; g.res2_cs = f->res2_cs; g.res2_coff = f->res2_coff;

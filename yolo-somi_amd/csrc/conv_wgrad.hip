@@ -1,6 +1,6 @@
 // Weight gradient of the NHWC convolution on the fp32 matrix cores of gfx950 (autograd of F.conv2d w.r.t. its weight,
 // train.py:270 `scaler.scale(loss).backward()`):
-//   dW[co][(r*kw+q)*Cin + ci] = sum over pixels (b,ho,wo) of dy[b,ho,wo,co] * x[b, ho*s-p+r, wo*s-p+q, ci]
+//   dW[co][(r*kw+q)*Cin + ci] = sum over pixels (b,ho,wo) of dy[b,ho,wo,co] * x[b, ho*s-p+r*d, wo*s-p+q*d, ci]   (d = dilation)
 // GEMM view: rows = co, columns = k = (tap, ci) flattened exactly as the packed weight, reduction = pixels.  A workgroup (256
 // threads, 4 waves) owns a BM (co) x BN (k) tile and a contiguous slice of the pixel range (split-K); a column tile may span
 // several taps (each thread's 16 B column quad has its own fixed tap), so narrow layers (Cin 4 / 64 / 192) still fill whole
@@ -29,7 +29,7 @@ constexpr unsigned W_MAX_BUF = 0xE0000000u;
 struct WgradArgs {
     const float *x, *dy;
     float *out;                              // [splits][n_sets][Cout][K]  (workspace) or dW itself when splits == 1
-    int B, H, W, Cin, x_cs, x_coff, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad;
+    int B, H, W, Cin, x_cs, x_coff, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil;
     int K;                                   // kh*kw*Cin
     int tiles_co, tiles_k, splits, pix_per_split, npix;    // npix = pixels per weight set (B*Ho*Wo, or Ho*Wo per sample)
     int bm, bn;                              // tile variant
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv_wgrad_f32_kernel(const W
     const int b_col = k0 + b_quad * 4;                                    // this thread's column quad: one tap, 4 channels
     const bool a_col_ok = co0 + a_quad * 4 < a.Cout, b_col_ok = b_col < a.K;
     const int b_tap = b_col / a.Cin, b_ci = b_col % a.Cin;
-    const int r = b_tap / a.kw, q = b_tap % a.kw;
+    const int r = (b_tap / a.kw) * a.dil, q = (b_tap % a.kw) * a.dil;   // the tap's offset in input pixels (dilated), fixed per thread
     constexpr int A_N = WG_PIX / A_ROWS_PER_PASS, B_N = WG_PIX / B_ROWS_PER_PASS;        // 4 ; 4,2,1
 
     // per B-row pixel coordinates (b, ho, wo) advanced incrementally by WG_PIX per K-tile
@@ -353,14 +353,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 }
 
 static int plan(const somi_conv_desc &f, WgradArgs &a) {
-    SOMI_REQUIRE(f.B > 0 && f.H > 0 && f.W > 0 && f.Cin > 0 && f.Cout > 0 && f.kh > 0 && f.kw > 0 && f.stride > 0 && f.pad >= 0,
+    SOMI_REQUIRE(f.B > 0 && f.H > 0 && f.W > 0 && f.Cin > 0 && f.Cout > 0 && f.kh > 0 && f.kw > 0 && f.stride > 0 && f.pad >= 0 &&
+                     f.dil > 0,
                  SOMI_EINVAL, "conv wgrad: bad geometry");
-    SOMI_REQUIRE(f.dil == 1, SOMI_ENOTIMPL, "conv wgrad: dilation 1 only");
-    SOMI_REQUIRE(f.Ho == (f.H + 2 * f.pad - f.kh) / f.stride + 1 && f.Wo == (f.W + 2 * f.pad - f.kw) / f.stride + 1, SOMI_EINVAL,
-                 "conv wgrad: Ho/Wo do not match the forward geometry");
+    SOMI_REQUIRE(f.Ho == (f.H + 2 * f.pad - (f.dil * (f.kh - 1) + 1)) / f.stride + 1 &&
+                     f.Wo == (f.W + 2 * f.pad - (f.dil * (f.kw - 1) + 1)) / f.stride + 1,
+                 SOMI_EINVAL, "conv wgrad: Ho/Wo do not match the forward geometry");
     SOMI_REQUIRE(f.Cin % 4 == 0 && f.Cout % 4 == 0, SOMI_EINVAL, "conv wgrad: Cin and Cout must be multiples of 4");
     a.B = f.B; a.H = f.H; a.W = f.W; a.Cin = f.Cin; a.Ho = f.Ho; a.Wo = f.Wo; a.Cout = f.Cout;
-    a.kh = f.kh; a.kw = f.kw; a.stride = f.stride; a.pad = f.pad;
+    a.kh = f.kh; a.kw = f.kw; a.stride = f.stride; a.pad = f.pad; a.dil = f.dil;
     a.K = f.kh * f.kw * f.Cin;
     a.per_sample = f.per_sample_w ? 1 : 0;
     a.npix = a.per_sample ? f.Ho * f.Wo : f.B * f.Ho * f.Wo;

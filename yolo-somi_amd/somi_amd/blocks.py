@@ -112,12 +112,13 @@ def _grad_targets(*params):
 
 
 def _plain_conv_backward(conv, src, dy, wt=None, *, dy_coff=0, dx_out=None, accumulate=False, need_dx=True, direct=()):
-    """Backward of a plain nn.Conv2d (stride 1, pad k // 2; no norm, no activation) that read the Act `src`: weight and bias gradients into .grad,
+    """Backward of a plain nn.Conv2d (stride 1, pad k // 2 - or, dilated, the conv's own padding; no norm, no activation) that read the Act `src`: weight and bias gradients into .grad,
     -> the data gradient as an Act (written into dx_out if given, added to it if accumulate; None without need_dx).
     dy: gradient tensor w.r.t. the output, pad4(out_channels) wide from channel dy_coff (pad channels zero).  wt: the weight packed for the
     data-gradient kernel (packed here when None).  direct: which of 'weight' / 'bias' the kernels accumulate straight into .grad when it is
     a contiguous fp32 tensor and nothing is padded (the weight of a 1x1 conv only); the others go through a scratch tensor and _acc_grad."""
-    k = conv.kernel_size[0]
+    k, dil = conv.kernel_size[0], conv.dilation[0]
+    p = conv.padding[0] if dil > 1 else k // 2
     c1, c2 = conv.in_channels, conv.out_channels
     c1p, cp = pad4(c1), pad4(c2)
     g = conv.weight.grad
@@ -126,7 +127,7 @@ def _plain_conv_backward(conv, src, dy, wt=None, *, dy_coff=0, dx_out=None, accu
         gv = g.view(c2, c1)                                       # the optimizer's flat view: the kernel adds to it in place
         ops.conv2d_wgrad_nhwc(src.t, dy, kh=1, kw=1, cin=c1p, x_coff=src.coff, cout=cp, dy_coff=dy_coff, out=gv, accumulate=gv)
     else:
-        dw = ops.conv2d_wgrad_nhwc(src.t, dy, kh=k, kw=k, stride=1, pad=k // 2, cin=c1p, x_coff=src.coff, cout=cp, dy_coff=dy_coff)
+        dw = ops.conv2d_wgrad_nhwc(src.t, dy, kh=k, kw=k, stride=1, pad=p, dil=dil, cin=c1p, x_coff=src.coff, cout=cp, dy_coff=dy_coff)
         _acc_grad(conv.weight, dw.view(cp, k, k, c1p)[:c2, :, :, :c1].permute(0, 3, 1, 2))
     if conv.bias is not None:
         if 'bias' in direct and cp == c2:
@@ -143,7 +144,7 @@ def _plain_conv_backward(conv, src, dy, wt=None, *, dy_coff=0, dx_out=None, accu
     B, H, W, _ = src.shape
     if dx_out is None:
         dx_out = Act(torch.empty(B, H, W, c1p, device=dy.device, dtype=torch.float32), 0, c1)
-    ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1p, kh=k, kw=k, stride=1, pad=k // 2, cout=cp, dy_coff=dy_coff, out=dx_out.t,
+    ops.conv2d_dgrad_nhwc(dy, wt, B=B, H=H, W=W, cin=c1p, kh=k, kw=k, stride=1, pad=p, dil=dil, cout=cp, dy_coff=dy_coff, out=dx_out.t,
                           dx_coff=dx_out.coff, accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff)
     return dx_out
 
@@ -281,17 +282,20 @@ def _pack_wb(w, b, dev):
 
 
 class Conv(_Packed):
-    """conv2d(bias=False) -> BatchNorm2d -> SiLU as one fused launch (models/common.py:53-70).  g > 1 runs on the grouped / depthwise
+    """conv2d(bias=False) -> BatchNorm2d -> SiLU as one fused launch (models/common.py:53-70).  d > 1 (dense, stride 1) walks dilated taps
+    in the same kernels, forward and both gradients.  g > 1 runs on the grouped / depthwise
     kernels (gconv.hip): k 1, 3 or 5, stride 1 or 2, pad k // 2, at most 16 input channels per group."""
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
-        if d != 1:
-            raise NotImplementedError('dilated Conv is not on the SOMI path')
         if isinstance(k, (tuple, list)):                         # C3 hands its bottlenecks (1, 1) / (3, 3) (models/common.py:1558)
             if len(k) != 2 or k[0] != k[1]:
                 raise NotImplementedError('square kernels only')
             k = int(k[0])
+        if d != 1 and g != 1:
+            raise NotImplementedError('grouped / depthwise dilated Conv is not on the SOMI path (dense convs only)')
+        if d != 1 and s != 1:
+            raise NotImplementedError(f'dilated Conv with stride {s} is not on the SOMI path (its data gradient runs at stride 1 only)')
         if g != 1:
             if k not in (1, 3, 5) or s not in (1, 2) or autopad(k, p, d) != k // 2:
                 raise NotImplementedError(f'grouped Conv with k={k}, s={s}, p={p} is not on the SOMI path (k 1/3/5, stride 1/2, pad k // 2)')
@@ -340,17 +344,17 @@ class Conv(_Packed):
         pool: a dict - when the shape allows, the pass that writes z also takes its global average / max pools per (image, channel) and leaves
         them as pool['avg'], pool['max'] (a channel attention behind this block then needs no pass of its own over z)."""
         pk = self._packed(x.t.device)                            # rebuilt after every optimizer step (Model.invalidate)
-        k, s, p = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0]
+        k, s, p, dil = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0], self.conv.dilation[0]
         c2, cp = self.conv.out_channels, pad4(self.conv.out_channels)
         B, H, W, _ = x.shape
-        Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
+        Ho, Wo = ops.conv_out_size(H, k, s, p, dil), ops.conv_out_size(W, k, s, p, dil)
         y = torch.empty(B, Ho, Wo, cp, device=x.t.device, dtype=torch.float32)
         st = {'pivot': pk['rm']} if self.conv.groups > 1 or y.numel() * 4 <= 0xE0000000 else None     # the epilogue leaves y's per-channel partial sums
         if self.conv.groups > 1:                                 # grouped / depthwise: the same partial sums, from the stencil kernel
             ops.gconv2d_nhwc(x.t, pk['gw'], c1=self.conv.in_channels, c2=c2, groups=self.conv.groups, k=k, stride=s, x_coff=x.coff, out=y, cw=cp,
                              bn_stats=st)
         else:
-            ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
+            ops.conv2d_nhwc(x.t, pk['wp'], None, kh=k, kw=k, stride=s, pad=p, dil=dil, act='none', cin=pad4(x.c), x_coff=x.coff, out=y, cout=cp,
                             alg_cin=x.c, alg_cout=c2, bn_stats=st)
         (mean, rstd, scale, shift), commit = _bn_train(self.bn, cp, y, partials=st, npix=B * Ho * Wo, vec=pk)
         commit()                                                 # running statistics back into the module buffers
@@ -382,7 +386,7 @@ class Conv(_Packed):
         cbam: state of ops.cbam_backward(bn=...) - dz is then the gradient w.r.t. t*ca*sa of the CBAM bottleneck this conv opens, and the attention's
         step C runs inside the BatchNorm backward kernels too (pooled = the MLP backward's (davg, dmax, amaxp) on that call's dca)."""
         x, y, mean, rstd, scale, shift, pk = self.__dict__.pop('_ctx')
-        k, s, p = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0]
+        k, s, p, dil = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0], self.conv.dilation[0]
         c1, c2, cp = self.conv.in_channels, self.conv.out_channels, pad4(self.conv.out_channels)
         dev = y.device
         dy = torch.zeros_like(y) if cp != c2 else torch.empty_like(y)
@@ -401,16 +405,16 @@ class Conv(_Packed):
         if self.conv.groups > 1:
             return self._backward_grouped(x, dy, pk, dx_out, accumulate, need_dx, also_add)
         if pk['gp'] is not None:                                  # accumulate into the packed gradient master
-            ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=s, pad=p, cin=pad4(c1), x_coff=x.coff, cout=cp, out=pk['gp'],
+            ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=s, pad=p, dil=dil, cin=pad4(c1), x_coff=x.coff, cout=cp, out=pk['gp'],
                                   accumulate=pk['gp'])
         else:
-            dw = ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=s, pad=p, cin=pad4(c1), x_coff=x.coff, cout=cp)
+            dw = ops.conv2d_wgrad_nhwc(x.t, dy, kh=k, kw=k, stride=s, pad=p, dil=dil, cin=pad4(c1), x_coff=x.coff, cout=cp)
             _acc_grad(self.conv.weight, dw.view(cp, k, k, pad4(c1))[:c2, :, :, :c1].permute(0, 3, 1, 2))
         if not need_dx:
             return None
         if dx_out is None:
             dx_out = Act(torch.empty(B, H, W, pad4(c1), device=dev, dtype=torch.float32), 0, c1)
-        ops.conv2d_dgrad_nhwc(dy, pk['wt'], B=B, H=H, W=W, cin=pad4(c1), kh=k, kw=k, stride=s, pad=p, cout=cp, out=dx_out.t,
+        ops.conv2d_dgrad_nhwc(dy, pk['wt'], B=B, H=H, W=W, cin=pad4(c1), kh=k, kw=k, stride=s, pad=p, dil=dil, cout=cp, out=dx_out.t,
                               dx_coff=dx_out.coff, accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff,
                               accumulate2=None if also_add is None else also_add.t,
                               acc2_coff=0 if also_add is None else also_add.coff)
@@ -444,10 +448,10 @@ class Conv(_Packed):
         if self.conv.groups > 1:
             return self._forward_grouped(x, out, residual, a_chan, a_pix)
         wp, bp = self._packed(x.t.device)
-        k, s, p = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0]
+        k, s, p, dil = self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0], self.conv.dilation[0]
         c2 = self.conv.out_channels
         B, H, W, _ = x.shape
-        Ho, Wo = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
+        Ho, Wo = ops.conv_out_size(H, k, s, p, dil), ops.conv_out_size(W, k, s, p, dil)
         if out is None:
             out = new_act(x.t, Ho, Wo, c2)
             cout = pad4(c2)
@@ -455,7 +459,7 @@ class Conv(_Packed):
             if c2 % 4:
                 raise NotImplementedError('writing into a channel slice needs c2 % 4 == 0')
             cout = c2
-        ops.conv2d_nhwc(x.t, wp[:cout], bp, kh=k, kw=k, stride=s, pad=p, act=_act_name(self.act), cin=pad4(x.c),
+        ops.conv2d_nhwc(x.t, wp[:cout], bp, kh=k, kw=k, stride=s, pad=p, dil=dil, act=_act_name(self.act), cin=pad4(x.c),
                         x_coff=x.coff, out=out.t, cout=cout, y_coff=out.coff,
                         residual=None if residual is None else residual.t,
                         res_coff=0 if residual is None else residual.coff, a_chan_scale=a_chan, a_pix_scale=a_pix,
@@ -2304,6 +2308,191 @@ class C3_CA(C3):
         self.m = nn.Sequential(*(CABottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
 
     accumulates, folds_pooled, reduction = False, False, 1       # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
+
+
+class ASPP(nn.Module):
+    """cv2(cat(t, maxpool3(t), m_0(t), ..)), t = cv1(x) (models/common.py:1829-1843): atrous spatial pyramid pooling.  The m_i are bare 3x3
+    nn.Conv2d(bias=False) of dilation = padding = (k_i - 1) // 2 (2, 4, 6 for the default k), no norm and no activation.  Nothing is
+    concatenated: cv1 writes slice 0 of cv2's input buffer, the parallel-window pool kernel writes slice 1 (window 3, with codes in training)
+    and each dilated conv its own slice.  Backward: cv2's data gradient, the pool's share and every dilated conv's data gradient added into
+    slice 0 in place, then cv1."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13)):
+        super().__init__()
+        k = tuple(int(v) for v in k)
+        if not k or any(v < 3 or v % 2 == 0 for v in k):
+            raise NotImplementedError(f'ASPP rates from k={k}: odd k >= 3 only (dilation = padding = (k - 1) // 2 >= 1 keeps the map size)')
+        c_ = c1 // 2
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=1, padding=1)      # parameter-free; kept for repr parity
+        self.m = nn.ModuleList([nn.Conv2d(c_, c_, kernel_size=3, stride=1, padding=(x - 1) // 2, dilation=(x - 1) // 2, bias=False) for x in k])
+        self.cv2 = Conv(c_ * (len(k) + 2), c2, 1, 1)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _packed_m(self, dev):
+        """Per dilated conv (forward packing, data-gradient packing), rebuilt when a weight changed (in training: every forward)."""
+        key = (dev, tuple(m.weight._version for m in self.m))
+        cache = self.__dict__.get('_pk')
+        if self.training or cache is None or cache[0] != key:
+            with torch.no_grad():
+                ws = [m.weight.detach().float() for m in self.m]
+                cache = (key, [(pack_conv_weight(w).to(dev), pack_dgrad_weight(w).to(dev) if self.training else None) for w in ws])
+            self.__dict__['_pk'] = cache
+        return cache[1]
+
+    def invalidate(self):
+        self.__dict__.pop('_pk', None)
+
+    def forward(self, x):
+        c_, n = self.cv1.conv.out_channels, len(self.m)
+        if c_ % 4:
+            raise NotImplementedError('ASPP hidden width must be a multiple of 4 on the MI355X path')
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, (n + 2) * c_)
+        self.cv1(x, out=cat.slice(0, c_))
+        codes = ops.spp_pool_(cat.t, c_, (3,), 0, codes=self.training)
+        pk = self._packed_m(x.t.device)
+        for i, (m, (wp, _)) in enumerate(zip(self.m, pk)):
+            ops.conv2d_nhwc(cat.t, wp, None, kh=3, kw=3, stride=1, pad=m.padding[0], dil=m.dilation[0], act='none', cin=c_, x_coff=0,
+                            out=cat.t, cout=c_, y_coff=(2 + i) * c_)
+        if self.training:
+            self.__dict__['_ctx'] = (cat, codes[1], pk)
+        return self.cv2(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        cat, codes, pk = self.__dict__.pop('_ctx')
+        c_ = self.cv1.conv.out_channels
+        dcat = self.cv2.backward(dout)
+        ops.spp_pool_backward_(dcat.t, codes, c_, (3,), dcat.coff)
+        d0 = dcat.slice(0, c_)
+        for i, (m, (_, wt)) in enumerate(zip(self.m, pk)):
+            _plain_conv_backward(m, cat.slice(0, c_), dcat.t, wt, dy_coff=dcat.coff + (2 + i) * c_, dx_out=d0, accumulate=True)
+        return self.cv1.backward(d0, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
+class DWR(nn.Module):
+    """Dilation-wise residual (models/common.py:7431-7447): conv_1x1(cat(d1(t), d3(t), d5(t))) + x with t = conv_3x3(x); the branches are 3x3
+    Convs of dilation 1, 3 and 5 and dim, dim / 2, dim / 2 channels.  The branches write the three slices of one 2 * dim buffer, the
+    residual rides conv_1x1's output pass.  Backward: the branches' data gradients are summed into one tensor by `accumulate`, and x's own
+    share (the residual) joins conv_3x3's data-gradient epilogue."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.conv_3x3 = Conv(dim, dim // 2, 3)
+        self.conv_3x3_d1 = Conv(dim // 2, dim, 3, d=1)
+        self.conv_3x3_d3 = Conv(dim // 2, dim // 2, 3, d=3)
+        self.conv_3x3_d5 = Conv(dim // 2, dim // 2, 3, d=5)
+        self.conv_1x1 = Conv(dim * 2, dim, k=1)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _branches(self):
+        dim = self.conv_1x1.conv.out_channels
+        return ((self.conv_3x3_d1, 0, dim), (self.conv_3x3_d3, dim, dim // 2), (self.conv_3x3_d5, dim + dim // 2, dim // 2))
+
+    def forward(self, x, out=None):
+        dim = self.conv_1x1.conv.out_channels
+        if dim % 8:
+            raise NotImplementedError('DWR width must be a multiple of 8 on the MI355X path (its branches write slices of dim / 2 channels)')
+        B, H, W, _ = x.shape
+        t = self.conv_3x3(x)
+        cat = concat_act(x.t, H, W, 2 * dim)
+        for blk, off, c in self._branches():
+            blk(t, out=cat.slice(off, c))
+        return self.conv_1x1(cat, out=out, residual=x)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        dim = self.conv_1x1.conv.out_channels
+        dcat = self.conv_1x1.backward(dout)
+        dt = None
+        for blk, off, c in self._branches():
+            dt = blk.backward(dcat.slice(off, c), dx_out=dt, accumulate=dt is not None)
+        fuse = dout.coff % 4 == 0                                 # dim % 8 == 0: the residual's gradient rides the dgrad epilogue
+        dx = self.conv_3x3.backward(dt, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, dim)
+        return dx
+
+
+class DWRSeg_Conv(_Packed):
+    """gelu(bn(DWR(conv(x)))) with a 1x1 Conv (models/common.py:7450-7466; kernel_size, stride, groups and dilation are accepted and unused, as in
+    the reference, whose DWR child is called `dcnv3`).  Eval: the BatchNorm's running statistics and the GELU are one pass over DWR's output;
+    training: the one BatchNorm train path, GELU after the normalisation (order 0)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, groups=1, dilation=1):
+        super().__init__()
+        self.conv = Conv(in_channels, out_channels, k=1)
+        self.dcnv3 = DWR(out_channels)
+        self.bn = nn.BatchNorm2d(out_channels)
+        self.gelu = nn.GELU()
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack_params(self):
+        return self.bn.parameters()                               # the children pack themselves
+
+    def _pack(self, dev):
+        return tuple(v.detach().float().contiguous().to(dev) for v in bn_fold(self.bn))
+
+    def forward(self, x, out=None, residual=None):
+        c = self.bn.num_features
+        u = self.dcnv3(self.conv(x))                              # a whole tensor of its own, c % 8 == 0
+        if out is None:
+            out = new_act(x.t, u.shape[1], u.shape[2], c)
+        res = dict(residual=None if residual is None else residual.t, res_coff=0 if residual is None else residual.coff)
+        if not self.training:
+            s, t = self._packed(u.t.device)
+            ops.chan_affine_act(u.t, c, u.coff, s, t, 'gelu', 0, out.t, out.coff, **res)
+            return Act(out.t, out.coff, c)
+        st, commit = _bn_train(self.bn, c, u.t, coff=u.coff)
+        commit()
+        ops.chan_affine_act(u.t, c, u.coff, st[2], st[3], 'gelu', 0, out.t, out.coff, **res)
+        self.__dict__['_ctx'] = (u, st)
+        return Act(out.t, out.coff, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        u, st = self.__dict__.pop('_ctx')
+        c = self.bn.num_features
+        du = _bn_backward(self.bn, dout.t, dout.coff, u.t, st, 'gelu', torch.empty_like(u.t), c, coff=u.coff, order=0)
+        d = self.dcnv3.backward(Act(du, u.coff, c))
+        return self.conv.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
+class Bottleneck_DWRSeg(nn.Module):
+    """cv1 (k[0] Conv) -> DWRSeg_Conv (+x) (models/common.py:7469-7484); the shortcut rides the GELU pass (forward) and cv1's dgrad epilogue
+    (backward)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, k[0], 1)
+        self.cv2 = DWRSeg_Conv(c_, c2, k[1], 1, groups=g)
+        self.add = shortcut and c1 == c2
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x, out=None):
+        return self.cv2(self.cv1(x), out=out, residual=x if self.add else None)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = self.cv2.backward(dout)
+        c1 = self.cv1.conv.in_channels
+        fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0
+        dx = self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if self.add and not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class C2f_DWR(C2f):
+    """C2f whose blocks are Bottleneck_DWRSeg(c, c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) (models/common.py:7487-7511): C2f's slice scheme."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(Bottleneck_DWRSeg(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
+
+    accumulates, folds_pooled, reduction = False, False, 1       # C2f's backward, dx_out / accumulate included; the walk adds its gradient itself
 
 
 class Concat(nn.Module):

@@ -180,6 +180,25 @@ def yolov5_ca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
     return cfg
 
 
+def yolov5_context_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='aspp'):
+    """yolov5s 6.0 with the dilated-convolution context blocks (ASPP, models/common.py:1829-1843; C2f_DWR, :7431-7511).  The reference registers
+    both in its parser (models/yolo.py:1472-1492, C2f_DWR among the modules repeated inside) but ships no yaml that names them.  where='aspp': a
+    [-1, 1, 'ASPP', [1024]] row in SPPF's place; where='dwr': [-1, n, 'C2f_DWR', [512, True]] and [-1, n, 'C2f_DWR', [1024, True]] in place of
+    the P4 and P5 backbone C3 rows, same n; where='both': both changes."""
+    if where not in ('aspp', 'dwr', 'both'):
+        raise ValueError(f"where must be 'aspp', 'dwr' or 'both', got {where!r}")
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    bb = cfg['backbone']
+    if where in ('aspp', 'both'):
+        (i,) = [j for j, row in enumerate(bb) if row[2] == 'SPPF']
+        bb[i] = [-1, 1, 'ASPP', [1024]]
+    if where in ('dwr', 'both'):
+        for j, row in enumerate(bb):
+            if row[2] == 'C3' and row[3][0] in (512, 1024):
+                bb[j] = [row[0], row[1], 'C2f_DWR', [row[3][0], True]]
+    return cfg
+
+
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
     C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""

@@ -10,7 +10,7 @@ C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny
 nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; the two learned
 drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-transformer C3 (C3TR stays outside); ASFF_Detect, the plain
 Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck); and coordinate
-attention, as the C3_CA block and as a CoorAttention row of its own.
+attention, as the C3_CA block and as a CoorAttention row of its own; and the dilated-convolution context blocks ASPP and C2f_DWR.
 """
 import math
 from copy import deepcopy
@@ -31,9 +31,10 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'Focus': B.Focus, 'GhostConv': B.GhostConv, 'GhostBottleneck': B.GhostBottleneck, 'DWConv': B.DWConv,
        'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA,
        'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR,        # models/yolo.py:1472-1479
-       'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention}        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
+       'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention,        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
+       'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR}                      # the dilated-conv context blocks, models/yolo.py:1472-1492
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR')
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution

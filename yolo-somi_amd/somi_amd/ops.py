@@ -905,9 +905,10 @@ def cfs_blend(x, xproj, logit, G, Gc):
     return out
 
 
-def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, cout=None, dy_coff=0, out=None, dx_coff=0,
+def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, dil=1, cout=None, dy_coff=0, out=None, dx_coff=0,
                       accumulate=None, acc_coff=0, per_sample_w=False, accumulate2=None, acc2_coff=0):
-    """dx of the conv x (B,H,W,cin) -> y (B,Ho,Wo,cout); dy is (B,Ho,Wo,dy_cs); w_dgrad packed [cin][kh*kw*cout]."""
+    """dx of the conv x (B,H,W,cin) -> y (B,Ho,Wo,cout); dy is (B,Ho,Wo,dy_cs); w_dgrad packed [cin][kh*kw*cout].
+    dil > 1 runs at stride 1 only (the library refuses the combination)."""
     _, Ho, Wo, dy_cs = dy.shape
     cout = dy_cs - dy_coff if cout is None else cout
     if out is None:
@@ -915,7 +916,7 @@ def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, cou
     d = ConvDesc()
     d.prec = CONV_PREC
     d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = B, H, W, cin, Ho, Wo, cout
-    d.kh, d.kw, d.stride, d.pad, d.dil, d.per_sample_w = kh, kw, stride, pad, 1, int(per_sample_w)
+    d.kh, d.kw, d.stride, d.pad, d.dil, d.per_sample_w = kh, kw, stride, pad, dil, int(per_sample_w)
     _conv_workspace(d, dy.device)
     if accumulate2 is not None:                                   # second added tensor (e.g. the shortcut branch's gradient)
         d.residual2, d.res2_cs, d.res2_coff = _ptr(_f32c(accumulate2)), accumulate2.shape[3], acc2_coff
@@ -924,7 +925,7 @@ def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, cou
     def info():
         g = ConvDesc()                                           # the geometry the kernel runs in: rows = forward-input pixels
         g.B, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout = B, Ho, Wo, cout, H, W, cin
-        g.kh, g.kw, g.stride, g.per_sample_w = kh, kw, stride, int(per_sample_w)
+        g.kh, g.kw, g.stride, g.dil, g.per_sample_w = kh, kw, stride, dil, int(per_sample_w)
         if stride == 1:
             g.workspace, g.workspace_bytes = d.workspace, d.workspace_bytes
         return _lib.lib().somi_conv2d_kernel_name(C.byref(g)).decode(), 2.0 * B * Ho * Wo * cout * cin * kh * kw, (B, H, W, cin, cout, kh, stride, 2)
@@ -936,7 +937,7 @@ def conv2d_dgrad_nhwc(dy, w_dgrad, *, B, H, W, cin, kh, kw, stride=1, pad=0, cou
     return out
 
 
-def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, cin=None, x_coff=0, cout=None, dy_coff=0, out=None, accumulate=None,
+def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, dil=1, cin=None, x_coff=0, cout=None, dy_coff=0, out=None, accumulate=None,
                       per_sample_w=False):
     """dW [Cout][kh*kw*Cin] (forward packing) of the conv x (B,H,W,cin) -> y (B,Ho,Wo,cout) from x and dy."""
     B, H, W, x_cs = x.shape
@@ -946,7 +947,7 @@ def conv2d_wgrad_nhwc(x, dy, *, kh, kw, stride=1, pad=0, cin=None, x_coff=0, cou
     d = ConvDesc()
     d.prec = CONV_PREC
     d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = B, H, W, cin, Ho, Wo, cout
-    d.kh, d.kw, d.stride, d.pad, d.dil, d.per_sample_w = kh, kw, stride, pad, 1, int(per_sample_w)
+    d.kh, d.kw, d.stride, d.pad, d.dil, d.per_sample_w = kh, kw, stride, pad, dil, int(per_sample_w)
     shape = ((B,) if per_sample_w else ()) + (cout, kh * kw * cin)
     if out is None:
         out = torch.empty(*shape, device=x.device, dtype=torch.float32)
