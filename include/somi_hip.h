@@ -111,10 +111,20 @@ typedef struct somi_conv_desc {
      * made on): 1 = operands rounded to bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate - autocast's arithmetic), 2 = "bf16x3": each
      * operand split into two bf16 values and hi*hi + hi*lo + lo*hi accumulated in fp32 (~1e-5 relative error).  Tensors stay fp32 in
      * HBM either way.  Honoured by the plain channel-aligned launches (Cin % 32 == 0, shared weights, no operand modulation) of
-     * somi_conv2d_nhwc_f32 / _dgrad_ / _wgrad_; every other launch computes in exact fp32. */
+     * somi_conv2d_nhwc_f32 / _dgrad_ / _wgrad_; every other launch computes in exact fp32 - among them the forward and the data gradient of
+     * a patch-embedding conv of more than 32 taps (kh == kw == stride >= 6, pad 0, dil 1: see somi_conv2d_nhwc_f32), whose instantiation
+     * has no reduced-precision form; its weight gradient honours `prec` like any other. */
     int32_t prec;
 } somi_conv_desc;
 
+/* Any kh, kw, stride, pad, dil.  Which code a launch runs: Cin % 32 == 0 with kh*kw <= 32 taps takes the wave-uniform tap walk with a
+ * per-row tap mask (LDS-DMA staging, stream-K with a workspace, `prec`) - that includes the patch-embedding geometry kh == kw == stride
+ * == p, pad 0 (MultiSEAM's stems, models/common.py:8510) at p = 3 and 5.  The same geometry at p*p > 32 (p = 7: 49 taps) with Cin % 32
+ * == 0 takes instantiations of its own, here and in somi_conv2d_dgrad_nhwc_f32: no tap of an in-range output pixel leaves the image, so
+ * there is no tap mask; the data gradient runs p*p parity classes of ONE tap each (dx pixel (h, w) has the tap (h % p, w % p) and the
+ * source pixel (h / p, w / p)), and the dx pixels with h >= Ho*p or w >= Wo*p, which no tap reaches, are written as exact zeros (plus
+ * `accumulate` / residual2, if given).  Exact fp32 whatever `prec` asks for.  Everything else - Cin % 32 != 0, more than 32 taps at
+ * another geometry, modulated operands beyond 32 taps - takes the generic register-staged path: correct, not fast. */
 int somi_conv2d_nhwc_f32(const somi_conv_desc *d, somi_stream_t stream);
 /* Scratch size that enables the stream-K schedule for every shape (64 MiB). */
 size_t somi_conv2d_workspace_bytes(void);
@@ -123,7 +133,8 @@ int somi_conv2d_stat_rows(const somi_conv_desc *d);
 
 /* Data gradient of the convolution whose FORWARD geometry `fwd` describes (x (B,H,W,Cin) -> y (B,Ho,Wo,Cout); the pointer
  * fields of `fwd` are ignored):  dx[b,h,w,ci] = sum_{r,q,co} dy[b,(h+p-r)/s,(w+p-q)/s,co] * W[co][ci][r][q]
- * over the taps for which the divisions are exact and in range (autograd of F.conv2d, train.py:270 `backward()`).
+ * over the taps for which the divisions are exact and in range (autograd of F.conv2d, train.py:270 `backward()`); a pixel no tap
+ * reaches (kh == stride, h >= Ho*stride) is written as 0 (+ accumulate).
  * With fwd->dil = d > 1 (stride 1 only):  dx[b,h,w,ci] = sum_{r,q,co} dy[b, h+p-r*d, w+p-q*d, co] * W[co][ci][r][q];
  * fwd->Ho / Wo must be the dilated output size (H + 2p - (d*(kh-1)+1))/s + 1.  d > 1 together with s > 1 returns
  * SOMI_ENOTIMPL: the taps that reach a pixel would then depend on (h+p-r*d) % s, which the parity classes do not model.
@@ -138,7 +149,8 @@ int somi_conv2d_dgrad_nhwc_f32(const somi_conv_desc *fwd, const float *dy, int d
 
 /* Weight gradient of the convolution whose FORWARD geometry `fwd` describes:
  *   dw[co][(r*kw+q)*Cin + ci] = sum_{b,ho,wo} dy[b,ho,wo,co] * x[b, ho*s-p+r*d, wo*s-p+q*d, ci]  (same packing as the forward weights)
- * with d = fwd->dil >= 1 at any stride; fwd->Ho / Wo (and the workspace size) follow the dilated extent d*(kh-1)+1.
+ * with d = fwd->dil >= 1 at any stride; fwd->Ho / Wo (and the workspace size) follow the dilated extent d*(kh-1)+1.  Any tap count: a
+ * thread's column quad has one fixed tap, so the patch-embedding geometry (kh == kw == stride, 9 / 25 / 49 taps) runs the code every conv runs.
  * MFMA GEMM with the reduction over pixels, split over workgroups; the split partials live in `workspace`
  * (somi_conv2d_wgrad_workspace_bytes) and are summed in a fixed order, on top of `accumulate` if given (may alias dw).
  * per_sample_w: one gradient per image, dw is [B][Cout][K]. Cin, Cout multiples of 4. */

@@ -207,7 +207,12 @@ constexpr int conv_waves_per_simd() {
 }
 // DILBWD: the data gradient of a DILATED conv (stride 1: one parity class): the backwards tap walk steps by d.dil pixels.  An instantiation of
 // its own, so that every other launch - the forward at any dilation and the data gradient at dil == 1 - runs the code it always ran.
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool MODULATE, bool FAST, int NS = 0, bool DILBWD = false>
+// PATCH: a patch-embedding conv, kh == kw == stride == p with pad 0 and dil 1, of more than 32 taps (p = 7: 49), forward and data gradient.
+// No tap of an in-range output pixel leaves the image, so a row has no tap mask (which is what holds FAST to 32 taps) but one validity flag:
+// the row exists and, in the data gradient, its one source pixel (h / p, w / p) does - the pixels with h >= Ho * p or w >= Wo * p have none
+// and come out as exact zeros (plus `accumulate`).  The K walk, the p^2 one-tap parity classes of the data gradient and the LDS-DMA staging
+// are the FAST path's.  An instantiation of its own, under the rule DILBWD set.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool MODULATE, bool FAST, int NS = 0, bool DILBWD = false, bool PATCH = false>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN, WAVES_M * WAVES_N, MODULATE, FAST, NS>())) void conv_igemm_f32_kernel(const ConvArgs a) {
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;   // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;             // 32x32 MFMA tiles per wave
@@ -218,6 +223,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
     constexpr bool DMA = FAST && !MODULATE && NS == 0 && 2 * TILE * sizeof(float) <= 65536;
     static_assert(NS == 0 || (FAST && !MODULATE), "the bf16 forms exist for the plain FAST path only");
     static_assert(!DILBWD || !MODULATE, "a data gradient has no modulated operand");
+    static_assert(!PATCH || (FAST && !MODULATE && NS == 0 && !DILBWD), "the patch form is a plain exact-fp32 FAST instantiation");
     static_assert((WAVES_M * WAVES_N == 4 || WAVES_M * WAVES_N == 8) && TM >= 1 && TN >= 1 && A_ROWS >= 1 && B_ROWS >= 1, "bad tiling");
 
     __shared__ __attribute__((aligned(16))) float lds[TileLds<BM, BN, WAVES_M, WAVES_N>::FLOATS];
@@ -326,7 +332,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
 #pragma unroll
             for (int i = 0; i < A_ROWS; ++i) {
                 unsigned mk = 0;
-                for (int t = 0; t < ntap; ++t) {
+                if constexpr (PATCH)                                          // one flag per row: tap (0,0) of the row (its only tap in a dgrad class)
+                    mk = ((unsigned)a_hi0[i] < (unsigned)d.H && (unsigned)a_wi0[i] < (unsigned)d.W) ? 1u : 0u;
+                for (int t = 0; !PATCH && t < ntap; ++t) {
                     const int tr = t / nq_c, tq = t % nq_c;                  // class-local tap index (dgrad: r = ph + s*tr)
                     const int hh = a_hi0[i] + (cls ? (DILBWD ? tr * bstep : -tr) : tr * d.dil);
                     const int ww = a_wi0[i] + (cls ? (DILBWD ? tq * bstep : -tq) : tq * d.dil);
@@ -354,7 +362,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         auto fetch_tile = [&](int kt_next) {
             if constexpr (FAST) {
                 const int dpix = cls ? (DILBWD ? (r_u * d.W + q_u) * bstep : -(r_u * d.W + q_u)) : (r_u * d.W + q_u) * d.dil;
-                const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = 1u << tp_u;
+                const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = PATCH ? 1u : 1u << tp_u;
 #pragma unroll
                 for (int i = 0; i < A_ROWS; ++i) {
                     const bool ok = (a_mask[i] & bit) != 0;
@@ -437,7 +445,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         auto dma_tile = [&](float *buf) {
             if constexpr (DMA) {
                 const int dpix = cls ? (DILBWD ? (r_u * d.W + q_u) * bstep : -(r_u * d.W + q_u)) : (r_u * d.W + q_u) * d.dil;
-                const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = 1u << tp_u;
+                const unsigned sd = (unsigned)(dpix * d.x_cs + c0_u) * 4u, bit = PATCH ? 1u : 1u << tp_u;
                 float *wrow = buf + wave * 8 * OP_LD;
 #pragma unroll
                 for (int i = 0; i < A_ROWS; ++i)
@@ -654,9 +662,14 @@ static const int kTileBM[4] = {128, 64, 128, 128}, kTileBN[4] = {128, 128, 64, 3
 static bool fast_path(const somi_conv_desc &d) {
     return d.Cin % BK == 0 && d.kh * d.kw <= 32 && (size_t)d.kh * d.kw * d.Cin * 4 < (1u << 27);
 }
+// the PATCH instantiations: k == s patch-embedding geometry beyond the 32 taps of the FAST mask (k = s <= 5 qualifies for FAST and stays there)
+static bool patch_path(const somi_conv_desc &d) {
+    return d.Cin % BK == 0 && d.kh * d.kw > 32 && d.kh == d.kw && d.stride == d.kh && d.pad == 0 && d.dil == 1 && !d.a_chan_scale &&
+           !d.a_pix_scale && (size_t)d.kh * d.kw * d.Cin * 4 < (1u << 27);
+}
 // resident workgroups chip-wide (stream-K slots): two per CU; three for the plain fp32 form of the 8-wave 128 x 64 tile
 static inline int sk_slots(int variant, const somi_conv_desc &d) {
-    const bool three = variant == 2 && !d.a_chan_scale && !d.a_pix_scale && d.prec != 1 && d.prec != 2 && fast_path(d);
+    const bool three = variant == 2 && ((!d.a_chan_scale && !d.a_pix_scale && d.prec != 1 && d.prec != 2 && fast_path(d)) || patch_path(d));
     return three ? SK_GRID * 3 / 2 : SK_GRID;
 }
 
@@ -664,7 +677,7 @@ static inline int sk_slots(int variant, const somi_conv_desc &d) {
 // problems too and the K-tiles are streamed over 512 workgroups whenever whole rounds of tiles would leave >10% of the
 // slots idle; without one, small-M problems take the 64-row tile to fill the chip.
 static TilePlan plan_tiles(const somi_conv_desc &d, int M, int dgrad) {
-    const bool sk_ok = d.workspace && fast_path(d) && !d.per_sample_w && !(dgrad && d.stride > 1);
+    const bool sk_ok = d.workspace && (fast_path(d) || patch_path(d)) && !d.per_sample_w && !(dgrad && d.stride > 1);
     TilePlan p{0, false};
     const long blocks128 = (long)cdiv(M, 128) * cdiv(d.Cout, 128) * (d.per_sample_w ? d.B : 1);
     if (d.Cout > 64) {
@@ -690,8 +703,8 @@ static int launch(const ConvArgs &a, const TilePlan &tp, hipStream_t s) {
     ConvArgs args = a;
     const bool sk = tp.sk;
     const bool mod = a.d.a_chan_scale || a.d.a_pix_scale;
-    const bool fast = fast_path(a.d);
-    args.cls = a.dgrad && fast;
+    const bool fast = fast_path(a.d), patch = patch_path(a.d);
+    args.cls = a.dgrad && (fast || patch);
     args.sk = sk ? 1 : 0;
     args.ws = static_cast<float *>(a.d.workspace);
     const int st = a.d.stride, ncls = args.cls ? st * st : 1;
@@ -711,6 +724,11 @@ static int launch(const ConvArgs &a, const TilePlan &tp, hipStream_t s) {
     auto fixup = [&] {
         if (sk) hipLaunchKernelGGL((conv_streamk_fixup_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(sk_grid - 1), dim3(WAVES_M * WAVES_N * 64), 0, s, args, sk_grid);
     };
+    if (patch) {                                                   // k == s > 5, forward and data gradient: exact fp32 whatever `prec` asks for
+        hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WAVES_M, WAVES_N, false, true, 0, false, true>), grid, dim3(WAVES_M * WAVES_N * 64), 0, s, args);
+        fixup();
+        return launch_status(a.dgrad ? "somi_conv2d_dgrad_nhwc_f32 (patch)" : "somi_conv2d_nhwc_f32 (patch)");
+    }
     if (a.dgrad && a.d.dil > 1) {                                  // dilated data gradient (stride 1, never modulated): the DILBWD instantiations
         if constexpr (WAVES_M * WAVES_N == 8) {
             if (a.ns == 1 && fast)

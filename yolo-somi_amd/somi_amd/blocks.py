@@ -1070,19 +1070,109 @@ class Residual(nn.Module):
         self.fn = fn
 
 
-class SEAM(_Packed):
-    """models/common.py:8448-8505: dw3x3+GELU+BN -> Residual(dw3x3+GELU+BN) -> 1x1+GELU+BN -> GAP -> MLP -> x*exp(.)."""
+def _seam_stage(c2, act):
+    """One stage of SEAM's / MultiSEAM's DCovN (models/common.py:8458-8467, 8513-8522)."""
+    return nn.Sequential(Residual(nn.Sequential(nn.Conv2d(c2, c2, 3, 1, 1, groups=c2), act(), nn.BatchNorm2d(c2))),
+                         nn.Conv2d(c2, c2, 1, 1, 0, groups=1), act(), nn.BatchNorm2d(c2))
+
+
+def _seam_width_ok(c):
+    """What somi_dwconv3x3_bwd_workspace_floats accepts: C / 4 divides 256."""
+    return c % 4 == 0 and 256 % (c // 4) == 0
+
+
+class _SeamStages(_Packed):
+    """What SEAM and MultiSEAM share: the stages {Residual(dw3x3 -> act -> BN) -> 1x1 -> act -> BN} behind a stem -> act -> BN, the last of them
+    read by the global average pool only.  `_act` is the activation's name (in front of every BatchNorm: order 1)."""
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack_stage(self, st, dev):
+        f = lambda t: t.detach().float().contiguous().to(dev)   # noqa: E731
+        pk = dict(dw=f(st[0].fn[0].weight[:, 0].permute(1, 2, 0).reshape(9, -1)), b=f(st[0].fn[0].bias), pw=f(st[1].weight.flatten(1)),
+                  pb=f(st[1].bias))
+        if self.training:
+            pk['pwt'] = pack_dgrad_weight(st[1].weight.detach().float()).to(dev)
+        else:
+            pk['bn1'], pk['bn2'] = tuple(map(f, bn_fold(st[0].fn[2]))), tuple(map(f, bn_fold(st[3])))
+        return pk
+
+    def _bn_train(self, u, bn, residual=None):
+        """z = BN_batch(act(u)) [+ residual] (act before the norm, models/common.py:8455-8457; the Residual wrapper's add :7183 rides the same
+        pass); returns z and the saved statistics."""
+        dev, c, act = u.device, u.shape[3], self._act
+        if ops.SYNC_BN is None:
+            # two passes over u: the statistics of act(u) taken on the fly, then z = act(u) * scale + shift (order 1) - act(u) is never stored
+            # (the backward reads u too); three passes and a tensor less than act -> statistics -> affine
+            st, commit = _bn_train(bn, c, u, act=act)
+            z = ops.chan_affine_act(u, c, 0, st[2], st[3], act, 1, torch.empty_like(u), residual=residual)
+        else:
+            vec = _bn_clones(bn)
+            g = ops.chan_affine_act(u, c, 0, torch.ones(c, device=dev), torch.zeros(c, device=dev), act, 0, torch.empty_like(u))
+            st, commit = _bn_train(bn, c, g, vec=vec)
+            z = ops.chan_affine_act(g, c, 0, st[2], st[3], 'none', 0, g, residual=residual)
+        commit()
+        return z, st
+
+    def _stages_train(self, stages, pks, y0):
+        """y0: the stem's output.  -> (the (B, C) global average of the last stage's output, the context _stages_backward reads)."""
+        ctx = []
+        for i, (st, pk) in enumerate(zip(stages, pks)):
+            u1 = ops.dwconv3x3(y0, pk['dw'], pk['b'])
+            y1, s1 = self._bn_train(u1, st[0].fn[2], residual=y0)    # Residual: fn(y0) + y0
+            u2 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1)
+            if i + 1 < len(stages):
+                y2, s2 = self._bn_train(u2, st[3])
+            elif ops.SYNC_BN is None:
+                # BN(act(u2)) is read by the global average pool only, and the mean of an affine map is the affine map of the mean: the statistics
+                # pass, then ONE pass that averages act(u2) per image and applies scale / shift to the (B,C) result - the normalised tensor is
+                # never written
+                s2, commit = _bn_train(st[3], c := u2.shape[3], u2, act=self._act)
+                commit()
+                y2 = ops.global_pool_act(u2, self._act, s2[2], s2[3], c=c)
+            else:
+                y2, s2 = self._bn_train(u2, st[3])
+                y2, _ = ops.global_pool(y2, want_max=False)
+            ctx.append((y0, u1, s1, y1, u2, s2))
+            y0 = y2
+        return y0, ctx
+
+    def _stages_backward(self, stages, pks, ctx, davg):
+        """davg (B, C): the gradient of the average _stages_train returned.  Parameter gradients into .grad; -> the gradient of the stem's output."""
+        dy2 = None
+        for st, pk, (y0, u1, s1, y1, u2, s2) in reversed(list(zip(stages, pks, ctx))):
+            c, dev, act = u2.shape[3], u2.device, self._act
+            # the last y2 is read by the global average pool only: its gradient is davg / HW at every pixel - handed to the BatchNorm backward
+            # as such (no zero tensor filled, added to and read twice)
+            du2 = _bn_backward(st[3], dy2, 0, u2, s2, act, torch.empty_like(u2), c, order=1, pooled=(davg, None, None) if dy2 is None else None)
+            dy1 = _plain_conv_backward(st[1], Act(y1), du2, pk['pwt'], direct=('bias',)).t
+            du1 = _bn_backward(st[0].fn[2], dy1, 0, u1, s1, act, torch.empty_like(u1), c, order=1)
+            gw, gb = torch.zeros_like(pk['dw']), torch.zeros(c, device=dev)
+            dy2 = ops.dwconv3x3_backward(du1, y0, pk['dw'], gw, gb, dx_accumulate=dy1)       # + the residual branch
+            _acc_grad(st[0].fn[0].weight, gw.view(3, 3, c).permute(2, 0, 1).unsqueeze(1))
+            _acc_grad(st[0].fn[0].bias, gb)
+        return dy2
+
+    def _stages_eval(self, stages, pks, y0):
+        act = self._act
+        for st, pk in zip(stages, pks):
+            y1 = ops.dwconv3x3(y0, pk['dw'], pk['b'], *pk['bn1'], residual=y0, act=act)
+            y0 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1, act=act, post_scale=pk['bn2'][0], post_shift=pk['bn2'][1])
+        return ops.global_pool(y0, want_max=False)[0]
+
+
+class SEAM(_SeamStages):
+    """models/common.py:8448-8505: dw3x3+GELU+BN -> n x [Residual(dw3x3+GELU+BN) -> 1x1+GELU+BN] -> GAP -> MLP -> x*exp(.); the stages are
+    DCovN[3] ... DCovN[2 + n], as the reference spreads them."""
+    _act = 'gelu'
+    accumulates, folds_pooled, reduction = False, False, 1
 
     def __init__(self, c1, c2, n, reduction=16):
         super().__init__()
         if c1 != c2:
             c2 = c1
-        if n != 1:
-            raise NotImplementedError('SEAM with n != 1 is not on the SOMI path')
-        stage = nn.Sequential(
-            Residual(nn.Sequential(nn.Conv2d(c2, c2, 3, 1, 1, groups=c2), nn.GELU(), nn.BatchNorm2d(c2))),
-            nn.Conv2d(c2, c2, 1, 1, 0, groups=1), nn.GELU(), nn.BatchNorm2d(c2))
-        self.DCovN = nn.Sequential(nn.Conv2d(c1, c2, 3, 1, 1, groups=c1), nn.GELU(), nn.BatchNorm2d(c2), stage)
+        if not isinstance(n, int) or n < 1:
+            raise NotImplementedError(f'SEAM with n = {n!r} stages is not on the SOMI path (an int >= 1)')
+        self.DCovN = nn.Sequential(nn.Conv2d(c1, c2, 3, 1, 1, groups=c1), nn.GELU(), nn.BatchNorm2d(c2), *(_seam_stage(c2, nn.GELU) for _ in range(n)))
         self.fc = nn.Sequential(nn.Linear(c2, c2 // reduction, bias=False), nn.ReLU(inplace=True),
                                 nn.Linear(c2 // reduction, c2, bias=False), nn.Sigmoid())
         for m in self.modules():
@@ -1092,84 +1182,41 @@ class SEAM(_Packed):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
+    def _stages(self):
+        return list(self.DCovN)[3:]
+
     def _pack(self, dev):
         f = lambda t: t.detach().float().contiguous().to(dev)   # noqa: E731
-        dw = lambda conv: f(conv.weight[:, 0].permute(1, 2, 0).reshape(9, -1))   # noqa: E731  [9][C]
         d = self.DCovN
-        if self.training:
-            st = d[3]
-            return dict(dw0=dw(d[0]), b0=f(d[0].bias), dw1=dw(st[0].fn[0]), b1=f(st[0].fn[0].bias), pw=f(st[1].weight.flatten(1)),
-                        pb=f(st[1].bias), pwt=pack_dgrad_weight(st[1].weight.detach().float()).to(dev), W1=f(self.fc[0].weight),
-                        W2=f(self.fc[2].weight))
-        st = d[3]
-        pw = st[1]
-        return dict(dw0=dw(d[0]), b0=f(d[0].bias), bn0=tuple(map(f, bn_fold(d[2]))),
-                    dw1=dw(st[0].fn[0]), b1=f(st[0].fn[0].bias), bn1=tuple(map(f, bn_fold(st[0].fn[2]))),
-                    pw=f(pw.weight.flatten(1)), pb=f(pw.bias), bn2=tuple(map(f, bn_fold(st[3]))),
-                    W1=f(self.fc[0].weight), W2=f(self.fc[2].weight))
+        pk = dict(dw0=f(d[0].weight[:, 0].permute(1, 2, 0).reshape(9, -1)), b0=f(d[0].bias), stages=[self._pack_stage(st, dev) for st in self._stages()],
+                  W1=f(self.fc[0].weight), W2=f(self.fc[2].weight))
+        if not self.training:
+            pk['bn0'] = tuple(map(f, bn_fold(d[2])))
+        return pk
 
     # ------------------------------------------------------------------------------------------ training mode
-    accumulates, folds_pooled, reduction = False, False, 1
-
-    def _bn_train(self, u, bn, residual=None):
-        """z = BN_batch(GELU(u)) [+ residual] (act before the norm, models/common.py:8455-8457; the Residual wrapper's add :7183 rides the same
-        pass); returns z and the saved statistics."""
-        dev, c = u.device, u.shape[3]
-        if ops.SYNC_BN is None:
-            # two passes over u: the statistics of gelu(u) taken on the fly, then z = gelu(u) * scale + shift (order 1) - gelu(u) is never stored
-            # (the backward reads u too); three passes and a tensor less than act -> statistics -> affine
-            st, commit = _bn_train(bn, c, u, act='gelu')
-            z = ops.chan_affine_act(u, c, 0, st[2], st[3], 'gelu', 1, torch.empty_like(u), residual=residual)
-        else:
-            vec = _bn_clones(bn)
-            g = ops.chan_affine_act(u, c, 0, torch.ones(c, device=dev), torch.zeros(c, device=dev), 'gelu', 0, torch.empty_like(u))
-            st, commit = _bn_train(bn, c, g, vec=vec)
-            z = ops.chan_affine_act(g, c, 0, st[2], st[3], 'none', 0, g, residual=residual)
-        commit()
-        return z, st
-
     def _forward_train(self, x):
         self.invalidate()
         pk = self._packed(x.t.device)
-        d, st = self.DCovN, self.DCovN[3]
         u0 = ops.dwconv3x3(x.t, pk['dw0'], pk['b0'])
-        y0, s0 = self._bn_train(u0, d[2])
-        u1 = ops.dwconv3x3(y0, pk['dw1'], pk['b1'])
-        y1, s1 = self._bn_train(u1, st[0].fn[2], residual=y0)    # Residual: fn(y0) + y0
-        u2 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1)
-        if ops.SYNC_BN is None:
-            # BN(GELU(u2)) is read by the global average pool only, and the mean of an affine map is the affine map of the mean: the statistics pass,
-            # then ONE pass that averages gelu(u2) per image and applies scale / shift to the (B,C) result - the normalised tensor is never written
-            s2, commit = _bn_train(st[3], c := u2.shape[3], u2, act='gelu')
-            commit()
-            avg = ops.global_pool_act(u2, 'gelu', s2[2], s2[3], c=c)
-        else:
-            y2, s2 = self._bn_train(u2, st[3])
-            avg, _ = ops.global_pool(y2, want_max=False)
+        y0, s0 = self._bn_train(u0, self.DCovN[2])
+        avg, ctx = self._stages_train(self._stages(), pk['stages'], y0)
         sc = ops.attn_mlp(1, avg, None, pk['W1'], None, pk['W2'], None)
-        self.__dict__['_ctx'] = (x, u0, s0, y0, u1, s1, y1, u2, s2, avg, sc, pk)
+        self.__dict__['_ctx'] = (x, u0, s0, ctx, avg, sc, pk)
         return Act(ops.scale_channels(x.t, sc), 0, x.c)
 
     def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         if dx_out is not None or accumulate:
             raise NotImplementedError('SEAM writes its own input gradient')
-        x, u0, s0, y0, u1, s1, y1, u2, s2, avg, sc, pk = self.__dict__.pop('_ctx')
-        d, st = self.DCovN, self.DCovN[3]
+        x, u0, s0, ctx, avg, sc, pk = self.__dict__.pop('_ctx')
+        d = self.DCovN
         c = x.c
         dev = x.t.device
         dx, dsc = ops.scale_channels_backward(dout.t, x.t, sc)
         (gW1, gW2), fin = _grad_targets(self.fc[0].weight, self.fc[2].weight)
         davg, _ = ops.attn_mlp_backward(1, dsc, sc, avg, None, pk['W1'], None, pk['W2'], gW1, None, gW2, None)
         fin()
-        # y2 is read by the global average pool only: its gradient is davg / HW at every pixel - handed to the BatchNorm backward as such
-        # (no zero tensor filled, added to and read twice)
-        du2 = _bn_backward(st[3], None, 0, u2, s2, 'gelu', torch.empty_like(u2), c, order=1, pooled=(davg, None, None))     # of BN(GELU(u)): order 1
-        dy1 = _plain_conv_backward(st[1], Act(y1), du2, pk['pwt'], direct=('bias',)).t
-        du1 = _bn_backward(st[0].fn[2], dy1, 0, u1, s1, 'gelu', torch.empty_like(u1), c, order=1)
-        gw, gb = torch.zeros_like(pk['dw1']), torch.zeros(c, device=dev)
-        dy0 = ops.dwconv3x3_backward(du1, y0, pk['dw1'], gw, gb, dx_accumulate=dy1)       # + the residual branch
-        _acc_grad(st[0].fn[0].weight, gw.view(3, 3, c).permute(2, 0, 1).unsqueeze(1))
-        _acc_grad(st[0].fn[0].bias, gb)
+        dy0 = self._stages_backward(self._stages(), pk['stages'], ctx, davg)
         du0 = _bn_backward(d[2], dy0, 0, u0, s0, 'gelu', torch.empty_like(u0), c, order=1)
         gw0, gb0 = torch.zeros_like(pk['dw0']), torch.zeros(c, device=dev)
         dx = ops.dwconv3x3_backward(du0, x.t, pk['dw0'], gw0, gb0, dx_accumulate=dx)
@@ -1184,11 +1231,115 @@ class SEAM(_Packed):
             return self._forward_train(x)
         pk = self._packed(x.t.device)
         y0 = ops.dwconv3x3(x.t, pk['dw0'], pk['b0'], *pk['bn0'], act='gelu')
-        y1 = ops.dwconv3x3(y0, pk['dw1'], pk['b1'], *pk['bn1'], residual=y0, act='gelu')
-        y2 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1, act='gelu', post_scale=pk['bn2'][0],
-                             post_shift=pk['bn2'][1])
-        avg, _ = ops.global_pool(y2, want_max=False)
+        avg = self._stages_eval(self._stages(), pk['stages'], y0)
         s = ops.attn_mlp(1, avg, None, pk['W1'], None, pk['W2'], None)
+        return Act(ops.scale_channels(x.t, s), 0, x.c)
+
+
+class MultiSEAM(_SeamStages):
+    """models/common.py:8508-8555: three DcovN branches - a patch-embedding conv (k = s = p, with bias) + SiLU + BN, then `depth` stages
+    {Residual(dw3x3+SiLU+BN) -> 1x1+SiLU+BN} - whose global averages and that of x itself are averaged, -> MLP -> x*exp(.).  Torch's default
+    initialisation (the reference's MultiSEAM does not call SEAM's xavier initialiser).  Everything behind the patch convs works on maps p^2
+    times smaller; no full-resolution tensor exists besides the output and dx."""
+    _act = 'silu'
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def __init__(self, c1, c2, depth, kernel_size=3, patch_size=[3, 5, 7], reduction=16):    # noqa: B006  (the reference's signature)
+        super().__init__()
+        if c1 != c2:
+            c2 = c1
+        if kernel_size != 3:
+            raise NotImplementedError(f'MultiSEAM with kernel_size {kernel_size!r}: the reference fixes padding=1, so only kernel_size 3 keeps the map size')
+        if (not isinstance(patch_size, (list, tuple)) or len(patch_size) != 3 or
+                not all(isinstance(p, int) and not isinstance(p, bool) and p > 0 for p in patch_size)):
+            raise NotImplementedError(f'MultiSEAM with patch_size {patch_size!r}: three positive ints (one per DCovN branch)')
+        if not isinstance(depth, int) or depth < 1:
+            raise NotImplementedError(f'MultiSEAM with depth = {depth!r} is not on the SOMI path (an int >= 1)')
+        if not _seam_width_ok(c2):
+            raise NotImplementedError(f'MultiSEAM at {c2} channels: the depthwise 3x3 backward takes widths whose quarter divides 256 (4 ... 1024)')
+        self.patch_size = tuple(patch_size)
+        for j, p in enumerate(self.patch_size):
+            setattr(self, f'DCovN{j}', nn.Sequential(nn.Conv2d(c1, c2, kernel_size=p, stride=p), nn.SiLU(), nn.BatchNorm2d(c2),
+                                                     *(_seam_stage(c2, nn.SiLU) for _ in range(depth))))
+        self.fc = nn.Sequential(nn.Linear(c2, c2 // reduction, bias=False), nn.ReLU(inplace=True),
+                                nn.Linear(c2 // reduction, c2, bias=False), nn.Sigmoid())
+
+    def _branches(self):
+        return [getattr(self, f'DCovN{j}') for j in range(3)]
+
+    def _pack(self, dev):
+        f = lambda t: t.detach().float().contiguous().to(dev)   # noqa: E731
+        pk = dict(W1=f(self.fc[0].weight), W2=f(self.fc[2].weight), br=[])
+        for d in self._branches():
+            w = d[0].weight.detach().float()
+            b = dict(w=pack_conv_weight(w).to(dev), b=f(d[0].bias), stages=[self._pack_stage(st, dev) for st in list(d)[3:]])
+            if self.training:
+                b['wt'] = pack_dgrad_weight(w).to(dev)
+            else:
+                b['bn0'] = tuple(map(f, bn_fold(d[2])))
+            pk['br'].append(b)
+        return pk
+
+    def _check(self, x):
+        if x.coff != 0 or x.t.shape[3] != x.c or x.c % 4:
+            raise NotImplementedError('MultiSEAM input must be a whole tensor with channels a multiple of 4')
+        H, W, p = x.t.shape[1], x.t.shape[2], max(self.patch_size)
+        if H < p or W < p:
+            raise RuntimeError(f'MultiSEAM: a {H} x {W} map is smaller than its largest patch, {p} x {p}')
+
+    # ------------------------------------------------------------------------------------------ training mode
+    def _forward_train(self, x):
+        self.invalidate()
+        pk = self._packed(x.t.device)
+        avgs, ctx = [], []
+        for d, b, p in zip(self._branches(), pk['br'], self.patch_size):
+            u0 = ops.conv2d_nhwc(x.t, b['w'], b['b'], kh=p, kw=p, stride=p, pad=0)       # bias, no activation: the backward reads u0
+            y0, s0 = self._bn_train(u0, d[2])
+            a, c = self._stages_train(list(d)[3:], b['stages'], y0)
+            avgs.append(a)
+            ctx.append((u0, s0, c))
+        ax, _ = ops.global_pool(x.t, want_max=False)
+        avg = (avgs[0] + avgs[1] + avgs[2] + ax) / 4                    # four (B, C) vectors
+        sc = ops.attn_mlp(1, avg, None, pk['W1'], None, pk['W2'], None)
+        self.__dict__['_ctx'] = (x, ctx, avg, sc, pk)
+        return Act(ops.scale_channels(x.t, sc), 0, x.c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('MultiSEAM writes its own input gradient')
+        x, ctx, avg, sc, pk = self.__dict__.pop('_ctx')
+        B, H, W, c = x.t.shape
+        dev = x.t.device
+        dx, dsc = ops.scale_channels_backward(dout.t, x.t, sc)
+        (gW1, gW2), fin = _grad_targets(self.fc[0].weight, self.fc[2].weight)
+        davg, _ = ops.attn_mlp_backward(1, dsc, sc, avg, None, pk['W1'], None, pk['W2'], gW1, None, gW2, None)
+        fin()
+        dq = davg / 4                                                   # a quarter to each of the four pools
+        if need_dx:
+            ops.pool_backward_add_(dx, 0, c, dq)                         # x's own pool: davg / (4 HW) at every pixel
+        for d, b, p, (u0, s0, sctx) in zip(self._branches(), pk['br'], self.patch_size, ctx):
+            dy0 = self._stages_backward(list(d)[3:], b['stages'], sctx, dq)
+            du0 = _bn_backward(d[2], dy0, 0, u0, s0, 'silu', torch.empty_like(u0), c, order=1)
+            dw = ops.conv2d_wgrad_nhwc(x.t, du0, kh=p, kw=p, stride=p, pad=0, cin=c, cout=c)
+            _acc_grad(d[0].weight, dw.view(c, p, p, c).permute(0, 3, 1, 2))
+            (db,), fin = _grad_targets(d[0].bias)
+            ops.chan_sum_(du0, c, 0, db)
+            fin()
+            if need_dx:                                                 # the pixels beyond Ho * p, which no tap reaches, keep what dx holds
+                ops.conv2d_dgrad_nhwc(du0, b['wt'], B=B, H=H, W=W, cin=c, kh=p, kw=p, stride=p, pad=0, cout=c, out=dx, accumulate=dx)
+        return Act(dx, 0, c) if need_dx else None
+
+    def forward(self, x):
+        self._check(x)
+        if self.training:
+            return self._forward_train(x)
+        pk = self._packed(x.t.device)
+        avgs = []
+        for d, b, p in zip(self._branches(), pk['br'], self.patch_size):
+            y0 = ops.conv2d_nhwc(x.t, b['w'], b['b'], kh=p, kw=p, stride=p, pad=0, act='silu', post_scale=b['bn0'][0], post_shift=b['bn0'][1])
+            avgs.append(self._stages_eval(list(d)[3:], b['stages'], y0))
+        ax, _ = ops.global_pool(x.t, want_max=False)
+        s = ops.attn_mlp(1, (avgs[0] + avgs[1] + avgs[2] + ax) / 4, None, pk['W1'], None, pk['W2'], None)
         return Act(ops.scale_channels(x.t, s), 0, x.c)
 
 

@@ -79,14 +79,20 @@ def _swap_upsample(rows, upsample):
     return [[r[0], r[1], *copy.deepcopy(swap)] if r[2] == 'nn.Upsample' else r for r in rows]
 
 
-def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8, upsample='nearest'):
+def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8, upsample='nearest', seam='seam', seam_depth=1):
     """The layer table of models/modules/YOLO-SOMI.yaml as a dict (C2fEACBAM -> C2fCBAM).
 
     dcn=True: "yolov5l-SOMI (DCNv3 blocks)" of BASELINE configs[1].  The reference vendors DCNv3 but wires it into no yaml (SURVEY
     fact 3), so the sites are the build's choice: one DCNv3_YOLO block (DCNv3 -> BN -> SiLU, 3x3, `dcn_group` groups) behind each of
     the two high-resolution lateral convs of the neck - P2 (160x160 at 640) and P3 (80x80), 256 channels: the representative
     shapes of SURVEY section 8a row F10.  Later layers shift by one / two; their `from` indices are rewritten accordingly.
-    upsample='carafe' | 'dysample': the neck's three nn.Upsample rows become the learned upsampler (UPSAMPLE_ROWS)."""
+    upsample='carafe' | 'dysample': the neck's three nn.Upsample rows become the learned upsampler (UPSAMPLE_ROWS).
+    seam='multi': the neck's three SEAM rows become MultiSEAM (models/common.py:8527-8555, registered beside SEAM at models/yolo.py:1475) with
+    `seam_depth` stages per branch; seam='seam' with seam_depth > 1: SEAM with that many stages.  The defaults give the shipped table."""
+    if seam not in ('seam', 'multi'):
+        raise ValueError(f"seam={seam!r} ('seam' or 'multi')")
+    if not isinstance(seam_depth, int) or seam_depth < 1:
+        raise ValueError(f'seam_depth={seam_depth!r} (an int >= 1)')
     bb = [[-1, 1, 'Conv', [64, 3, 2]], [-1, 1, 'ODConv_3rd', [128, 3, 2, 4]], [-1, 3, 'C2fCBAM', [128, True]],
           [-1, 1, 'Conv', [256, 3, 2]], [-1, 6, 'C2fCBAM', [256, True]], [-1, 1, 'Conv', [512, 3, 2]],
           [-1, 6, 'C2fCBAM', [512, True]], [-1, 1, 'Conv', [1024, 3, 2]], [-1, 3, 'C2fCBAM', [1024, True]],
@@ -102,6 +108,10 @@ def somi_cfg(width=1.0, depth=1.0, nc=10, anchors=4, dcn=False, dcn_group=8, ups
           [[25, 28, 31, 34], 1, 'DecoupledDetect', ['nc', 'anchors']]]
     import copy
     bb, hd = copy.deepcopy(bb), copy.deepcopy(hd)
+    if seam == 'multi' or seam_depth > 1:
+        for l in hd:
+            if l[2] == 'SEAM':
+                l[2:] = ['MultiSEAM', [256, seam_depth]] if seam == 'multi' else ['SEAM', [256, seam_depth, 16]]
     if dcn:
         layers = bb + hd
         for after in (11, 10):                                   # insert behind layer 11 first, so that index 10 stays valid

@@ -32,7 +32,8 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'C3Ghost': B.C3Ghost, 'C2f': B.C2f, 'SCDown': B.SCDown, 'C2fCIB': B.C2fCIB, 'PSA': B.PSA,
        'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR,        # models/yolo.py:1472-1479
        'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention,        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
-       'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR}                      # the dilated-conv context blocks, models/yolo.py:1472-1492
+       'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR,                      # the dilated-conv context blocks, models/yolo.py:1472-1492
+       'MultiSEAM': B.MultiSEAM}                                  # in SEAM's branch (models/yolo.py:1475), not repeated inside (:1487-1490)
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
 _REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
