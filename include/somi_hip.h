@@ -405,6 +405,58 @@ int somi_coordatt_apply_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stre
 int somi_coordatt_bwd_gates_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
 int somi_coordatt_bwd_input_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
 
+/* Channel prior convolutional attention (CPCA, CPCABottleneck: models/common.py:5753-5859; cpca.hip): the strip part
+ *   s = u + V7(H7(u)) + V11(H11(u)) + V21(H21(u)),  H_k the depthwise (1,k) conv along W, V_k the depthwise (k,1) conv along H, zero padding k / 2,
+ * and the element-wise passes of the block; its 1x1 conv, GELU, depthwise 5x5, global pools and channel scale run on the existing entries.
+ * Every tensor is a channel slice of width C (a multiple of 4) of a (B,H,W,.) tensor.  Tap tensors w[k] are (C, taps[k]) floats - how
+ * nn.Conv2d stores (C,1,1,k) and (C,1,k,1) -, biases (C) floats; neither needs any alignment beyond a float's.  taps must be (7, 11, 21).
+ * fan-out (somi_cpca_fanout_nhwc_f32): dst[k] = S_k(src[0]) [+ bias[k]] for the three tap sets; src[0] is read once.
+ * fan-in  (somi_cpca_fanin_nhwc_f32):  dst[0] = [dst[0] +] src[3] + sum_k (S_k(src[k]) [+ bias[k]]); `accumulate` adds to what dst[0] holds.
+ * axis 0: S_k runs along W, 1: along H.  flip: the taps are walked backwards (the transposed conv of the data gradient).  bias[k] NULL: none.
+ * Training forward: fan-out along W, fan-in along H (9 tensor passes, the three t_k = dst of the fan-out kept); data gradient: fan-out along H
+ * of ds, flipped, no bias -> dt_k; fan-in along W of dt_k, flipped, no bias, src[3] = ds -> du.
+ * wgrad (somi_cpca_wgrad_nhwc_f32): from u, t_k, ds, dt_k all 78 tap gradients, dw_h[k] (C, taps[k]) and dw_v[k] likewise, and the six bias
+ * gradients db_h[k] = sum dt_k, db_v[k] = sum ds (C each), written, or added to what they hold with `accumulate`; a NULL target is skipped.
+ * Per-workgroup rows of partials in `workspace` (somi_cpca_wgrad_workspace_floats floats, 16-byte aligned), then a fixed-order tree.
+ * No float atomics anywhere: two launches are bit-identical. */
+typedef struct somi_cpca_strip_desc {
+    somi_slice src[4];         /* fan-out: src[0]; fan-in: src[0..2] the three branch tensors, src[3] the pass-through */
+    somi_slice dst[3];         /* fan-out: the three results; fan-in: dst[0] */
+    const float *w[3];
+    const float *bias[3];
+    int32_t taps[3];           /* 7, 11, 21 */
+    int32_t axis, flip, accumulate;
+    int32_t B, H, W, C;
+} somi_cpca_strip_desc;
+typedef struct somi_cpca_wgrad_desc {
+    somi_slice u, t[3], ds, dt[3];
+    float *dw_h[3], *dw_v[3], *db_h[3], *db_v[3];
+    int32_t taps[3];
+    int32_t accumulate;
+    int32_t B, H, W, C;
+    float *workspace;
+    uint64_t workspace_floats;
+} somi_cpca_wgrad_desc;
+size_t somi_cpca_strip_desc_bytes(void);
+size_t somi_cpca_wgrad_desc_bytes(void);
+int somi_cpca_fanout_nhwc_f32(const somi_cpca_strip_desc *d, somi_stream_t stream);
+int somi_cpca_fanin_nhwc_f32(const somi_cpca_strip_desc *d, somi_stream_t stream);
+size_t somi_cpca_wgrad_workspace_floats(int B, int H, int W, int C);
+/* How many tiles in a row a workgroup of the strip kernels (wgrad = 0) or of the weight gradient's first stage (wgrad = 1) walks along
+ * `axis` at this shape - host arithmetic: 4 (32) halved while fewer than 1024 (512) workgroups exist.  0 for sizes the kernels refuse. */
+int somi_cpca_tiles_per_workgroup(int B, int H, int W, int C, int axis, int wgrad);
+int somi_cpca_wgrad_nhwc_f32(const somi_cpca_wgrad_desc *d, somi_stream_t stream);
+/* out = x * y (the gate product conv(s) * a), and its backward dx = dout * y, dy = dout * x; npix pixels, slices of width C */
+int somi_cpca_gate_nhwc_f32(somi_slice x, somi_slice y, somi_slice out, long npix, int C, somi_stream_t stream);
+int somi_cpca_gate_bwd_nhwc_f32(somi_slice dout, somi_slice x, somi_slice y, somi_slice dx, somi_slice dy, long npix, int C, somi_stream_t stream);
+/* CPCA_ChannelAttention's sum of two sigmoids: z (2B, C) = the shared MLP on the B average rows, then on the B maximum rows;
+ * g[b][c] = sigmoid(z[b][c]) + sigmoid(z[B + b][c]);  backward: dz (2B, C) from dg (B, C). */
+int somi_cpca_sigmoid2_f32(const float *z, float *g, int B, int C, somi_stream_t stream);
+int somi_cpca_sigmoid2_bwd_f32(const float *z, const float *dg, float *dz, int B, int C, somi_stream_t stream);
+/* amaxp[b][c] = the first pixel p with x[b,p,c] == mx[b][c], mx the spatial maximum somi_global_pool_nhwc_f32 took of the same tensor: what
+ * somi_pool_bwd_add_nhwc_f32 needs.  An integer minimum over the matching pixels, independent of the order. */
+int somi_cpca_argmax_pixel_nhwc_f32(somi_slice x, const float *mx, int32_t *amaxp, int B, int HW, int C, somi_stream_t stream);
+
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed
  * inside the kernel from the raw parameter w_dev (n_in floats on the device; no host copy of it is needed).

@@ -69,6 +69,20 @@ class CoordAttDesc(C.Structure):
                 ('workspace_floats', C.c_uint64)]
 
 
+class CpcaStripDesc(C.Structure):
+    """struct somi_cpca_strip_desc (include/somi_hip.h)."""
+    _fields_ = [('src', Slice * 4), ('dst', Slice * 3), ('w', C.c_void_p * 3), ('bias', C.c_void_p * 3), ('taps', C.c_int32 * 3),
+                ('axis', C.c_int32), ('flip', C.c_int32), ('accumulate', C.c_int32), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('C', C.c_int32)]
+
+
+class CpcaWgradDesc(C.Structure):
+    """struct somi_cpca_wgrad_desc (include/somi_hip.h)."""
+    _fields_ = [('u', Slice), ('t', Slice * 3), ('ds', Slice), ('dt', Slice * 3), ('dw_h', C.c_void_p * 3), ('dw_v', C.c_void_p * 3),
+                ('db_h', C.c_void_p * 3), ('db_v', C.c_void_p * 3), ('taps', C.c_int32 * 3), ('accumulate', C.c_int32), ('B', C.c_int32),
+                ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -224,6 +238,18 @@ SIGNATURES = {
     'somi_coordatt_apply_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
     'somi_coordatt_bwd_gates_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
     'somi_coordatt_bwd_input_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
+    'somi_cpca_strip_desc_bytes': (Z, []),
+    'somi_cpca_wgrad_desc_bytes': (Z, []),
+    'somi_cpca_fanout_nhwc_f32': (I, [C.POINTER(CpcaStripDesc), S]),
+    'somi_cpca_fanin_nhwc_f32': (I, [C.POINTER(CpcaStripDesc), S]),
+    'somi_cpca_wgrad_workspace_floats': (Z, [I, I, I, I]),
+    'somi_cpca_tiles_per_workgroup': (I, [I, I, I, I, I, I]),
+    'somi_cpca_wgrad_nhwc_f32': (I, [C.POINTER(CpcaWgradDesc), S]),
+    'somi_cpca_gate_nhwc_f32': (I, [Slice, Slice, Slice, C.c_long, I, S]),
+    'somi_cpca_gate_bwd_nhwc_f32': (I, [Slice, Slice, Slice, Slice, Slice, C.c_long, I, S]),
+    'somi_cpca_sigmoid2_f32': (I, [P, P, I, I, S]),
+    'somi_cpca_sigmoid2_bwd_f32': (I, [P, P, P, I, I, S]),
+    'somi_cpca_argmax_pixel_nhwc_f32': (I, [Slice, P, P, I, I, I, S]),
     'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
@@ -274,7 +300,9 @@ def lib():
             raise RuntimeError('libsomi_hip.so ABI version mismatch')
         if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)
                         or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)
-                        or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)):
+                        or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)
+                        or L.somi_cpca_strip_desc_bytes() != C.sizeof(CpcaStripDesc)
+                        or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

@@ -2461,6 +2461,238 @@ class C3_CA(C3):
     accumulates, folds_pooled, reduction = False, False, 1       # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
 
 
+class CPCA_ChannelAttention(_Packed):
+    """t * (sigmoid(MLP(avgpool t)) + sigmoid(MLP(maxpool t))) (models/common.py:5753-5779): the shared MLP - two 1x1 convs with bias on a 1x1
+    map, i.e. two small dense layers - runs once on the 2B rows (averages, then maxima) one pooling pass leaves; each half gets its own sigmoid
+    before the sum (CBAM sums first)."""
+
+    def __init__(self, input_channels, internal_neurons):
+        super().__init__()
+        self.fc1 = nn.Conv2d(in_channels=input_channels, out_channels=internal_neurons, kernel_size=1, stride=1, bias=True)
+        self.fc2 = nn.Conv2d(in_channels=internal_neurons, out_channels=input_channels, kernel_size=1, stride=1, bias=True)
+        self.input_channels = input_channels
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def _pack(self, dev):
+        return tuple(t.detach().float().contiguous().to(dev) for t in (self.fc1.weight.flatten(1), self.fc1.bias, self.fc2.weight.flatten(1),
+                                                                       self.fc2.bias))
+
+    def forward(self, x):
+        """x: a whole unpadded tensor as an Act.  -> x * g as an Act of its own."""
+        c = self.input_channels
+        if x.coff != 0 or x.t.shape[3] != c or x.c != c:
+            raise NotImplementedError(f'CPCA_ChannelAttention({c}) works on whole tensors of {c} channels')
+        if self.fc1.out_channels < 1:
+            raise NotImplementedError(f'CPCA_ChannelAttention({c}, {self.fc1.out_channels}): the MLP needs at least one hidden neuron')
+        if c > 1024:
+            raise NotImplementedError(f'CPCA_ChannelAttention({c}): the shared MLP runs on the small dense layer, at most 1024 channels')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd CPCA runs on the MI355X only (no CPU fallback)')
+        W1, b1, W2, b2 = self._packed(x.t.device)
+        B = x.shape[0]
+        pooled = torch.empty(2 * B, c, device=x.t.device, dtype=torch.float32)
+        ops.global_pool(x.t, c=c, out=pooled)
+        h = ops.linear(pooled, W1, b1, 'relu')
+        z = ops.linear(h, W2, b2, 'none')
+        g = ops.cpca_sigmoid2(z)
+        if self.training:
+            self.__dict__['_ctx'] = (x, pooled, h, z, g, (W1, W2))
+        return Act(ops.scale_channels(x.t, g), 0, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """dout: the gradient of x * g, a whole tensor (Act or tensor).  -> the gradient of x as an Act: a tensor of its own, or copied into
+        dx_out's slice (added to it with `accumulate`) by one more pass; None without need_dx (the MLP's gradients are still taken)."""
+        x, pooled, h, z, g, (W1, W2) = self.__dict__.pop('_ctx')
+        d = dout.t if isinstance(dout, Act) else dout
+        B, c = g.shape
+        dt, dg = ops.scale_channels_backward(d, x.t, g)
+        dz = ops.cpca_sigmoid2_backward(z, dg)
+        (gW1, gb1, gW2, gb2), fin = _grad_targets(self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        dh = torch.empty_like(h)
+        ops.linear_backward(h, W2, dz, z, 0, 'none', gW2, gb2, dx=dh)
+        dpooled = torch.empty_like(pooled)
+        ops.linear_backward(pooled, W1, dh, h, 0, 'relu', gW1, gb1, dx=dpooled)
+        fin()
+        if not need_dx:
+            return None
+        amaxp = ops.argmax_pixel(x.t, pooled[B:], c)
+        ops.pool_backward_add_(dt, 0, c, dpooled[:B], dpooled[B:], amaxp)
+        if dx_out is None:
+            return Act(dt, 0, c)
+        if accumulate:
+            ops.add_(dx_out.t, dx_out.coff, dt, 0, c)
+        else:
+            ops.resample_slice(dt, 0, dx_out.t, dx_out.coff, c)
+        return Act(dx_out.t, dx_out.coff, c)
+
+
+_CPCA_STRIPS = (('dconv1_7', 'dconv7_1', 7), ('dconv1_11', 'dconv11_1', 11), ('dconv1_21', 'dconv21_1', 21))
+
+
+class _CPCACore(_Packed):
+    """The arithmetic CPCA and CPCABottleneck share (models/common.py:5797-5815, 5842-5857), on the children `ca`, `dconv5_5`, the six strip
+    convs, `conv` and `act` of the class that mixes this in:
+        a = ca(gelu(conv(x)));  u = dconv5_5(a);  s = u + V7(H7(u)) + V11(H11(u)) + V21(H21(u));  out = [s +] conv(conv(s) * a)
+    `conv` is ONE 1x1 conv with bias used three times: its weight and bias gradients are the sum over the three uses, accumulated into one
+    buffer by the existing wgrad and channel-sum kernels.  The strips are two launches forward (ops.cpca_fanout along W, ops.cpca_fanin along H),
+    two for the data gradient (the same kernels with the axes swapped and the taps flipped) and one call for all twelve strip parameter
+    gradients (ops.cpca_wgrad).  GELU rides the conv epilogue in eval; in training the pre-activation is kept.  The bottleneck's shortcut
+    adds s, the strip sum - the reference's forward rebinds the name `x` to it before `return x + out` (models/common.py:5854, 5859), so that
+    is what a trained checkpoint expects -; it rides the last conv's epilogue forward and the second conv's dgrad epilogue backward.  All inner tensors are whole tensors of exactly C channels: C must be a width pad4 leaves alone."""
+
+    def _init_cpca(self, c, r):
+        self.ca = CPCA_ChannelAttention(input_channels=c, internal_neurons=c // r)
+        self.dconv5_5 = nn.Conv2d(c, c, kernel_size=5, padding=2, groups=c)
+        self.dconv1_7 = nn.Conv2d(c, c, kernel_size=(1, 7), padding=(0, 3), groups=c)
+        self.dconv7_1 = nn.Conv2d(c, c, kernel_size=(7, 1), padding=(3, 0), groups=c)
+        self.dconv1_11 = nn.Conv2d(c, c, kernel_size=(1, 11), padding=(0, 5), groups=c)
+        self.dconv11_1 = nn.Conv2d(c, c, kernel_size=(11, 1), padding=(5, 0), groups=c)
+        self.dconv1_21 = nn.Conv2d(c, c, kernel_size=(1, 21), padding=(0, 10), groups=c)
+        self.dconv21_1 = nn.Conv2d(c, c, kernel_size=(21, 1), padding=(10, 0), groups=c)
+        self.conv = nn.Conv2d(c, c, kernel_size=(1, 1), padding=0)
+        self.act = nn.GELU()
+
+    def _strip_params(self):
+        hs = [getattr(self, h) for h, _, _ in _CPCA_STRIPS]
+        vs = [getattr(self, v) for _, v, _ in _CPCA_STRIPS]
+        return hs, vs
+
+    def _pack_params(self):
+        hs, vs = self._strip_params()
+        return [*self.conv.parameters(), *self.dconv5_5.parameters(), *(p for m in hs + vs for p in m.parameters())]
+
+    def _pack(self, dev):
+        c = self.conv.in_channels
+        f = lambda t: t.detach().float().contiguous().to(dev)       # noqa: E731
+        hs, vs = self._strip_params()
+        w = self.conv.weight.detach().float()
+        pk = dict(wh=[f(m.weight) for m in hs], bh=[f(m.bias) for m in hs], wv=[f(m.weight) for m in vs], bv=[f(m.bias) for m in vs],
+                  g5=pack_gconv_weight(self.dconv5_5.weight.detach(), c).to(dev), b5=f(self.dconv5_5.bias))
+        pk['wp'], pk['bp'] = pack_conv_weight(w, cin_pad=c, cout_pad=c).to(dev), f(self.conv.bias)
+        if self.training:
+            pk['wt'] = pack_dgrad_weight(w, cin_pad=c, cout_pad=c).to(dev)
+            pk['one'], pk['zero'] = torch.ones(c, device=dev), torch.zeros(c, device=dev)
+        return pk
+
+    def _cpca_forward(self, x, add_s, out):
+        """x: the attended map (Act of C channels); add_s: the bottleneck's shortcut, + s; out: the Act to write (a new one when None)."""
+        c = self.conv.in_channels
+        if x.c != c:
+            raise RuntimeError(f'CPCA over {c} channels got a map of {x.c}')
+        if c % 4 or pad4(c) != c or x.up:
+            raise NotImplementedError(f'CPCA over {c} channels: the strip kernels need a real tensor whose channel count is a multiple of 4 and '
+                                      f'stored unpadded (a multiple of 32 from 64 up)')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd CPCA runs on the MI355X only (no CPU fallback)')
+        pk = self._packed(x.t.device)
+        B, H, W, _ = x.shape
+        conv = dict(kh=1, kw=1, stride=1, pad=0, cin=c, cout=c)
+        y0 = None
+        if self.training:
+            y0 = ops.conv2d_nhwc(x.t, pk['wp'], pk['bp'], act='none', x_coff=x.coff, **conv)
+            t = ops.chan_affine_act(y0, c, 0, pk['one'], pk['zero'], 'gelu', 0, torch.empty_like(y0))
+        else:
+            t = ops.conv2d_nhwc(x.t, pk['wp'], pk['bp'], act='gelu', x_coff=x.coff, **conv)
+        a = self.ca(Act(t, 0, c))
+        u = ops.gconv2d_nhwc(a.t, pk['g5'], pk['b5'], c1=c, c2=c, groups=c, k=5)
+        ts = ops.cpca_fanout(u, pk['wh'], pk['bh'], c, axis='w')
+        s = ops.cpca_fanin(ts, u, pk['wv'], pk['bv'], c, axis='h')
+        sa = ops.conv2d_nhwc(s, pk['wp'], pk['bp'], act='none', **conv)
+        p = ops.cpca_gate(sa, a.t, c)
+        if out is None:
+            out = new_act(x.t, H, W, c)
+        ops.conv2d_nhwc(p, pk['wp'], pk['bp'], act='none', out=out.t, y_coff=out.coff, residual=s if add_s else None, **conv)
+        if self.training:
+            self.__dict__['_cctx'] = (x, y0, a, u, ts, s, sa, p, pk, add_s)
+        return Act(out.t, out.coff, c)
+
+    def _cpca_backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """dout: the gradient of the output (Act).  -> the gradient of the attended map as an Act (written into dx_out if given, added to it with
+        `accumulate`).  Every parameter gradient is accumulated into .grad."""
+        x, y0, a, u, ts, s, sa, p, pk, add_s = self.__dict__.pop('_cctx')
+        c = self.conv.in_channels
+        B, H, W, _ = x.shape
+        direct = ('weight', 'bias')
+        dp = _plain_conv_backward(self.conv, Act(p, 0, c), dout.t, pk['wt'], dy_coff=dout.coff, direct=direct)
+        dsa, da = ops.cpca_gate_backward(dp.t, sa, a.t, c)
+        _plain_conv_backward(self.conv, Act(s, 0, c), dsa, pk['wt'], need_dx=False, direct=direct)
+        ds = torch.empty_like(s)                                  # + dout where the shortcut added s
+        ops.conv2d_dgrad_nhwc(dsa, pk['wt'], B=B, H=H, W=W, cin=c, kh=1, kw=1, cout=c, out=ds, accumulate=dout.t if add_s else None,
+                              acc_coff=dout.coff)
+        dts = ops.cpca_fanout(ds, pk['wv'], None, c, axis='h', flip=True)
+        du = ops.cpca_fanin(dts, ds, pk['wh'], None, c, axis='w', flip=True)
+        hs, vs = self._strip_params()
+        tg, fin = _grad_targets(*(m.weight for m in hs), *(m.weight for m in vs), *(m.bias for m in hs), *(m.bias for m in vs))
+        ops.cpca_wgrad(u, ts, ds, dts, c, tg[0:3], tg[3:6], tg[6:9], tg[9:12], accumulate=True)
+        fin()
+        (gw5, gb5), fin = _grad_targets(self.dconv5_5.weight, self.dconv5_5.bias)
+        ops.gconv2d_wgrad_nhwc(a.t, du, c1=c, c2=c, groups=c, k=5, out=gw5, accumulate=True)
+        ops.chan_sum_(du, c, 0, gb5)
+        fin()
+        ops.gconv2d_dgrad_nhwc(du, pk['g5'], H=H, W=W, c1=c, c2=c, groups=c, k=5, out=da, cx=c, accumulate=da)
+        dt = self.ca.backward(da).t
+        ops.gelu_backward_(y0, dt)
+        return _plain_conv_backward(self.conv, x, dt, pk['wt'], dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, direct=direct)
+
+
+class CPCA(_CPCACore):
+    """Channel prior convolutional attention as a layer of its own (models/common.py:5782-5815)."""
+
+    def __init__(self, channels, channelAttention_reduce=4):
+        super().__init__()
+        self._init_cpca(channels, channelAttention_reduce)
+
+    accumulates = folds_pooled = False                           # takes dx_out / accumulate, not walked that way
+    reduction = 1
+
+    def forward(self, x, out=None):
+        return self._cpca_forward(x, False, out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        return self._cpca_backward(dout, dx_out, accumulate, need_dx)
+
+
+class CPCABottleneck(_CPCACore):
+    """cv1 -> cv2 -> CPCA arithmetic (+ the strip sum s when shortcut, see _CPCACore) (models/common.py:5818-5859).  The attention's modules are
+    sized by c1 and read cv2's c2-channel output: c1 == c2 is required."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5, channelAttention_reduce=4):
+        super().__init__()
+        if c1 != c2:
+            raise NotImplementedError(f'CPCABottleneck({c1}, {c2}): the attention is sized by c1 and reads cv2\'s c2 channels; the reference\'s '
+                                      f'forward fails too unless c1 == c2')
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, k[0], 1)
+        self.cv2 = Conv(c_, c2, k[1], 1, g=g)
+        self.add = shortcut and c1 == c2
+        self._init_cpca(c1, channelAttention_reduce)
+
+    accumulates = folds_pooled = False                           # like Bottleneck: takes dx_out / accumulate, not walked that way
+    reduction = 1
+
+    def forward(self, x, out=None):
+        return self._cpca_forward(self.cv2(self.cv1(x)), self.add, out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = self.cv2.backward(self._cpca_backward(dout))
+        return self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
+class C3CPCA(C3):
+    """C3 whose bottlenecks are CPCABottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) (models/common.py:1684-1689); repeated inside,
+    like C3 (models/yolo.py:1477, 1490)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(CPCABottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
+
+    accumulates = folds_pooled = False                           # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
+    reduction = 1
+
+
 class ASPP(nn.Module):
     """cv2(cat(t, maxpool3(t), m_0(t), ..)), t = cv1(x) (models/common.py:1829-1843): atrous spatial pyramid pooling.  The m_i are bare 3x3
     nn.Conv2d(bias=False) of dilation = padding = (k_i - 1) // 2 (2, 4, 6 for the default k), no norm and no activation.  Nothing is

@@ -209,6 +209,26 @@ def yolov5_context_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='aspp'
     return cfg
 
 
+def yolov5_cpca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
+    """yolov5s 6.0 with channel prior convolutional attention (models/common.py:5753-5859, 1684-1689).  The reference registers C3CPCA and CPCA
+    in its parser (models/yolo.py:1477, 1490, 1566-1568) but ships no yaml that names them.  where='c3': the four backbone C3 rows become
+    C3CPCA, repeated inside like C3; where='row': a [-1, 1, 'CPCA', []] row behind SPPF (sized by its input), the head's absolute indices
+    one up."""
+    if where not in ('c3', 'row'):
+        raise ValueError(f"where must be 'c3' or 'row', got {where!r}")
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    if where == 'c3':
+        for row in cfg['backbone']:
+            if row[2] == 'C3':
+                row[2] = 'C3CPCA'
+        return cfg
+    cfg['backbone'].append([-1, 1, 'CPCA', []])
+    for row in cfg['head']:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+    return cfg
+
+
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
     C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""

@@ -10,7 +10,9 @@ C2fCIB, PSA) and what the remaining stock hub graphs need (yolov3 / -spp / -tiny
 nn.MaxPool2d, nn.ZeroPad2d, SPP with other window sets, n > 1 repeats as an nn.Sequential, up to five Detect levels; the two learned
 drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-transformer C3 (C3TR stays outside); ASFF_Detect, the plain
 Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck); and coordinate
-attention, as the C3_CA block and as a CoorAttention row of its own; and the dilated-convolution context blocks ASPP and C2f_DWR.
+attention, as the C3_CA block and as a CoorAttention row of its own; the dilated-convolution context blocks ASPP and C2f_DWR; and channel
+prior convolutional attention: C3CPCA (a C3 of CPCABottleneck blocks, repeated inside) and a `[-1, 1, 'CPCA', []]` row sized by its input,
+channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.py).
 """
 import math
 from copy import deepcopy
@@ -33,9 +35,10 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'BottleneckCSP': B.BottleneckCSP, 'C3STR': B.C3STR,        # models/yolo.py:1472-1479
        'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention,        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
        'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR,                      # the dilated-conv context blocks, models/yolo.py:1472-1492
-       'MultiSEAM': B.MultiSEAM}                                  # in SEAM's branch (models/yolo.py:1475), not repeated inside (:1487-1490)
+       'MultiSEAM': B.MultiSEAM,                                  # in SEAM's branch (models/yolo.py:1475), not repeated inside (:1487-1490)
+       'C3CPCA': B.C3CPCA}                                        # models/yolo.py:1477, repeated inside (:1490)
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR')
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
@@ -84,6 +87,10 @@ def parse_model(d, ch):
             m = B.DySample
             args.insert(0, ch[f])
             c2 = ch[f]
+        elif name == 'CPCA':                                      # models/yolo.py:1566-1568: sized by its input, channels pass through
+            m = B.CPCA
+            c2 = ch[f]
+            args = [c2]
         elif name in _PASS_THROUGH:                               # parameter-free, channels pass through
             m = _PASS_THROUGH[name]
             c2 = ch[f]

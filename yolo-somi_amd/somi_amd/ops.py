@@ -535,6 +535,129 @@ def coordatt_backward_input(dout, a_h, a_w, gh, gw, c, do_coff=0, *, out=None, d
     return out
 
 
+# ---------------------------------------------------------------------------------------------- CPCA strips (cpca.hip)
+CPCA_TAPS = (7, 11, 21)
+
+
+def _cpca_slice(spec):
+    """tensor, or (tensor, channel offset) -> Slice."""
+    t, coff = spec if isinstance(spec, (tuple, list)) else (spec, 0)
+    return _slice(t, coff)
+
+
+def _cpca_vec(t, n, what):
+    """A parameter-shaped device tensor of n floats (any view of contiguous memory: (C,1,1,k), (C,1,k,1), (C,k), (C,))."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        raise RuntimeError(f'{what}: {n} contiguous fp32 values are expected, got {tuple(t.shape)} {t.dtype}')
+    return _ptr(t)
+
+
+def _cpca_strip_desc(shape, c, ws, biases, axis, flip, taps, what):
+    B, H, W, _ = shape
+    taps = tuple(int(k) for k in taps)
+    d = _lib.CpcaStripDesc()
+    d.B, d.H, d.W, d.C, d.axis, d.flip = B, H, W, c, {'w': 0, 'h': 1}[axis], int(bool(flip))
+    biases = (None, None, None) if biases is None else biases
+    for k in range(3):
+        d.taps[k] = taps[k]
+        d.w[k] = _cpca_vec(ws[k], c * taps[k], f'{what}: taps {k}')
+        d.bias[k] = _cpca_vec(biases[k], c, f'{what}: bias {k}')
+    return d
+
+
+def cpca_fanout(x, ws, biases, c, x_coff=0, *, axis, flip=False, outs=None, taps=CPCA_TAPS):
+    """The three strip convs of one tensor: outs[k] = S_k(x) [+ biases[k]], S_k the depthwise conv of taps[k] taps along `axis` ('w' or 'h', zero
+    padding k // 2) with the (c, k) weights ws[k], walked backwards with `flip`.  x is read once.  outs: three tensors or (tensor, channel
+    offset) pairs (new (B,H,W,c) tensors when None).  -> the three tensors."""
+    B, H, W, _ = x.shape
+    outs = [torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) for _ in range(3)] if outs is None else list(outs)
+    d = _cpca_strip_desc(x.shape, c, ws, biases, axis, flip, taps, 'cpca_fanout')
+    d.src[0] = _slice(x, x_coff)
+    for k in range(3):
+        d.dst[k] = _cpca_slice(outs[k])
+    check(_lib.lib().somi_cpca_fanout_nhwc_f32(C.byref(d), _stream()), 'cpca_fanout')
+    return [o[0] if isinstance(o, (tuple, list)) else o for o in outs]
+
+
+def cpca_fanin(ts, through, ws, biases, c, *, axis, flip=False, out=None, o_coff=0, accumulate=False, taps=CPCA_TAPS):
+    """out = [out +] through + sum_k (S_k(ts[k]) [+ biases[k]]): the three branches closed by their second strip conv and summed with the
+    pass-through tensor in one pass.  ts / through: tensors or (tensor, channel offset) pairs."""
+    first = ts[0][0] if isinstance(ts[0], (tuple, list)) else ts[0]
+    B, H, W, _ = first.shape
+    if out is None:
+        if accumulate:
+            raise RuntimeError('cpca_fanin: accumulate needs the tensor to add to')
+        out = torch.empty(B, H, W, c, device=first.device, dtype=torch.float32)
+    d = _cpca_strip_desc(first.shape, c, ws, biases, axis, flip, taps, 'cpca_fanin')
+    for k in range(3):
+        d.src[k] = _cpca_slice(ts[k])
+    d.src[3], d.dst[0], d.accumulate = _cpca_slice(through), _slice(out, o_coff), int(accumulate)
+    check(_lib.lib().somi_cpca_fanin_nhwc_f32(C.byref(d), _stream()), 'cpca_fanin')
+    return out
+
+
+def cpca_wgrad(u, ts, ds, dts, c, dw_h, dw_v, db_h, db_v, *, accumulate=False, taps=CPCA_TAPS):
+    """All strip weight and bias gradients of s = u + sum_k V_k(H_k(u)) in one call: dw_h[k] (c, k) from (dts[k], u), dw_v[k] from (ds, ts[k]),
+    db_h[k] = sum dts[k], db_v[k] = sum ds; written into the given contiguous fp32 tensors (any of them None: skipped), added with `accumulate`.
+    u, ts[k], ds, dts[k]: tensors or (tensor, channel offset) pairs."""
+    first = u[0] if isinstance(u, (tuple, list)) else u
+    B, H, W, _ = first.shape
+    taps = tuple(int(k) for k in taps)
+    d = _lib.CpcaWgradDesc()
+    d.B, d.H, d.W, d.C, d.accumulate = B, H, W, c, int(accumulate)
+    d.u, d.ds = _cpca_slice(u), _cpca_slice(ds)
+    for k in range(3):
+        d.taps[k] = taps[k]
+        d.t[k], d.dt[k] = _cpca_slice(ts[k]), _cpca_slice(dts[k])
+        d.dw_h[k], d.dw_v[k] = _cpca_vec(dw_h[k], c * taps[k], 'cpca_wgrad: dw_h'), _cpca_vec(dw_v[k], c * taps[k], 'cpca_wgrad: dw_v')
+        d.db_h[k], d.db_v[k] = _cpca_vec(db_h[k], c, 'cpca_wgrad: db_h'), _cpca_vec(db_v[k], c, 'cpca_wgrad: db_v')
+    ws = torch.empty(max(_lib.lib().somi_cpca_wgrad_workspace_floats(B, H, W, c), 4), device=first.device, dtype=torch.float32)
+    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    check(_lib.lib().somi_cpca_wgrad_nhwc_f32(C.byref(d), _stream()), 'cpca_wgrad')
+
+
+def cpca_gate(x, y, c, x_coff=0, y_coff=0, *, out=None, o_coff=0):
+    """out = x * y over c channels (CPCA's conv(s) * a)."""
+    if out is None:
+        out = torch.empty(*x.shape[:3], c, device=x.device, dtype=torch.float32)
+    check(_lib.lib().somi_cpca_gate_nhwc_f32(_slice(x, x_coff), _slice(y, y_coff), _slice(out, o_coff), _npix(x), c, _stream()), 'cpca_gate')
+    return out
+
+
+def cpca_gate_backward(dout, x, y, c, do_coff=0, x_coff=0, y_coff=0):
+    """-> (dx, dy) = (dout * y, dout * x), new (B,H,W,c) tensors."""
+    dx = torch.empty(*x.shape[:3], c, device=x.device, dtype=torch.float32)
+    dy = torch.empty_like(dx)
+    check(_lib.lib().somi_cpca_gate_bwd_nhwc_f32(_slice(dout, do_coff), _slice(x, x_coff), _slice(y, y_coff), _slice(dx, 0), _slice(dy, 0),
+                                                 _npix(x), c, _stream()), 'cpca_gate_backward')
+    return dx, dy
+
+
+def cpca_sigmoid2(z):
+    """z (2B, C): the shared MLP's output on the average rows, then on the maximum rows -> g (B, C) = sigmoid(z[:B]) + sigmoid(z[B:])."""
+    B, c = z.shape[0] // 2, z.shape[1]
+    g = torch.empty(B, c, device=z.device, dtype=torch.float32)
+    check(_lib.lib().somi_cpca_sigmoid2_f32(_ptr(_f32c(z)), _ptr(g), B, c, _stream()), 'cpca_sigmoid2')
+    return g
+
+
+def cpca_sigmoid2_backward(z, dg):
+    dz = torch.empty_like(z)
+    check(_lib.lib().somi_cpca_sigmoid2_bwd_f32(_ptr(_f32c(z)), _ptr(_f32c(dg)), _ptr(dz), dg.shape[0], dg.shape[1], _stream()),
+          'cpca_sigmoid2_backward')
+    return dz
+
+
+def argmax_pixel(x, mx, c, x_coff=0):
+    """(B, c) int32: the first pixel of every channel's spatial maximum mx (global_pool's) in slice [x_coff, x_coff + c) of x."""
+    B, H, W, _ = x.shape
+    out = torch.empty(B, c, device=x.device, dtype=torch.int32)
+    check(_lib.lib().somi_cpca_argmax_pixel_nhwc_f32(_slice(x, x_coff), _ptr(_f32c(mx)), _ptr(out), B, H * W, c, _stream()), 'argmax_pixel')
+    return out
+
+
 def _spp_k(k):
     k = [int(v) for v in k]
     return [len(k)] + (k + [0, 0, 0])[:3]
@@ -677,13 +800,20 @@ def bifpn(srcs, ups, w_dev, eps=1e-4, out=None):
     return out
 
 
-def global_pool(x, c=None, x_coff=0, want_max=True):
+def global_pool(x, c=None, x_coff=0, want_max=True, out=None):
+    """out: a contiguous (2B, c) tensor whose halves receive the averages and the maxima (CPCA's shared MLP reads both as one batch)."""
     B, H, W, cs = x.shape
     c = cs - x_coff if c is None else c
     nchunk = _lib.lib().somi_pool_nchunk(H * W)
     ws = torch.empty(2 * B * nchunk * c, device=x.device, dtype=torch.float32)
-    avg = torch.empty(B, c, device=x.device, dtype=torch.float32)
-    mx = torch.empty(B, c, device=x.device, dtype=torch.float32) if want_max else None
+    if out is not None:
+        if tuple(out.shape) != (2 * B, c) or out.dtype != torch.float32 or not out.is_contiguous() or not want_max:
+            raise RuntimeError(f'global_pool: out must be a contiguous fp32 ({2 * B}, {c}) tensor and takes both pools, got {tuple(out.shape)} '
+                               f'{out.dtype}, want_max={want_max}')
+        avg, mx = out[:B], out[B:]
+    else:
+        avg = torch.empty(B, c, device=x.device, dtype=torch.float32)
+        mx = torch.empty(B, c, device=x.device, dtype=torch.float32) if want_max else None
     check(_lib.lib().somi_global_pool_nhwc_f32(_ptr(_f32c(x)), cs, x_coff, B, H * W, c, _ptr(avg), _ptr(mx), _ptr(ws),
                                                _stream()), 'global_pool')
     return avg, mx
