@@ -58,7 +58,7 @@ enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_AC
                                        coordinate attention: taken wherever SOMI_ACT_LEAKY is */ };
 
 /* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
- * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc).  An input slice is only read. */
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_simam_desc).  An input slice is only read. */
 typedef struct somi_slice {
     float *p;
     int32_t cs, coff;
@@ -456,6 +456,49 @@ int somi_cpca_sigmoid2_bwd_f32(const float *z, const float *dg, float *dz, int B
 /* amaxp[b][c] = the first pixel p with x[b,p,c] == mx[b][c], mx the spatial maximum somi_global_pool_nhwc_f32 took of the same tensor: what
  * somi_pool_bwd_add_nhwc_f32 needs.  An integer minimum over the matching pixels, independent of the order. */
 int somi_cpca_argmax_pixel_nhwc_f32(somi_slice x, const float *mx, int32_t *amaxp, int B, int HW, int C, somi_stream_t stream);
+
+/* SimAM attention (SimAM, models/common.py:2915-2939; SimAMWithSlicing, :9374-9408; SimAMWithFlexibleSlicing, :9411-9480; simam.hip): the
+ * parameter-free energy gate as ONE operator over a grid of ny x nx regions of the map x (B,H,W,.).  Region (i, j) spans rows
+ * [i * step_y, i * step_y + len_y) and columns [j * step_x, j * step_x + len_x); with stretch_last the last region of an axis runs to the map
+ * edge (needs step == len).  Per (image, region r, channel), over the region's own N_r pixels:
+ *   mu_r = mean x,  d = x - mu_r,  S_r = sum d^2,  D_r = 4 (S_r / n + lambda),  s = sigmoid(d^2 / D_r + 0.5),
+ * the divisor n GIVEN, not derived from N_r.  The three modules are
+ *   whole map  ny = nx = 1, len = step = (H, W), n = H W - 1;
+ *   quadrants  ny = nx = 2, len = step = (H / 2, W / 2), stretch_last, n = (H / 2)(W / 2) - 1 for all four, the larger ones included;
+ *   windows    len = t, step = st, ny = (H - t) / st + 1, nx = (W - t) / st + 1, n = t t - 1.
+ * A pixel's weight in a region that covers it is w = 1 / k, k its 1-based rank among the regions covering the pixel in row-major order (the
+ * reference divides a window's contribution by the coverage count at the time it is added, not by the final count); at most 4 regions may
+ * cover a pixel along one axis (ceil(len / step) <= 4, else SOMI_ENOTIMPL).  A region has at least two pixels; lambda > 0.
+ * Every tensor is a channel slice of width C (a multiple of 4).  stats and sums are plain (B, ny * nx, 2, C) tensors, 16-byte aligned.
+ * stats     (somi_simam_stats_nhwc_f32):     stats[b][r][0] = mu_r, [1] = S_r, the sum of squared deviations about that mean (count, mean, M2
+ *           partials merged by the pairwise update in a fixed order - not sum x^2 - N mu^2).  One pass over x.
+ * apply     (somi_simam_apply_nhwc_f32):     y = [x +] sum_{r covers the pixel} w x s, written; a pixel no region covers gets 0 [+ x].
+ *           add_input: the [x +] (PSSimAM's b + attn(b)).
+ * bwd sums  (somi_simam_bwd_sums_nhwc_f32):  y holds dout = g (read).  sums[b][r][0] = A_r = sum T d, [1] = B_r = sum T d^2, T = w g x s (1 - s).
+ * bwd input (somi_simam_bwd_input_nhwc_f32): dx = [g +] sum_{r covers} ( w g s + 2 T d / D_r - 2 A_r / (N_r D_r) - (8 / n) d B_r / D_r^2 ),
+ *           written, or added to what dx holds with `accumulate`; the gate is recomputed from x and stats, [g +] with add_input.
+ * stats and bwd sums split a region larger than one chunk over workgroups through `workspace` (somi_simam_workspace_floats(d) floats,
+ * 16-byte aligned; 0: not needed, the pointer may be NULL) and a fixed-order second stage.  No float atomics: two launches are bit-identical. */
+typedef struct somi_simam_desc {
+    somi_slice x;              /* the map, read by all four */
+    somi_slice y;              /* apply: the output, written; both backward passes: dout, read; unused by stats */
+    somi_slice dx;             /* bwd input only */
+    float *stats;              /* stats: written; the other three: read */
+    float *sums;               /* bwd sums: written; bwd input: read */
+    int32_t B, H, W, C;
+    int32_t ny, nx, step_y, step_x, len_y, len_x, stretch_last;
+    int32_t add_input;         /* apply: out = x + ...; bwd input: dx = g + ... */
+    int32_t accumulate;        /* bwd input: add to what dx holds */
+    float n, lambda;
+    float *workspace;          /* stats and bwd sums */
+    uint64_t workspace_floats;
+} somi_simam_desc;
+size_t somi_simam_desc_bytes(void);   /* sizeof(somi_simam_desc) as the library was compiled: lets a binding check its mirror */
+size_t somi_simam_workspace_floats(const somi_simam_desc *d);   /* from B, H, W, C and the region grid; 0 for a grid the kernels refuse too */
+int somi_simam_stats_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
+int somi_simam_apply_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
+int somi_simam_bwd_sums_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
+int somi_simam_bwd_input_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
 
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed

@@ -83,6 +83,14 @@ class CpcaWgradDesc(C.Structure):
                 ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
 
 
+class SimamDesc(C.Structure):
+    """struct somi_simam_desc (include/somi_hip.h)."""
+    _fields_ = [('x', Slice), ('y', Slice), ('dx', Slice), ('stats', C.c_void_p), ('sums', C.c_void_p), ('B', C.c_int32), ('H', C.c_int32),
+                ('W', C.c_int32), ('C', C.c_int32), ('ny', C.c_int32), ('nx', C.c_int32), ('step_y', C.c_int32), ('step_x', C.c_int32),
+                ('len_y', C.c_int32), ('len_x', C.c_int32), ('stretch_last', C.c_int32), ('add_input', C.c_int32), ('accumulate', C.c_int32),
+                ('n', C.c_float), ('lam', C.c_float), ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -250,7 +258,13 @@ SIGNATURES = {
     'somi_cpca_sigmoid2_f32': (I, [P, P, I, I, S]),
     'somi_cpca_sigmoid2_bwd_f32': (I, [P, P, P, I, I, S]),
     'somi_cpca_argmax_pixel_nhwc_f32': (I, [Slice, P, P, I, I, I, S]),
-    'somi_spp_pool_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
+    'somi_simam_desc_bytes': (Z, []),
+    'somi_simam_workspace_floats': (Z, [C.POINTER(SimamDesc)]),
+    'somi_simam_stats_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
+    'somi_simam_apply_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
+    'somi_simam_bwd_sums_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
+    'somi_simam_bwd_input_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
+    'somi_spp_pool_nhwc_f32':(I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
     'somi_carafe_bwd_nhwc_f32': (I, [P, P, P, P, P] + [I] * 13 + [S]),
@@ -302,7 +316,8 @@ def lib():
                         or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)
                         or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)
                         or L.somi_cpca_strip_desc_bytes() != C.sizeof(CpcaStripDesc)
-                        or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)):
+                        or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)
+                        or L.somi_simam_desc_bytes() != C.sizeof(SimamDesc)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

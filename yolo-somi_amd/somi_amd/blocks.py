@@ -2693,6 +2693,181 @@ class C3CPCA(C3):
     reduction = 1
 
 
+# ------------------------------------------------------------------------------------------------ SimAM
+class _SimAMGate(nn.Module):
+    """The parameter-free SimAM gate over a grid of regions (simam.hip), shared by SimAM (one region), SimAMWithSlicing (four quadrants) and
+    SimAMWithFlexibleSlicing (windows): per (image, region, channel) mu = the mean over the region's own pixels, d = x - mu, S = sum d^2,
+    D = 4 (S / n + e_lambda), out = sum over the regions covering a pixel of w x sigmoid(d^2 / D + 0.5).  Forward: ops.simam_stats, then
+    ops.simam_apply; backward: ops.simam_backward_sums, then ops.simam_backward_input, the gate recomputed from x and the kept statistics.
+    Subclasses give _grid(H, W) -> ops.simam_grid(...), which raises the limits by name before anything is launched."""
+
+    def _gate_width(self, a, what):
+        """How many channels the kernels walk of Act `a`: its whole padded width (pad channels hold zeros and come out zero), or an aligned slice."""
+        if a.up:
+            raise NotImplementedError(f'{type(self).__name__} needs a real tensor, not an upsampled view')
+        if a.coff == 0 and a.t.shape[3] == pad4(a.c):
+            return pad4(a.c)
+        if a.c % 4 or a.coff % 4:
+            raise NotImplementedError(f'{type(self).__name__}: {what} as a channel slice needs a channel count and offset that are multiples of 4')
+        return a.c
+
+    def forward(self, x, out=None, add_input=False):
+        """out = [x +] gate(x); add_input: PSSimAM's b + attn(b) in the same pass."""
+        B, H, W, _ = x.shape
+        grid = self._grid(H, W)
+        cw = self._gate_width(x, 'the input')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd SimAM runs on the MI355X only (no CPU fallback)')
+        if out is None:
+            out = new_act(x.t, H, W, x.c)
+        elif self._gate_width(Act(out.t, out.coff, x.c), 'the output') != cw:
+            raise NotImplementedError(f'{type(self).__name__}: input and output must both be whole padded tensors or both aligned slices')
+        stats = ops.simam_stats(x.t, cw, grid, x.coff)
+        ops.simam_apply(x.t, stats, cw, grid, x.coff, out=out.t, o_coff=out.coff, add_input=add_input)
+        if self.training:
+            self.__dict__['_ctx'] = (x, stats, grid, cw)
+        return Act(out.t, out.coff, x.c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True, add_input=False):
+        """-> the gradient of x as an Act: written into dx_out if given, added to it with `accumulate`.  add_input: the forward's `x +`."""
+        x, stats, grid, cw = self.__dict__.pop('_ctx')
+        if not need_dx:
+            return None
+        if self._gate_width(Act(dout.t, dout.coff, x.c), 'the output gradient') != cw:
+            raise NotImplementedError(f'{type(self).__name__}: the output gradient must be laid out like the input')
+        B, H, W, _ = x.shape
+        if dx_out is None:
+            dx_out, accumulate = new_act(x.t, H, W, x.c), False
+        elif self._gate_width(Act(dx_out.t, dx_out.coff, x.c), 'the input gradient') != cw:
+            raise NotImplementedError(f'{type(self).__name__}: the input gradient must be laid out like the input')
+        sums = ops.simam_backward_sums(dout.t, x.t, stats, cw, grid, dout.coff, x.coff)
+        ops.simam_backward_input(dout.t, x.t, stats, sums, cw, grid, dout.coff, x.coff, out=dx_out.t, dx_coff=dx_out.coff,
+                                 accumulate=accumulate, add_input=add_input)
+        return Act(dx_out.t, dx_out.coff, x.c)
+
+
+class SimAM(_SimAMGate):
+    """SimAM over the whole map (models/common.py:2915-2939): one region, n = H W - 1.  c1 is ignored, as in the reference."""
+
+    def __init__(self, c1, e_lambda=1e-4):
+        super().__init__()
+        self.activaton = nn.Sigmoid()                            # the reference's spelling; parameter-free
+        self.e_lambda = e_lambda
+
+    accumulates, folds_pooled, reduction = False, False, 1       # takes dx_out / accumulate, not walked that way
+
+    def _grid(self, H, W):
+        return ops.simam_grid('map', H, W, self.e_lambda)
+
+
+class SimAMWithSlicing(_SimAMGate):
+    """SimAM per quadrant (models/common.py:9374-9408): rows split at H // 2, columns at W // 2 - on odd sizes the second region is the larger
+    one -, each region's mean and S over its own pixels, and n = (H // 2)(W // 2) - 1 for all four, the larger ones included."""
+
+    def __init__(self, c1, e_lambda=1e-4):
+        super().__init__()
+        self.activation = nn.Sigmoid()
+        self.e_lambda = e_lambda
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _grid(self, H, W):
+        return ops.simam_grid('quadrants', H, W, self.e_lambda)
+
+
+class SimAMWithFlexibleSlicing(_SimAMGate):
+    """SimAM per target_size x target_size window (models/common.py:9411-9480): windows start at range(0, H - t + 1, st) x range(0, W - t + 1, st),
+    st = t without overlap, else int(t (1 - overlap_ratio)); n = t t - 1.  Pixels no window covers are ZERO in the output.  With overlap the
+    reference divides a window's contribution by the coverage count at the time it is added, so the k-th window over a pixel (row-major) counts
+    1 / k - not 1 / (the final count); the kernels do the same."""
+
+    def __init__(self, c1, target_size, overlap_ratio=0.0, e_lambda=1e-4):
+        super().__init__()
+        self.target_size = target_size
+        self.overlap_ratio = overlap_ratio
+        if target_size < 2:
+            raise ValueError(f'SimAMWithFlexibleSlicing: target_size {target_size}: a window of one pixel has no variance (the reference divides 0 by 0)')
+        st = target_size if overlap_ratio == 0.0 else int(target_size * (1 - overlap_ratio))
+        if st < 1:
+            raise ValueError(f'SimAMWithFlexibleSlicing: overlap_ratio {overlap_ratio} at target_size {target_size} gives a stride of {st} '
+                             f'(the reference\'s range() raises)')
+        if -(-target_size // st) > ops.SIMAM_MAX_COVER:
+            raise NotImplementedError(f'SimAMWithFlexibleSlicing: overlap_ratio {overlap_ratio} at target_size {target_size} (stride {st}) puts '
+                                      f'{-(-target_size // st)} windows over a pixel along one axis; the kernels take at most {ops.SIMAM_MAX_COVER}')
+        self.stride = (st, st)
+        self.activation = nn.Sigmoid()
+        self.e_lambda = e_lambda
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _grid(self, H, W):
+        return ops.simam_grid('windows', H, W, self.e_lambda, self.target_size, self.stride[0])
+
+
+class Conv_SWS(Conv):
+    """act(bn(conv(att(x)))), att = SimAMWithFlexibleSlicing(c1, target_size, overlap_ratio, e_lambda) (models/common.py:9483-9495): a Conv with
+    sliding-window SimAM in front of it.  Children conv, bn, act, att as in the reference; att has no parameters.  The reference's fuseforward
+    (another order) is dead code there - Model.fuse only touches Conv / DWConv instances - and is not mirrored."""
+
+    def __init__(self, c1, c2, target_size, overlap_ratio=0.0, e_lambda=1e-4, k=1, s=1, p=None, g=1, act=True):
+        super().__init__(c1, c2, k, s, p, g, 1, act)
+        self.att = SimAMWithFlexibleSlicing(c1, target_size, overlap_ratio, e_lambda)
+
+    accumulates = folds_pooled = False                           # the gate's backward stands between the conv's data gradient and the input
+    reduction = property(lambda self: self.conv.stride[0])
+
+    def forward(self, x, out=None):
+        return Conv.forward(self, self.att(x), out=out)
+
+    def backward(self, dz, dx_out=None, accumulate=False, need_dx=True):
+        if not need_dx:
+            self.att.__dict__.pop('_ctx', None)
+            return Conv.backward(self, dz, need_dx=False)
+        return self.att.backward(Conv.backward(self, dz), dx_out=dx_out, accumulate=accumulate)
+
+
+class PSSimAM(nn.Module):
+    """cv2(cat(a, b2)) with a, b = cv1(x).split, b1 = b + SimAM(b), b2 = b1 + ffn(b1) (models/common.py:2942-2961): PSA's shape around SimAM.
+    cv1 writes [a | b] into cv2's input buffer and ffn[1] writes b2 over b.  Eval: the gate reads b in place, a channel slice at offset c.
+    Training: b is copied out once first - the gate's backward recomputes it from the b it read -; `b +` rides the gate's apply pass and its
+    gradient the gate's input-gradient pass, which writes b's gradient next to a's, so cv1 reads one buffer."""
+
+    def __init__(self, c1, c2, e=0.5):
+        super().__init__()
+        if c1 != c2:
+            raise ValueError(f'PSSimAM needs c1 == c2, got {c1} and {c2}')
+        self.c = int(c1 * e)
+        if self.c % 4 or self.c == 0:
+            raise NotImplementedError(f'PSSimAM with {self.c} channels per branch: the branches are channel slices, a multiple of 4 channels each')
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.attn = SimAM(self.c)
+        self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x):
+        c = self.c
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, 2 * c)
+        self.cv1(x, out=cat)
+        b = cat.slice(c, c)
+        if self.training:                                         # ffn[1] overwrites cat's b; the gate's backward needs it
+            b = new_act(x.t, H, W, c)
+            ops.resample_slice(cat.t, c, b.t, 0, c)
+        b1 = self.attn(b, add_input=True)
+        self.ffn[1](self.ffn[0](b1), out=cat.slice(c, c), residual=b1)
+        return self.cv2(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        c = self.c
+        dcat = self.cv2.backward(dout)
+        db2 = dcat.slice(c, c)
+        db1 = self.ffn[0].backward(self.ffn[1].backward(db2), also_add=db2)
+        self.attn.backward(db1, dx_out=db2, add_input=True)       # db2's slice is free again: it takes b's gradient
+        return self.cv1.backward(dcat, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+
+
 class ASPP(nn.Module):
     """cv2(cat(t, maxpool3(t), m_0(t), ..)), t = cv1(x) (models/common.py:1829-1843): atrous spatial pyramid pooling.  The m_i are bare 3x3
     nn.Conv2d(bias=False) of dilation = padding = (k_i - 1) // 2 (2, 4, 6 for the default k), no norm and no activation.  Nothing is

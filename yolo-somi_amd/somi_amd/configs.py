@@ -229,6 +229,31 @@ def yolov5_cpca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
     return cfg
 
 
+SIMAM_WHERE = ('row', 'slicing', 'sws', 'ps')
+
+
+def yolov5_simam_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='row'):
+    """yolov5s 6.0 with the parameter-free SimAM attention family (models/common.py:2915-2961, 9374-9495).  The reference registers the five
+    names in its parser (models/yolo.py:1472, 1502-1513 and the generic branch) but ships no yaml that names them.  where='row': a
+    [-1, 1, 'SimAM', [1024]] row behind SPPF; 'slicing': a [-1, 1, 'SimAMWithSlicing', [1024]] row there; 'ps': a PSSimAM row there, its
+    arguments - used as written by the parser - the width-scaled channel count; for these three the head's absolute indices move one up.
+    'sws': the P3 and P4 stride-2 backbone Convs (rows 3 and 5) become Conv_SWS [c2, 8, 0.5, 1e-4, 3, 2]: 8 x 8 windows at stride 4."""
+    if where not in SIMAM_WHERE:
+        raise ValueError(f'where must be one of {SIMAM_WHERE}, got {where!r}')
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    if where == 'sws':
+        for i in (3, 5):
+            row = cfg['backbone'][i]
+            row[2], row[3] = 'Conv_SWS', [row[3][0], 8, 0.5, 1e-4, 3, 2]
+        return cfg
+    c = math.ceil(1024 * width / 8) * 8                           # the parser's make_divisible(1024 * width, 8)
+    cfg['backbone'].append({'row': [-1, 1, 'SimAM', [1024]], 'slicing': [-1, 1, 'SimAMWithSlicing', [1024]], 'ps': [-1, 1, 'PSSimAM', [c, c]]}[where])
+    for row in cfg['head']:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+    return cfg
+
+
 def yolov5_ghost_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-ghost.yaml as a dict: yolov5s with GhostConv for the strided and lateral convs and C3Ghost for
     C3 (Focus stem, SPP(5,9,13)).  Defaults are the yaml's (depth 0.33, width 0.50, 80 classes, the COCO anchors)."""

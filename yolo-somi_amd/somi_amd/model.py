@@ -12,7 +12,9 @@ drop-ins for the neck's nn.Upsample rows, CARAFE and DySample; C3STR, the Swin-t
 Detect behind three adaptive-spatial-feature-fusion blocks (three levels of 128 / 256 / 512 channels, i.e. a yolov5s-width neck); and coordinate
 attention, as the C3_CA block and as a CoorAttention row of its own; the dilated-convolution context blocks ASPP and C2f_DWR; and channel
 prior convolutional attention: C3CPCA (a C3 of CPCABottleneck blocks, repeated inside) and a `[-1, 1, 'CPCA', []]` row sized by its input,
-channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.py).
+channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.py); and the parameter-free SimAM family: a `SimAM` row
+(from -1 only, arguments as written), `SimAMWithSlicing` and `SimAMWithFlexibleSlicing` rows (sized by their input; the channel count the row
+names must be the input's), `Conv_SWS` (a Conv behind sliding-window SimAM, width-scaled like Conv) and `PSSimAM` (arguments as written).
 """
 import math
 from copy import deepcopy
@@ -36,7 +38,9 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'C3_CA': B.C3_CA, 'CoorAttention': B.CoorAttention,        # CoorAttention: its own row with the same arguments, models/yolo.py:1630-1634
        'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR,                      # the dilated-conv context blocks, models/yolo.py:1472-1492
        'MultiSEAM': B.MultiSEAM,                                  # in SEAM's branch (models/yolo.py:1475), not repeated inside (:1487-1490)
-       'C3CPCA': B.C3CPCA}                                        # models/yolo.py:1477, repeated inside (:1490)
+       'C3CPCA': B.C3CPCA,                                        # models/yolo.py:1477, repeated inside (:1490)
+       'Conv_SWS': B.Conv_SWS}                                    # models/yolo.py:1472, not repeated inside
+_SIMAM_SLICED = {'SimAMWithSlicing': B.SimAMWithSlicing, 'SimAMWithFlexibleSlicing': B.SimAMWithFlexibleSlicing}      # models/yolo.py:1504-1513
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
 _REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
@@ -91,6 +95,25 @@ def parse_model(d, ch):
             m = B.CPCA
             c2 = ch[f]
             args = [c2]
+        elif name == 'SimAM':                                     # models/yolo.py:1502-1503: the arguments as written (c1 is ignored)
+            # the reference sets no c2 in this branch: the next row is sized by the PREVIOUS row's output, which is right for `from` -1 only
+            if f != -1:
+                raise NotImplementedError(f"a 'SimAM' row from {f}: the reference sizes the rows behind it by the previous row's channels "
+                                          f'(models/yolo.py:1502-1503 sets no c2), which is this row\'s input only for from = -1')
+            m = B.SimAM
+            c2 = ch[f]
+        elif name in _SIMAM_SLICED:                               # models/yolo.py:1504-1513: sized by its input; args[0] is what the parser records
+            m = _SIMAM_SLICED[name]
+            c1, c2 = ch[f], args[0]
+            if c2 != no:
+                c2 = make_divisible(c2 * gw, 8)
+            if c2 != c1:
+                raise ValueError(f'a {name!r} row that names {c2} channels (scaled) behind {c1}: the module passes its input through, and the '
+                                 f'reference would size the following rows by {c2}')
+            args = [c1, *args[1:]]
+        elif name == 'PSSimAM':                                   # the generic branch, models/yolo.py:1647-1648: arguments as written
+            m = B.PSSimAM
+            c2 = ch[f]
         elif name in _PASS_THROUGH:                               # parameter-free, channels pass through
             m = _PASS_THROUGH[name]
             c2 = ch[f]

@@ -535,6 +535,108 @@ def coordatt_backward_input(dout, a_h, a_w, gh, gw, c, do_coff=0, *, out=None, d
     return out
 
 
+# ---------------------------------------------------------------------------------------------- SimAM (simam.hip)
+SIMAM_MAX_COVER = 4     # regions over one pixel along an axis (SA_COVER of simam.hip)
+
+
+def simam_grid(mode, H, W, e_lambda=1e-4, target_size=None, stride=None):
+    """The region grid of a SimAM module on an H x W map -> (ny, nx, step_y, step_x, len_y, len_x, stretch_last, n, lambda), what the four
+    simam_* calls take as `grid`.  mode 'map': one region, n = H W - 1 (SimAM); 'quadrants': rows split at H // 2 and columns at W // 2, the
+    second region the larger one on odd sizes, n = (H // 2)(W // 2) - 1 for all four (SimAMWithSlicing); 'windows': target_size x target_size
+    windows at `stride`, starting at range(0, H - t + 1, stride) x range(0, W - t + 1, stride), n = t t - 1 (SimAMWithFlexibleSlicing).
+    The limits are raised here, by name, before anything is launched."""
+    if mode == 'map':
+        if H * W < 2:
+            raise RuntimeError(f'SimAM on a {H}x{W} map: one pixel has no variance (the reference divides 0 by 0)')
+        return (1, 1, H, W, H, W, 0, float(H * W - 1), float(e_lambda))
+    if mode == 'quadrants':
+        bh, bw = H // 2, W // 2
+        if H < 2 or W < 2 or bh * bw < 2:
+            raise RuntimeError(f'SimAMWithSlicing on a {H}x{W} map: a quadrant of {bh}x{bw} pixels has no variance (the reference divides 0 by 0)')
+        return (2, 2, bh, bw, bh, bw, 1, float(bh * bw - 1), float(e_lambda))
+    if mode != 'windows':
+        raise ValueError(f"simam_grid: mode {mode!r} (one of 'map', 'quadrants', 'windows')")
+    t, st = target_size, stride
+    if H < t or W < t:
+        raise RuntimeError(f'SimAMWithFlexibleSlicing: a {H}x{W} map is smaller than target_size {t}: no window fits (the reference returns zeros)')
+    return ((H - t) // st + 1, (W - t) // st + 1, st, st, t, t, 0, float(t * t - 1), float(e_lambda))
+
+
+def _simam_desc(x, c, grid, x_coff, stats, what):
+    B, H, W, _ = x.shape
+    d = _lib.SimamDesc()
+    d.B, d.H, d.W, d.C = B, H, W, c
+    d.ny, d.nx, d.step_y, d.step_x, d.len_y, d.len_x, d.stretch_last, d.n, d.lam = grid
+    d.x = _slice(x, x_coff)
+    if stats is not None:
+        if tuple(stats.shape) != (B, d.ny * d.nx, 2, c) or not stats.is_contiguous() or stats.dtype != torch.float32:
+            raise RuntimeError(f'{what}: a contiguous fp32 ({B}, {d.ny * d.nx}, 2, {c}) tensor is expected, got {tuple(stats.shape)}')
+        d.stats = _ptr(stats)
+    return d
+
+
+def _simam_workspace(d, dev):
+    ws = torch.empty(max(_lib.lib().somi_simam_workspace_floats(C.byref(d)), 4), device=dev, dtype=torch.float32)
+    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return ws
+
+
+def simam_stats(x, c, grid, x_coff=0):
+    """Per (image, region, channel) of slice [x_coff, x_coff + c) of x (B,H,W,cs): the mean over the region and the sum of squared deviations
+    about it -> stats (B, ny * nx, 2, c).  grid: simam_grid(...)."""
+    B = x.shape[0]
+    stats = torch.empty(B, grid[0] * grid[1], 2, c, device=x.device, dtype=torch.float32)
+    d = _simam_desc(x, c, grid, x_coff, stats, 'simam_stats')
+    ws = _simam_workspace(d, x.device)                            # noqa: F841  (alive until the launch is enqueued)
+    check(_lib.lib().somi_simam_stats_nhwc_f32(C.byref(d), _stream()), 'simam_stats')
+    return stats
+
+
+def simam_apply(x, stats, c, grid, x_coff=0, *, out=None, o_coff=0, add_input=False):
+    """out = [x +] sum over the regions covering a pixel of w * x * sigmoid(d^2 / D + 0.5); a pixel no region covers gets 0 [+ x]."""
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'simam_apply: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    d = _simam_desc(x, c, grid, x_coff, stats, 'simam_apply: stats')
+    d.y, d.add_input = _slice(out, o_coff), int(add_input)
+    check(_lib.lib().somi_simam_apply_nhwc_f32(C.byref(d), _stream()), 'simam_apply')
+    return out
+
+
+def simam_backward_sums(dout, x, stats, c, grid, do_coff=0, x_coff=0):
+    """The two per (image, region, channel) sums of the backward, A = sum T d and B = sum T d^2 with T = w g x s (1 - s) -> sums (B, ny * nx, 2, c)."""
+    B, H, W, _ = x.shape
+    if tuple(dout.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'simam_backward_sums: dout must be ({B}, {H}, {W}, .), got {tuple(dout.shape)}')
+    sums = torch.empty_like(stats)
+    d = _simam_desc(x, c, grid, x_coff, stats, 'simam_backward_sums: stats')
+    d.y, d.sums = _slice(dout, do_coff), _ptr(sums)
+    ws = _simam_workspace(d, x.device)                            # noqa: F841
+    check(_lib.lib().somi_simam_bwd_sums_nhwc_f32(C.byref(d), _stream()), 'simam_backward_sums')
+    return sums
+
+
+def simam_backward_input(dout, x, stats, sums, c, grid, do_coff=0, x_coff=0, *, out=None, dx_coff=0, accumulate=False, add_input=False):
+    """dx = [g +] sum over the covering regions of (w g s + 2 T d / D - 2 A / (N D) - (8 / n) d B / D^2), written into out's slice at dx_coff, or
+    added to it with `accumulate`; add_input: the gradient of apply's `x +`."""
+    B, H, W, _ = x.shape
+    if out is None:
+        if accumulate:
+            raise RuntimeError('simam_backward_input: accumulate needs the tensor to add to')
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if tuple(out.shape[:3]) != (B, H, W) or tuple(dout.shape[:3]) != (B, H, W):
+        raise RuntimeError(f'simam_backward_input: dout and dx must be ({B}, {H}, {W}, .), got {tuple(dout.shape)} and {tuple(out.shape)}')
+    d = _simam_desc(x, c, grid, x_coff, stats, 'simam_backward_input: stats')
+    if tuple(sums.shape) != tuple(stats.shape) or not sums.is_contiguous() or sums.dtype != torch.float32:
+        raise RuntimeError(f'simam_backward_input: sums must be like stats, got {tuple(sums.shape)}')
+    d.y, d.dx, d.sums = _slice(dout, do_coff), _slice(out, dx_coff), _ptr(sums)
+    d.accumulate, d.add_input = int(accumulate), int(add_input)
+    check(_lib.lib().somi_simam_bwd_input_nhwc_f32(C.byref(d), _stream()), 'simam_backward_input')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- CPCA strips (cpca.hip)
 CPCA_TAPS = (7, 11, 21)
 
