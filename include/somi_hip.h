@@ -58,7 +58,7 @@ enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_AC
                                        coordinate attention: taken wherever SOMI_ACT_LEAKY is */ };
 
 /* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
- * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_simam_desc).  An input slice is only read. */
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_simam_desc, the asf.hip descriptors).  An input slice is only read. */
 typedef struct somi_slice {
     float *p;
     int32_t cs, coff;
@@ -499,6 +499,98 @@ int somi_simam_stats_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
 int somi_simam_apply_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
 int somi_simam_bwd_sums_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
 int somi_simam_bwd_input_nhwc_f32(const somi_simam_desc *d, somi_stream_t stream);
+
+/* ASF-YOLO neck (Zoom_cat, models/common.py:4312-4327; ScalSeq, :4330-4355; attention_model, :4358-4424; asf.hip).  fp32, NHWC, every map a
+ * channel slice whose width is a multiple of 4, one channel quad per lane.  Every reduction has a fixed order, no float atomics: two launches
+ * on the same input are bit-identical.
+ *
+ * Zoom_cat.  l (B,2H,2W,.) Cl wide, m (B,H,W,.) Cm wide, s (B,(H+1)/2,(W+1)/2,.) Cs wide; out (B,H,W,.) Cl + Cm + Cs wide from out.coff.
+ * forward (somi_zoomcat_nhwc_f32), one launch: out[..., 0:Cl] = max2x2(l) + mean2x2(l), out[..., Cl:Cl+Cm] = m (skipped when m.p is NULL: the
+ *   producer wrote it in place), out[..., Cl+Cm:] = s at (h >> 1, w >> 1).  codes non-NULL (training): one byte per (pixel, quad of l's part),
+ *   (B,H,W,Cl/4) bytes, two bits per channel (bits 2j, 2j+1 of channel 4q + j): the window position 2i + j of the maximum, the first one in
+ *   row-major order on a tie.
+ * backward (somi_zoomcat_bwd_nhwc_f32), one launch, owner-computes: `out` holds dout (read);
+ *   dl[2h+i, 2w+j] = dout_l[h, w] * (1/4 + [code == 2i + j]),  dm = dout_m,  ds[hs, ws] = the sum of dout_s over the (up to) 2x2 pixels it fed;
+ *   the gradients go to the slices l, m, s, each written, or added to what it holds with accumulate[k]; a NULL p skips that gradient. */
+typedef struct somi_zoomcat_desc {
+    somi_slice l, m, s;        /* forward: the inputs, read; backward: dl, dm, ds */
+    somi_slice out;            /* forward: written; backward: dout, read */
+    uint8_t *codes;            /* (B,H,W,Cl/4) bytes */
+    int32_t B, H, W;           /* of m and out */
+    int32_t Cl, Cm, Cs;
+    int32_t accumulate[3];     /* backward: dl, dm, ds are added to */
+} somi_zoomcat_desc;
+size_t somi_zoomcat_desc_bytes(void);
+int somi_zoomcat_nhwc_f32(const somi_zoomcat_desc *d, somi_stream_t stream);
+int somi_zoomcat_bwd_nhwc_f32(const somi_zoomcat_desc *d, somi_stream_t stream);
+
+/* ScalSeq's tail behind the three maps u_i = conv3d(.) kept at their own resolution: u3 (B,H,W,.), u4 (B,H/2,W/2,.),
+ * u5 (B,H/4,W/4,.), H and W multiples of 4, all C wide.  The reference's (B,C,3,H,W) stack holds u3 once, every u4 pixel 4 times and every
+ * u5 pixel 16 times: weights w = 1, 4, 16, N = 3 B H W elements per channel.
+ * stats  (somi_scalseq_stats_f32):           mean and biased variance of the weighted union per channel (per-workgroup partial sums about the
+ *        pivot running_mean - 0 when NULL - then one workgroup per channel quad adds them in a fixed order, in double) -> mean, rstd = 1 / sqrt(var + eps),
+ *        scale = gamma rstd, shift = beta - mean scale (C floats each); running_mean / running_var, when given, move by `momentum` towards
+ *        mean and var N / (N - 1), as nn.BatchNorm3d moves them.
+ * fuse   (somi_scalseq_fuse_nhwc_f32):       out = max_i leaky0.1(scale u_i + shift), u4 read at (h / 2, w / 2), u5 at (h / 4, w / 4); the
+ *        maximum is taken AFTER the affine (a negative gamma reverses the order), ties go to the first i.  scale / shift NULL: 1 and 0 (eval,
+ *        the BatchNorm folded into the producing conv).  codes non-NULL: (B,H,W,C/4) bytes, two bits per channel, the winning i.
+ * route  (somi_scalseq_route_bwd_nhwc_f32):  `out` holds dout.  One lane per (4x4-aligned tile of P3, quad) reads dout and codes once and
+ *        writes g3, g4, g5: the gradient routed to branch i times the LeakyReLU slope there, the 2x2 / 4x4 children summed inside the tile;
+ *        per-workgroup partials of sum g and sum g xhat over all three maps go to `workspace`, a second kernel of the launch adds them in
+ *        a fixed order into sums (2, C) and ADDS dgamma += sum g xhat, dbeta += sum g (NULL: skipped).
+ * apply  (somi_scalseq_apply_bwd_f32):       in place on g3, g4, g5: du_i = scale (g_i - w_i (m1 + xhat_i m2)), m1 = sum g / N,
+ *        m2 = sum g xhat / N, xhat_i = (u_i - mean) rstd. */
+typedef struct somi_scalseq_desc {
+    somi_slice u3, u4, u5;     /* read by all four */
+    somi_slice out;            /* fuse: written; route: dout, read */
+    somi_slice g3, g4, g5;     /* route: written; apply: read and overwritten */
+    uint8_t *codes;            /* fuse: written when given; route: read */
+    const float *gamma, *beta; /* stats */
+    float *mean, *rstd, *scale, *shift;      /* stats: written; route and apply: read (fuse: scale, shift, may be NULL) */
+    float *running_mean, *running_var;       /* stats: updated when given */
+    float *sums;               /* (2, C): route: written; apply: read */
+    float *dgamma, *dbeta;     /* route: added to */
+    int32_t B, H, W, C;        /* of u3 */
+    float eps, momentum;
+    float *workspace;          /* stats and route */
+    uint64_t workspace_floats;
+} somi_scalseq_desc;
+size_t somi_scalseq_desc_bytes(void);
+size_t somi_scalseq_workspace_floats(int B, int H, int W, int C);
+int somi_scalseq_stats_f32(const somi_scalseq_desc *d, somi_stream_t stream);
+int somi_scalseq_fuse_nhwc_f32(const somi_scalseq_desc *d, somi_stream_t stream);
+int somi_scalseq_route_bwd_nhwc_f32(const somi_scalseq_desc *d, somi_stream_t stream);
+int somi_scalseq_apply_bwd_f32(const somi_scalseq_desc *d, somi_stream_t stream);
+
+/* attention_model: the ECA gate on (B, C) vectors and the mix t = x1 gate + x2 in front of the coordinate-attention passes.
+ * somi_eca_gate_f32:      gate[b,c] = sigmoid(sum_j w[j] avg[b, c + j - k / 2]), zero-padded; k odd, at most 9.
+ * somi_eca_gate_bwd_f32:  dz = dgate gate (1 - gate);  davg[b,c] = sum_j w[j] dz[b, c - j + k / 2];  dw[j] = sum_{b,c} dz[b,c] avg[b, c + j - k / 2],
+ *                         written, one workgroup in a fixed order.
+ * mix + means (somi_asf_mix_means_nhwc_f32):   t = x1 gate[b,c] + x2 written, and pool (B, H + W, .) = the row means (rows [0, H)) and column
+ *                         means (rows [H, H + W)) of t in the same pass (somi_coordatt_means with the mix in front; same partial layout).
+ * mix bwd sums (somi_asf_mix_bwd_sums_nhwc_f32):  `t` holds dt (read): ds[b,c] = sum over the pixels of dt x1, partials in `workspace`, then in order.
+ * mix bwd input (somi_asf_mix_bwd_input_nhwc_f32): dx1 = dt gate + davg / (H W), written, or added with `accumulate`.  dx2 is dt itself. */
+typedef struct somi_asfatt_desc {
+    somi_slice x1, x2;         /* mix: read; bwd sums: x1 read */
+    somi_slice t;              /* mix: written; both backward passes: dt, read */
+    somi_slice pool;           /* mix: (B, H + W, .) written */
+    somi_slice dx1;            /* bwd input */
+    const float *gate;         /* (B, C): mix and bwd input */
+    float *ds;                 /* (B, C): bwd sums, written */
+    const float *davg;         /* (B, C): bwd input */
+    int32_t B, H, W, C;
+    int32_t accumulate;        /* bwd input: add to what dx1 holds */
+    float *workspace;          /* mix and bwd sums */
+    uint64_t workspace_floats;
+} somi_asfatt_desc;
+size_t somi_asfatt_desc_bytes(void);
+size_t somi_asfatt_workspace_floats(int B, int H, int W, int C);
+int somi_eca_gate_f32(const float *avg, const float *w, int k, float *gate, int B, int C, somi_stream_t stream);
+int somi_eca_gate_bwd_f32(const float *avg, const float *w, int k, const float *gate, const float *dgate, float *davg, float *dw, int B, int C,
+                          somi_stream_t stream);
+int somi_asf_mix_means_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream);
+int somi_asf_mix_bwd_sums_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream);
+int somi_asf_mix_bwd_input_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream);
 
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed

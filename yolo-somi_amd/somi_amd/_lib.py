@@ -91,6 +91,28 @@ class SimamDesc(C.Structure):
                 ('n', C.c_float), ('lam', C.c_float), ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
 
 
+class ZoomcatDesc(C.Structure):
+    """struct somi_zoomcat_desc (include/somi_hip.h)."""
+    _fields_ = [('l', Slice), ('m', Slice), ('s', Slice), ('out', Slice), ('codes', C.c_void_p), ('B', C.c_int32), ('H', C.c_int32),
+                ('W', C.c_int32), ('Cl', C.c_int32), ('Cm', C.c_int32), ('Cs', C.c_int32), ('accumulate', C.c_int32 * 3)]
+
+
+class ScalseqDesc(C.Structure):
+    """struct somi_scalseq_desc (include/somi_hip.h)."""
+    _fields_ = [('u3', Slice), ('u4', Slice), ('u5', Slice), ('out', Slice), ('g3', Slice), ('g4', Slice), ('g5', Slice), ('codes', C.c_void_p),
+                ('gamma', C.c_void_p), ('beta', C.c_void_p), ('mean', C.c_void_p), ('rstd', C.c_void_p), ('scale', C.c_void_p),
+                ('shift', C.c_void_p), ('running_mean', C.c_void_p), ('running_var', C.c_void_p), ('sums', C.c_void_p), ('dgamma', C.c_void_p),
+                ('dbeta', C.c_void_p), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('eps', C.c_float),
+                ('momentum', C.c_float), ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
+
+
+class AsfAttDesc(C.Structure):
+    """struct somi_asfatt_desc (include/somi_hip.h)."""
+    _fields_ = [('x1', Slice), ('x2', Slice), ('t', Slice), ('pool', Slice), ('dx1', Slice), ('gate', C.c_void_p), ('ds', C.c_void_p),
+                ('davg', C.c_void_p), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('accumulate', C.c_int32),
+                ('workspace', C.c_void_p), ('workspace_floats', C.c_uint64)]
+
+
 class AugSource(C.Structure):
     """struct somi_aug_source (include/somi_hip.h)."""
     _fields_ = [('pixels', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('x1', C.c_int32), ('y1', C.c_int32),
@@ -264,6 +286,22 @@ SIGNATURES = {
     'somi_simam_apply_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
     'somi_simam_bwd_sums_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
     'somi_simam_bwd_input_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),
+    'somi_zoomcat_desc_bytes': (Z, []),
+    'somi_zoomcat_nhwc_f32': (I, [C.POINTER(ZoomcatDesc), S]),
+    'somi_zoomcat_bwd_nhwc_f32': (I, [C.POINTER(ZoomcatDesc), S]),
+    'somi_scalseq_desc_bytes': (Z, []),
+    'somi_scalseq_workspace_floats': (Z, [I, I, I, I]),
+    'somi_scalseq_stats_f32': (I, [C.POINTER(ScalseqDesc), S]),
+    'somi_scalseq_fuse_nhwc_f32': (I, [C.POINTER(ScalseqDesc), S]),
+    'somi_scalseq_route_bwd_nhwc_f32': (I, [C.POINTER(ScalseqDesc), S]),
+    'somi_scalseq_apply_bwd_f32': (I, [C.POINTER(ScalseqDesc), S]),
+    'somi_asfatt_desc_bytes': (Z, []),
+    'somi_asfatt_workspace_floats': (Z, [I, I, I, I]),
+    'somi_eca_gate_f32': (I, [P, P, I, P, I, I, S]),
+    'somi_eca_gate_bwd_f32': (I, [P, P, I, P, P, P, P, I, I, S]),
+    'somi_asf_mix_means_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
+    'somi_asf_mix_bwd_sums_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
+    'somi_asf_mix_bwd_input_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
     'somi_spp_pool_nhwc_f32':(I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),
@@ -317,7 +355,10 @@ def lib():
                         or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)
                         or L.somi_cpca_strip_desc_bytes() != C.sizeof(CpcaStripDesc)
                         or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)
-                        or L.somi_simam_desc_bytes() != C.sizeof(SimamDesc)):
+                        or L.somi_simam_desc_bytes() != C.sizeof(SimamDesc)
+                        or L.somi_zoomcat_desc_bytes() != C.sizeof(ZoomcatDesc)
+                        or L.somi_scalseq_desc_bytes() != C.sizeof(ScalseqDesc)
+                        or L.somi_asfatt_desc_bytes() != C.sizeof(AsfAttDesc)):
             raise RuntimeError('libsomi_hip.so descriptor layout differs from this binding')
         _lib = L
     return _lib

@@ -2868,6 +2868,303 @@ class PSSimAM(nn.Module):
         return self.cv1.backward(dcat, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
 
 
+# ================================================================================================ ASF-YOLO neck
+def _asf_real(a, what):
+    """An input of the ASF blocks: a real tensor (no nn.Upsample view), channel slice offset and width multiples of 4."""
+    if a.up:
+        raise NotImplementedError(f'{what}: an nn.Upsample view as input is not on the SOMI path (the kernels read real maps)')
+    if a.c % 4 or a.coff % 4:
+        raise NotImplementedError(f'{what}: channel counts and slice offsets must be multiples of 4 (C % 4 == 0), got {a.c} at {a.coff}')
+
+
+def _asf_on_gpu(a, what):
+    if not a.t.is_cuda:
+        raise RuntimeError(f'somi_amd {what} runs on the MI355X only (no CPU fallback)')
+
+
+class Zoom_cat(nn.Module):
+    """cat(adaptive_max_pool2d(l) + adaptive_avg_pool2d(l), m, nearest(s)) at m's size (models/common.py:4312-4327) for l exactly 2x and s
+    exactly 1/2 of m per axis: one launch writes the three channel slices of the output (the reference makes two pooled maps, a sum, an
+    upsampled map and a concat); training keeps a two-bit arg-max code per pooled element.  Backward, one owner-computes launch: dl and ds in
+    tensors of their own, dm a slice of the incoming gradient (no copy), as Concat hands its gradients out."""
+
+    def __init__(self, in_dim):
+        super().__init__()
+
+    accumulates, folds_pooled, reduction = False, False, 2       # several inputs: backward(dout) returns the list of their gradients; l is 2x the output
+
+    def forward(self, xs):
+        if len(xs) != 3:
+            raise RuntimeError(f'Zoom_cat takes three inputs (l, m, s), got {len(xs)}')
+        l, m, s = xs
+        for a in xs:
+            _asf_real(a, 'Zoom_cat')
+        B, H, W = m.shape[:3]
+        if tuple(l.shape[:3]) != (B, 2 * H, 2 * W):
+            raise NotImplementedError(f'Zoom_cat: l must be exactly 2x m per axis ({2 * H}x{2 * W}), got {l.shape[1]}x{l.shape[2]} '
+                                      f'(non-integer zoom ratios are not on the SOMI path)')
+        if H % 2 or W % 2 or tuple(s.shape[:3]) != (B, H // 2, W // 2):
+            raise NotImplementedError(f'Zoom_cat: s must be exactly m / 2 per axis, got {s.shape[1]}x{s.shape[2]} under m {H}x{W} '
+                                      f'(non-integer zoom ratios are not on the SOMI path)')
+        _asf_on_gpu(m, 'Zoom_cat')
+        out = concat_act(m.t, H, W, l.c + m.c + s.c)
+        r = ops.zoomcat(l.t, m.t, s.t, l.c, m.c, s.c, l.coff, m.coff, s.coff, out=out.t, codes=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (r[1], l.c, m.c, s.c)
+        return out
+
+    def backward(self, dout):
+        codes, cl, cm, cs = self.__dict__.pop('_ctx')
+        dl, _, ds = ops.zoomcat_backward(dout.t, codes, cl, cm, cs, dout.coff)
+        return [Act(dl, 0, cl), dout.slice(cl, cm), Act(ds, 0, cs)]
+
+
+class ScalSeq(_Packed):
+    """Scale sequence fusion (models/common.py:4330-4355): P4 and P5 through a 1x1 Conv each, nearest-upsampled to P3's size, the three stacked
+    along a depth axis, Conv3d(1x1x1) -> BatchNorm3d -> LeakyReLU(0.1) -> max over the depth.  The Conv3d acts per pixel and the upsampling is
+    nearest at exactly 2x and 4x, so conv and affine commute with it: u_i = conv3d(.) is ONE 1x1 conv per level at the level's own resolution,
+    the batch statistics over the virtual (B,C,3,H,W) stack are the three maps' sums weighted 1, 4, 16 (ops.scalseq_stats), and one launch
+    takes max_i leaky(scale u_i + shift) per P3 pixel (ops.scalseq_fuse).  No stacked and no upsampled tensor exists.  Eval folds the BatchNorm
+    into the shared 1x1 weights.  Backward: two launches (route, apply) give du_i at the maps' own resolutions, then the existing wgrad
+    (three calls into one buffer) and dgrad; conv1 and conv2 are plain Conv backwards."""
+
+    def __init__(self, channel):
+        super().__init__()
+        self.conv1 = Conv(512, channel, 1)
+        self.conv2 = Conv(1024, channel, 1)
+        self.conv3d = nn.Conv3d(channel, channel, kernel_size=(1, 1, 1))
+        self.bn = nn.BatchNorm3d(channel)
+        self.act = nn.LeakyReLU(0.1)
+        self.pool_3d = nn.MaxPool3d(kernel_size=(3, 1, 1))
+
+    accumulates, folds_pooled, reduction = False, False, 1       # several inputs: backward(dout) returns the list of their gradients
+
+    def _pack_params(self):
+        return [*self.conv3d.parameters(), *self.bn.parameters()]
+
+    def _pack(self, dev):
+        c = self.conv3d.out_channels
+        w = self.conv3d.weight.detach().float().view(c, c, 1, 1)
+        b = self.conv3d.bias.detach().float()
+        if not self.training:                                    # BatchNorm3d folded into the shared 1x1 conv
+            s, t = bn_fold(self.bn)
+            w, b = w * s.detach().float().view(-1, 1, 1, 1), b * s.detach().float() + t.detach().float()
+        pk = dict(w=pack_conv_weight(w, cin_pad=pad4(c), cout_pad=c).to(dev), b=b.to(dev).contiguous())
+        if self.training:
+            pk['wt'] = pack_dgrad_weight(w, cin_pad=pad4(c), cout_pad=c).to(dev)
+            pk['gamma'], pk['beta'] = self.bn.weight.detach().float().to(dev).contiguous(), self.bn.bias.detach().float().to(dev).contiguous()
+        return pk
+
+    def forward(self, xs):
+        if len(xs) != 3:
+            raise RuntimeError(f'ScalSeq takes three inputs (p3, p4, p5), got {len(xs)}')
+        p3, p4, p5 = xs
+        c = self.conv3d.out_channels
+        for a in xs:
+            _asf_real(a, 'ScalSeq')
+        if c % 4:
+            raise NotImplementedError(f'ScalSeq({c}): the channel count must be a multiple of 4 (C % 4 == 0)')
+        if p3.c != c:
+            raise NotImplementedError(f'ScalSeq({c}): the p3 input must have {c} channels (the reference stacks it unchanged), got {p3.c}')
+        B, H, W = p3.shape[:3]
+        if H % 4 or W % 4 or tuple(p4.shape[:3]) != (B, H // 2, W // 2) or tuple(p5.shape[:3]) != (B, H // 4, W // 4):
+            raise NotImplementedError(f'ScalSeq: the maps must be exactly 1 : 1/2 : 1/4 per axis, got {tuple(p3.shape[1:3])}, '
+                                      f'{tuple(p4.shape[1:3])}, {tuple(p5.shape[1:3])} (non-integer zoom ratios are not on the SOMI path)')
+        if self.training and ops.SYNC_BN is not None:
+            raise NotImplementedError("ScalSeq's BatchNorm3d has no sync-BN form (--sync-bn)")
+        _asf_on_gpu(p3, 'ScalSeq')
+        pk = self._packed(p3.t.device)
+        srcs = (p3, self.conv1(p4), self.conv2(p5))
+        us = tuple(ops.conv2d_nhwc(a.t, pk['w'], pk['b'], kh=1, kw=1, stride=1, pad=0, act='none', cin=pad4(c), x_coff=a.coff, cout=c,
+                                   out=torch.empty(*a.shape[:3], c, device=a.t.device, dtype=torch.float32), alg_cin=c) for a in srcs)
+        out = new_act(p3.t, H, W, c)
+        if out.t.shape[3] != c:
+            out.t.zero_()                                         # pad channels of a tensor of its own
+        if not self.training:
+            ops.scalseq_fuse(us, c, out=out.t)
+            return out
+        bn = self.bn
+        dev = p3.t.device
+        inplace = bn.running_mean.device == dev and bn.running_mean.dtype == torch.float32
+        rm = bn.running_mean if inplace else bn.running_mean.detach().float().to(dev).clone()
+        rv = bn.running_var if inplace else bn.running_var.detach().float().to(dev).clone()
+        momentum = bn.momentum if bn.momentum is not None else 1.0 / (int(bn.num_batches_tracked) + 1)
+        st = ops.scalseq_stats(us, c, pk['gamma'], pk['beta'], bn.eps, momentum, rm, rv)
+        with torch.no_grad():
+            if not inplace:
+                bn.running_mean.copy_(rm)
+                bn.running_var.copy_(rv)
+            _bump_batches_tracked(bn)
+        _, codes = ops.scalseq_fuse(us, c, st[2], st[3], out=out.t, codes=True)
+        self.__dict__['_ctx'] = (srcs, us, st, codes, pk)
+        return out
+
+    def backward(self, dout):
+        srcs, us, st, codes, pk = self.__dict__.pop('_ctx')
+        c = self.conv3d.out_channels
+        dev = dout.t.device
+        (dgam, dbet), fin = _grad_targets(self.bn.weight, self.bn.bias)
+        gs, sums = ops.scalseq_route_backward(dout.t, codes, us, c, st, do_coff=dout.coff, dgamma=dgam, dbeta=dbet)
+        fin()
+        ops.scalseq_apply_backward(gs, us, c, st, sums)           # gs now hold du_i
+        conv = dict(kh=1, kw=1, stride=1, pad=0)
+        dw, db = None, torch.zeros(c, device=dev)
+        for a, du in zip(srcs, gs):                               # the shared weight: three wgrad calls into one buffer
+            dw = ops.conv2d_wgrad_nhwc(a.t, du, cin=pad4(c), x_coff=a.coff, cout=c, out=dw, accumulate=dw, **conv)
+            ops.chan_sum_(du, c, 0, db)
+        _acc_grad(self.conv3d.weight, dw.view(c, pad4(c))[:, :c].reshape(c, c, 1, 1, 1))
+        _acc_grad(self.conv3d.bias, db)
+        ds = []
+        for a, du in zip(srcs, gs):
+            B, H, W, _ = a.shape
+            dx = torch.empty(B, H, W, pad4(c), device=dev, dtype=torch.float32)
+            ops.conv2d_dgrad_nhwc(du, pk['wt'], B=B, H=H, W=W, cin=pad4(c), cout=c, out=dx, **conv)
+            ds.append(Act(dx, 0, c))
+        return [ds[0], self.conv1.backward(ds[1]), self.conv2.backward(ds[2])]
+
+
+class channel_att(nn.Module):
+    """ECA: x * sigmoid(conv1d_k(global average of x)) along the channels (models/common.py:4358-4374); k from the reference's formula.  Holds the
+    nn.Conv1d; attention_model runs it (ops.global_pool, ops.eca_gate) with the product folded into the mix in front of local_att."""
+
+    def __init__(self, channel, b=1, gamma=2):
+        super().__init__()
+        kernel_size = ops.eca_kernel_size(channel, b, gamma)
+        if kernel_size > ops.ECA_KMAX:
+            raise NotImplementedError(f'channel_att({channel}): kernel size {kernel_size} is beyond {ops.ECA_KMAX}')
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.conv = nn.Conv1d(1, 1, kernel_size=kernel_size, padding=(kernel_size - 1) // 2, bias=False)
+        self.sigmoid = nn.Sigmoid()
+
+    def forward(self, x):
+        raise RuntimeError('channel_att runs inside attention_model on the SOMI path (its product is folded into the mix kernel)')
+
+
+class local_att(nn.Module):
+    """x * s_h * s_w, s_h / s_w = sigmoid(F_h / F_w(relu(bn(conv_1x1(cat(row means, column means)))))) (models/common.py:4377-4409): coordinate
+    attention with ReLU for h-swish and no conv biases.  Holds the parameters; attention_model runs it on the coordinate-attention kernels."""
+
+    def __init__(self, channel, reduction=16):
+        super().__init__()
+        self.conv_1x1 = nn.Conv2d(in_channels=channel, out_channels=channel // reduction, kernel_size=1, stride=1, bias=False)
+        self.relu = nn.ReLU()
+        self.bn = nn.BatchNorm2d(channel // reduction)
+        self.F_h = nn.Conv2d(in_channels=channel // reduction, out_channels=channel, kernel_size=1, stride=1, bias=False)
+        self.F_w = nn.Conv2d(in_channels=channel // reduction, out_channels=channel, kernel_size=1, stride=1, bias=False)
+        self.sigmoid_h = nn.Sigmoid()
+        self.sigmoid_w = nn.Sigmoid()
+
+    def forward(self, x):
+        raise RuntimeError('local_att runs inside attention_model on the SOMI path (its means come from the mix kernel)')
+
+
+class attention_model(_Packed):
+    """local_att(channel_att(x1) + x2) (models/common.py:4412-4424).  Forward: the global average of x1 (ops.global_pool), the ECA gate on
+    (B, C) (ops.eca_gate), ONE pass that writes t = x1 gate + x2 and takes t's row and column means (ops.asf_mix_means), the small convs and
+    the BatchNorm on B (H + W) rows as coordinate attention runs them (ReLU, no biases; F_h and F_w stacked as one 1x1 conv), and
+    ops.coordatt_apply.  Backward: coordinate attention's two passes give dt, which IS dx2; ds = sum dt x1 (one pass), the ECA backward on
+    (B, C), dx1 = dt gate + davg / HW (one pass)."""
+
+    def __init__(self, ch=256):
+        super().__init__()
+        self.channel_att = channel_att(ch)
+        self.local_att = local_att(ch)
+
+    accumulates, folds_pooled, reduction = False, False, 1       # several inputs: backward(dout) returns the list of their gradients
+
+    def _pack(self, dev):
+        la = self.local_att
+        c, mip = la.F_h.out_channels, la.conv_1x1.out_channels
+        mp = pad4(mip)
+        wg = torch.cat([la.F_h.weight, la.F_w.weight]).detach().float()
+        pk = dict(wg=pack_conv_weight(wg, cin_pad=mp).to(dev), we=self.channel_att.conv.weight.detach().float().reshape(-1).to(dev).contiguous())
+        if not self.training:                                    # bn folded into conv_1x1
+            w1, b1 = _fold_conv_bn(la.conv_1x1, la.bn)
+            pk['w1'], pk['b1'] = pack_conv_weight(w1, cin_pad=c, cout_pad=mp).to(dev), torch.zeros(mp, device=dev)
+            pk['b1'][:mip] = b1.to(dev)
+            return pk
+        w1 = la.conv_1x1.weight.detach().float()
+        pk['w1'] = pack_conv_weight(w1, cin_pad=c, cout_pad=mp).to(dev)
+        pk['wt1'] = pack_dgrad_weight(w1, cin_pad=c, cout_pad=mp).to(dev)
+        pk['wtg'] = pack_dgrad_weight(wg, cin_pad=mp, cout_pad=2 * c).to(dev)
+        pk['one'], pk['zero'] = torch.ones(2 * c, device=dev), torch.zeros(2 * c, device=dev)
+        pk.update(_bn_vectors(la.bn, dev, mp))
+        return pk
+
+    def forward(self, xs):
+        if len(xs) != 2:
+            raise RuntimeError(f'attention_model takes two inputs, got {len(xs)}')
+        x1, x2 = xs
+        la = self.local_att
+        c, mip = la.F_h.out_channels, la.conv_1x1.out_channels
+        for a in xs:
+            _asf_real(a, 'attention_model')
+        if tuple(x1.shape[:3]) != tuple(x2.shape[:3]) or x1.c != x2.c:
+            raise NotImplementedError(f'attention_model: inputs of unequal shape, {tuple(x1.shape[:3])} x {x1.c} and {tuple(x2.shape[:3])} x '
+                                      f'{x2.c} (the reference adds them)')
+        if x1.c != c:
+            raise RuntimeError(f'attention_model({c}) got maps of {x1.c} channels')
+        _asf_on_gpu(x1, 'attention_model')
+        pk = self._packed(x1.t.device)
+        B, H, W, _ = x1.shape
+        mp = pad4(mip)
+        avg, _ = ops.global_pool(x1.t, c, x1.coff, want_max=False)
+        gate = ops.eca_gate(avg, pk['we'])
+        t, pool = ops.asf_mix_means(x1.t, x2.t, gate, c, x1.coff, x2.coff)
+        out = new_act(x1.t, H, W, c)
+        if out.t.shape[3] != c:
+            out.t.zero_()                                         # pad channels of a tensor of its own
+        conv = dict(kh=1, kw=1, stride=1, pad=0)
+        if not self.training:
+            t1 = ops.conv2d_nhwc(pool, pk['w1'], pk['b1'], act='relu', cin=c, cout=mp, alg_cout=mip, **conv)
+            g = ops.conv2d_nhwc(t1, pk['wg'], None, act='sigmoid', cin=mp, cout=2 * c, alg_cin=mip, **conv)
+        else:
+            y1 = ops.conv2d_nhwc(pool, pk['w1'], None, act='none', cin=c, cout=mp, alg_cout=mip, **conv)
+            st, commit = _bn_train(la.bn, mp, y1, vec=pk)
+            commit()
+            t1 = ops.chan_affine_act(y1, mp, 0, st[2], st[3], 'relu', 0, torch.empty_like(y1))
+            pre = ops.conv2d_nhwc(t1, pk['wg'], None, act='none', cin=mp, cout=2 * c, alg_cin=mip, **conv)
+            g = ops.chan_affine_act(pre, 2 * c, 0, pk['one'], pk['zero'], 'sigmoid', 0, torch.empty_like(pre))
+            self.__dict__['_ctx'] = (x1, avg, gate, t, pool, y1, st, t1, pre, g, pk)
+        ops.coordatt_apply(t, (g, 0, 0), (g, c, H), c, out=out.t, o_coff=out.coff)
+        return Act(out.t, out.coff, c)
+
+    def backward(self, dout):
+        x1, avg, gate, t, pool, y1, st, t1, pre, g, pk = self.__dict__.pop('_ctx')
+        la = self.local_att
+        c, mip = la.F_h.out_channels, la.conv_1x1.out_channels
+        mp = pad4(mip)
+        B, H, W, _ = x1.shape
+        dev = x1.t.device
+        conv = dict(kh=1, kw=1, stride=1, pad=0)
+        a_h, a_w = (g, 0, 0), (g, c, H)
+        dg = torch.zeros_like(g)                                  # the two quadrants nobody reads keep a zero gradient
+        ops.coordatt_backward_gates(dout.t, t, a_h, a_w, c, dout.coff, 0, da_h=(dg, 0, 0), da_w=(dg, c, H))
+        # through the sigmoid: a BatchNorm-activation backward with frozen unit statistics (F_h and F_w have no bias: its dbeta is dropped)
+        ops.bn_act_backward(dg, 0, pre, 0, 2 * c, pk['zero'], pk['one'], pk['one'], pk['zero'], 'sigmoid', 0, False, dg, 0, None,
+                            torch.zeros(2 * c, device=dev))
+        dwg = ops.conv2d_wgrad_nhwc(t1, dg, cin=mp, cout=2 * c, **conv).view(2 * c, mp)[:, :mip]
+        _acc_grad(la.F_h.weight, dwg[:c].reshape(c, mip, 1, 1))
+        _acc_grad(la.F_w.weight, dwg[c:].reshape(c, mip, 1, 1))
+        dt1 = ops.conv2d_dgrad_nhwc(dg, pk['wtg'], B=B, H=H + W, W=1, cin=mp, cout=2 * c, **conv)
+        dy1 = _bn_backward(la.bn, dt1, 0, y1, st, 'relu', torch.empty_like(y1), mp)
+        dw1 = ops.conv2d_wgrad_nhwc(pool, dy1, cin=c, cout=mp, **conv).view(mp, c)[:mip]
+        _acc_grad(la.conv_1x1.weight, dw1.reshape(mip, c, 1, 1))
+        dpool = ops.conv2d_dgrad_nhwc(dy1, pk['wt1'], B=B, H=H + W, W=1, cin=c, cout=mp, **conv)
+        dt = torch.empty(B, H, W, pad4(c), device=dev, dtype=torch.float32)
+        if pad4(c) != c:
+            dt.zero_()
+        ops.coordatt_backward_input(dout.t, a_h, a_w, (dpool, 0, 0), (dpool, 0, H), c, dout.coff, out=dt)
+        ds = ops.asf_mix_backward_sums(dt, x1.t, c, 0, x1.coff)
+        davg, dwe = ops.eca_gate_backward(avg, pk['we'], gate, ds)
+        _acc_grad(self.channel_att.conv.weight, dwe.view(1, 1, -1))
+        dx1 = torch.empty_like(dt)
+        if pad4(c) != c:
+            dx1.zero_()
+        ops.asf_mix_backward_input(dt, gate, davg, c, out=dx1)
+        return [Act(dx1, 0, c), Act(dt, 0, c)]                    # dx2 is dt itself
+
+
 class ASPP(nn.Module):
     """cv2(cat(t, maxpool3(t), m_0(t), ..)), t = cv1(x) (models/common.py:1829-1843): atrous spatial pyramid pooling.  The m_i are bare 3x3
     nn.Conv2d(bias=False) of dilation = padding = (k_i - 1) // 2 (2, 4, 6 for the default k), no norm and no activation.  Nothing is

@@ -161,6 +161,22 @@ def yolov5_cfg(width=0.50, depth=0.33, nc=80, anchors=None, version='6.0', upsam
                 backbone=copy.deepcopy(bb), head=_swap_upsample(copy.deepcopy(hd), upsample))
 
 
+def yolov5_asf_cfg(depth=0.33, nc=80, anchors=None):
+    """The v6.0 yolov5 backbone at width 1.0 with the ASF-YOLO head (attentional scale sequence fusion; models/common.py:4312-4424).  The
+    reference registers Zoom_cat, ScalSeq and attention_model in its parser (models/yolo.py:1577-1582) but ships no yaml that names them.
+    Width 1.0 is fixed: ScalSeq hard-codes 512 and 1024 input channels and the parser scales none of the three rows' arguments.  Every
+    Zoom_cat takes three inputs of its named width at strides 2 : 1 : 1/2 (rows 12 and 16), ScalSeq reads 256, 512 and 1024 channels at
+    strides 8, 16 and 32 (row 24), attention_model joins the P3 head row and ScalSeq's output (row 25), which Detect reads as its P3 level."""
+    cfg = yolov5_cfg(1.0, depth, nc, anchors)
+    cfg['head'] = [[-1, 1, 'Conv', [512, 1, 1]], [4, 1, 'Conv', [512, 1, 1]], [[-1, 6, -2], 1, 'Zoom_cat', [512]],
+                   [-1, 3, 'C3', [512, False]], [-1, 1, 'Conv', [256, 1, 1]], [2, 1, 'Conv', [256, 1, 1]],
+                   [[-1, 4, -2], 1, 'Zoom_cat', [256]], [-1, 3, 'C3', [256, False]], [-1, 1, 'Conv', [256, 3, 2]],
+                   [[-1, 14], 1, 'Concat', [1]], [-1, 3, 'C3', [512, False]], [-1, 1, 'Conv', [512, 3, 2]],
+                   [[-1, 10], 1, 'Concat', [1]], [-1, 3, 'C3', [1024, False]], [[4, 6, 8], 1, 'ScalSeq', [256]],
+                   [[17, -1], 1, 'attention_model', [256]], [[25, 20, 23], 1, 'Detect', ['nc', 'anchors']]]
+    return cfg
+
+
 def yolov5_swin_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-transformer.yaml (yolov5s with the Focus stem and SPP(5,9,13), a transformer C3 as the last
     backbone row) with C3STR - the Swin variant, models/common.py:1632-1637 - where that file has C3TR (row 9).  The reference registers C3STR

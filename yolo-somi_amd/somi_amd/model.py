@@ -14,7 +14,9 @@ attention, as the C3_CA block and as a CoorAttention row of its own; the dilated
 prior convolutional attention: C3CPCA (a C3 of CPCABottleneck blocks, repeated inside) and a `[-1, 1, 'CPCA', []]` row sized by its input,
 channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.py); and the parameter-free SimAM family: a `SimAM` row
 (from -1 only, arguments as written), `SimAMWithSlicing` and `SimAMWithFlexibleSlicing` rows (sized by their input; the channel count the row
-names must be the input's), `Conv_SWS` (a Conv behind sliding-window SimAM, width-scaled like Conv) and `PSSimAM` (arguments as written).
+names must be the input's), `Conv_SWS` (a Conv behind sliding-window SimAM, width-scaled like Conv) and `PSSimAM` (arguments as written);
+and the ASF-YOLO neck: `Zoom_cat` (three inputs at strides 2 : 1 : 1/2, c2 = 3 * args[0]), `ScalSeq` (three inputs of args[0], 512 and 1024
+channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] channels), none of them width-scaled.
 """
 import math
 from copy import deepcopy
@@ -124,6 +126,16 @@ def parse_model(d, ch):
         elif name == 'Concat':                                    # models/yolo.py:1589-1591
             m = B.Concat
             c2 = sum(ch[x] for x in f)
+        elif name == 'Zoom_cat':                                  # models/yolo.py:1577-1578: c2 = 3 * args[0], unscaled
+            m = B.Zoom_cat
+            c2 = 3 * args[0]
+            if not isinstance(f, (list, tuple)) or len(f) != 3 or sum(ch[x] for x in f) != c2:
+                got = [ch[x] for x in f] if isinstance(f, (list, tuple)) else ch[f]
+                raise ValueError(f"a 'Zoom_cat' row that names {args[0]} channels records 3 * {args[0]} = {c2} for the rows behind it, but its "
+                                 f'inputs carry {got}: the reference fails in the next conv (models/yolo.py:1578)')
+        elif name in ('attention_model', 'ScalSeq'):              # models/yolo.py:1579-1582: c2 = args[0], unscaled
+            m = B.attention_model if name == 'attention_model' else B.ScalSeq
+            c2 = args[0]
         elif name in _HEADS:                                      # models/yolo.py:1606-1619
             m = _HEADS[name]
             args.append([ch[x] for x in f])

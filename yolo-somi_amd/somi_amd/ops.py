@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns the HBM allocations and the stream; all arithm
 libsomi_hip.so.  Tensors must live on the GPU; anything else raises.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -634,6 +635,245 @@ def simam_backward_input(dout, x, stats, sums, c, grid, do_coff=0, x_coff=0, *, 
     d.y, d.dx, d.sums = _slice(dout, do_coff), _slice(out, dx_coff), _ptr(sums)
     d.accumulate, d.add_input = int(accumulate), int(add_input)
     check(_lib.lib().somi_simam_bwd_input_nhwc_f32(C.byref(d), _stream()), 'simam_backward_input')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- ASF-YOLO neck (asf.hip)
+def _map_check(t, shape, what):
+    if tuple(t.shape[:3]) != tuple(shape):
+        raise RuntimeError(f'{what} must be {tuple(shape)} + (channels,), got {tuple(t.shape)}')
+
+
+def zoomcat_small_size(size):
+    """The size of Zoom_cat's small map along an axis of the middle map's `size`: read at (h >> 1, w >> 1)."""
+    return (size + 1) // 2
+
+
+def zoomcat(l, m, s, cl, cm, cs, l_coff=0, m_coff=0, s_coff=0, *, out=None, o_coff=0, codes=False):
+    """Zoom_cat in one launch: out[..., 0:cl] = max2x2(l) + mean2x2(l), [cl:cl+cm] = m, [cl+cm:] = s at (h >> 1, w >> 1), from out's channel
+    o_coff.  l (B,2H,2W,.), m (B,H,W,.), s (B,(H+1)//2,(W+1)//2,.).  m=None: the producer has written m's slice of `out` already; `out` must
+    then be given.  codes=True (training): -> (out, codes), one byte per (pixel, quad of l's part) for zoomcat_backward."""
+    B, H2, W2, _ = l.shape
+    H, W = H2 // 2, W2 // 2
+    if H2 != 2 * H or W2 != 2 * W:
+        raise RuntimeError(f'zoomcat: l must have even sizes, got {tuple(l.shape)}')
+    if m is None and out is None:
+        raise RuntimeError('zoomcat: m in place needs the output tensor that holds it')
+    if m is not None:
+        _map_check(m, (B, H, W), 'zoomcat: m')
+    _map_check(s, (B, zoomcat_small_size(H), zoomcat_small_size(W)), 'zoomcat: s')
+    if out is None:
+        out = torch.empty(B, H, W, cl + cm + cs, device=l.device, dtype=torch.float32)
+    _map_check(out, (B, H, W), 'zoomcat: out')
+    d = _lib.ZoomcatDesc()
+    d.B, d.H, d.W, d.Cl, d.Cm, d.Cs = B, H, W, cl, cm, cs
+    d.l, d.s, d.out = _slice(l, l_coff), _slice(s, s_coff), _slice(out, o_coff)
+    if m is not None:
+        d.m = _slice(m, m_coff)
+    arg = torch.empty(B, H, W, max(cl // 4, 1), device=l.device, dtype=torch.uint8) if codes else None
+    d.codes = _ptr(arg)
+    check(_lib.lib().somi_zoomcat_nhwc_f32(C.byref(d), _stream()), 'zoomcat')
+    return (out, arg) if codes else out
+
+
+def zoomcat_backward(dout, codes, cl, cm, cs, do_coff=0, *, dl=True, dm=None, ds=True, accumulate=(False, False, False)):
+    """One owner-computes launch: dl[2h+i, 2w+j] = dout_l[h, w] (1/4 + [code == 2i + j]), dm = dout_m, ds = the sum of dout_s over the pixels a
+    small-map pixel fed.  Each of dl / dm / ds: None skips it, True makes a tensor, (tensor, channel offset) is written - or added to where
+    accumulate[k].  -> (dl, dm, ds) tensors (None where skipped)."""
+    B, H, W, _ = dout.shape
+    shapes = ((B, 2 * H, 2 * W, cl), (B, H, W, cm), (B, zoomcat_small_size(H), zoomcat_small_size(W), cs))
+    d = _lib.ZoomcatDesc()
+    d.B, d.H, d.W, d.Cl, d.Cm, d.Cs = B, H, W, cl, cm, cs
+    d.out, d.codes = _slice(dout, do_coff), _ptr(codes)
+    outs = []
+    for k, (name, tgt) in enumerate((('l', dl), ('m', dm), ('s', ds))):
+        if tgt is None:
+            outs.append(None)
+            continue
+        if tgt is True:
+            if accumulate[k]:
+                raise RuntimeError('zoomcat_backward: accumulate needs the tensor to add to')
+            tgt = (torch.empty(*shapes[k], device=dout.device, dtype=torch.float32), 0)
+        _map_check(tgt[0], shapes[k][:3], f'zoomcat_backward: d{name}')
+        setattr(d, name, _slice(*tgt))
+        d.accumulate[k] = int(accumulate[k])
+        outs.append(tgt[0])
+    if outs[0] is not None and (codes is None or codes.dtype != torch.uint8 or codes.numel() != B * H * W * (cl // 4)):
+        raise RuntimeError(f'zoomcat_backward: codes must hold {B * H * W * (cl // 4)} bytes')
+    check(_lib.lib().somi_zoomcat_bwd_nhwc_f32(C.byref(d), _stream()), 'zoomcat_backward')
+    return tuple(outs)
+
+
+def _scalseq_desc(us, c, coffs, what):
+    u3, u4, u5 = us
+    B, H, W, _ = u3.shape
+    if H % 4 or W % 4:
+        raise RuntimeError(f'{what}: the P3 map must have sizes that are multiples of 4, got {H}x{W}')
+    _map_check(u4, (B, H // 2, W // 2), f'{what}: u4')
+    _map_check(u5, (B, H // 4, W // 4), f'{what}: u5')
+    d = _lib.ScalseqDesc()
+    d.B, d.H, d.W, d.C = B, H, W, c
+    d.u3, d.u4, d.u5 = _slice(u3, coffs[0]), _slice(u4, coffs[1]), _slice(u5, coffs[2])
+    return d
+
+
+def _scalseq_workspace(d, dev):
+    ws = torch.empty(max(_lib.lib().somi_scalseq_workspace_floats(d.B, d.H, d.W, d.C), 4), device=dev, dtype=torch.float32)
+    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return ws
+
+
+def _scalseq_stats_args(d, st):
+    d.mean, d.rstd, d.scale, d.shift = (_ptr(_f32c(v)) for v in st)
+
+
+def scalseq_stats(us, c, gamma, beta, eps, momentum, running_mean=None, running_var=None, coffs=(0, 0, 0)):
+    """BatchNorm3d's batch statistics over ScalSeq's virtual (B,C,3,H,W) stack from the three maps us = (u3, u4, u5) at their own resolutions
+    (weights 1, 4, 16; N = 3 B H W) -> (mean, rstd, scale, shift); the running statistics move as nn.BatchNorm3d moves them (pivot of the
+    partial sums: running_mean)."""
+    if SYNC_BN is not None:
+        raise NotImplementedError("ScalSeq's BatchNorm3d has no sync-BN form (--sync-bn): its statistics are taken on one rank")
+    d = _scalseq_desc(us, c, coffs, 'scalseq_stats')
+    dev = us[0].device
+    st = tuple(torch.empty(c, device=dev, dtype=torch.float32) for _ in range(4))
+    _scalseq_stats_args(d, st)
+    d.gamma, d.beta, d.eps, d.momentum = _ptr(_f32c(gamma)), _ptr(_f32c(beta)), float(eps), float(momentum)
+    d.running_mean, d.running_var = _ptr(running_mean), _ptr(running_var)
+    ws = _scalseq_workspace(d, dev)                               # noqa: F841  (alive until the launch is enqueued)
+    check(_lib.lib().somi_scalseq_stats_f32(C.byref(d), _stream()), 'scalseq_stats')
+    return st
+
+
+def scalseq_fuse(us, c, scale=None, shift=None, coffs=(0, 0, 0), *, out=None, o_coff=0, codes=False):
+    """out = max_i leaky0.1(scale u_i + shift) per P3 pixel, u4 read at (h / 2, w / 2), u5 at (h / 4, w / 4), ties to the first i; scale / shift
+    None: 1 and 0.  codes=True: -> (out, codes), one byte per (pixel, quad) for scalseq_route_backward."""
+    d = _scalseq_desc(us, c, coffs, 'scalseq_fuse')
+    B, H, W, _ = us[0].shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=us[0].device, dtype=torch.float32)
+    _map_check(out, (B, H, W), 'scalseq_fuse: out')
+    d.out = _slice(out, o_coff)
+    if scale is not None:
+        d.scale, d.shift = _ptr(_f32c(scale)), _ptr(_f32c(shift))
+    arg = torch.empty(B, H, W, c // 4, device=us[0].device, dtype=torch.uint8) if codes else None
+    d.codes = _ptr(arg)
+    check(_lib.lib().somi_scalseq_fuse_nhwc_f32(C.byref(d), _stream()), 'scalseq_fuse')
+    return (out, arg) if codes else out
+
+
+def scalseq_route_backward(dout, codes, us, c, st, coffs=(0, 0, 0), *, do_coff=0, dgamma=None, dbeta=None):
+    """Pass 1 of ScalSeq's backward: dout and the codes read once per 4x4 tile of P3 -> g3, g4, g5 (the routed gradient times the LeakyReLU
+    slope, children summed, at the maps' own resolutions) and sums (2, c) = (sum g, sum g xhat); dgamma / dbeta, when given, are ADDED to."""
+    d = _scalseq_desc(us, c, coffs, 'scalseq_route_backward')
+    B, H, W, _ = us[0].shape
+    _map_check(dout, (B, H, W), 'scalseq_route_backward: dout')
+    if codes.dtype != torch.uint8 or codes.numel() != B * H * W * (c // 4):
+        raise RuntimeError(f'scalseq_route_backward: codes must hold {B * H * W * (c // 4)} bytes')
+    dev = dout.device
+    gs = tuple(torch.empty(*u.shape[:3], c, device=dev, dtype=torch.float32) for u in us)
+    sums = torch.empty(2, c, device=dev, dtype=torch.float32)
+    d.out, d.codes, d.sums = _slice(dout, do_coff), _ptr(codes), _ptr(sums)
+    d.g3, d.g4, d.g5 = (_slice(g, 0) for g in gs)
+    _scalseq_stats_args(d, st)
+    d.dgamma, d.dbeta = _ptr(dgamma), _ptr(dbeta)
+    ws = _scalseq_workspace(d, dev)                               # noqa: F841
+    check(_lib.lib().somi_scalseq_route_bwd_nhwc_f32(C.byref(d), _stream()), 'scalseq_route_backward')
+    return gs, sums
+
+
+def scalseq_apply_backward(gs, us, c, st, sums, coffs=(0, 0, 0), g_coffs=(0, 0, 0)):
+    """Pass 2, in place on gs: du_i = scale (g_i - w_i (m1 + xhat_i m2)), w = 1, 4, 16, m1 = sum g / N, m2 = sum g xhat / N.  -> gs."""
+    d = _scalseq_desc(us, c, coffs, 'scalseq_apply_backward')
+    for g, u in zip(gs, us):
+        _map_check(g, u.shape[:3], 'scalseq_apply_backward: a gradient map')
+    d.g3, d.g4, d.g5 = (_slice(g, o) for g, o in zip(gs, g_coffs))
+    _scalseq_stats_args(d, st)
+    d.sums = _ptr(_f32c(sums))
+    check(_lib.lib().somi_scalseq_apply_bwd_f32(C.byref(d), _stream()), 'scalseq_apply_backward')
+    return gs
+
+
+ECA_KMAX = 9            # ECA_KMAX of asf.hip
+
+
+def eca_kernel_size(channel, b=1, gamma=2):
+    """channel_att's kernel size (models/common.py:4361-4362): 3 for 8 to 64 channels, 5 for 128 to 1024."""
+    k = int(abs((math.log(channel, 2) + b) / gamma))
+    return k if k % 2 else k + 1
+
+
+def eca_gate(avg, w):
+    """gate[b,c] = sigmoid(sum_j w[j] avg[b, c + j - k // 2]), zero-padded: nn.Conv1d(1, 1, k, padding=k // 2, bias=False) along the channels."""
+    B, c = avg.shape
+    gate = torch.empty_like(avg)
+    check(_lib.lib().somi_eca_gate_f32(_ptr(_f32c(avg)), _ptr(_f32c(w)), w.numel(), _ptr(gate), B, c, _stream()), 'eca_gate')
+    return gate
+
+
+def eca_gate_backward(avg, w, gate, dgate):
+    """-> (davg (B, c), dw (k)) of eca_gate, both written."""
+    B, c = avg.shape
+    davg, dw = torch.empty_like(avg), torch.empty(w.numel(), device=avg.device, dtype=torch.float32)
+    check(_lib.lib().somi_eca_gate_bwd_f32(_ptr(_f32c(avg)), _ptr(_f32c(w)), w.numel(), _ptr(_f32c(gate)), _ptr(_f32c(dgate)), _ptr(davg), _ptr(dw),
+                                           B, c, _stream()), 'eca_gate_backward')
+    return davg, dw
+
+
+def _asfatt_desc(B, H, W, c, workspace_on=None):
+    d = _lib.AsfAttDesc()
+    d.B, d.H, d.W, d.C = B, H, W, c
+    ws = None
+    if workspace_on is not None:
+        ws = torch.empty(max(_lib.lib().somi_asfatt_workspace_floats(B, H, W, c), 4), device=workspace_on, dtype=torch.float32)
+        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return d, ws
+
+
+def _gate_check(g, B, c, what):
+    if tuple(g.shape) != (B, c):
+        raise RuntimeError(f'{what} must be ({B}, {c}), got {tuple(g.shape)}')
+    return _ptr(_f32c(g))
+
+
+def asf_mix_means(x1, x2, gate, c, x1_coff=0, x2_coff=0, *, t=None, t_coff=0, pool=None, p_coff=0):
+    """t = x1 * gate[b,c] + x2 written, and pool (B, H + W, 1, .) = the row means and column means of t from the same pass.  -> (t, pool)."""
+    B, H, W, _ = x1.shape
+    _map_check(x2, (B, H, W), 'asf_mix_means: x2')
+    if t is None:
+        t = torch.empty(B, H, W, c, device=x1.device, dtype=torch.float32)
+    if pool is None:
+        pool = torch.empty(B, H + W, 1, c, device=x1.device, dtype=torch.float32)
+    _map_check(t, (B, H, W), 'asf_mix_means: t')
+    _map_check(pool, (B, H + W, 1), 'asf_mix_means: pool')
+    d, ws = _asfatt_desc(B, H, W, c, x1.device)                   # noqa: F841  (alive until the launch is enqueued)
+    d.x1, d.x2, d.t, d.pool, d.gate = _slice(x1, x1_coff), _slice(x2, x2_coff), _slice(t, t_coff), _slice(pool, p_coff), _gate_check(gate, B, c, 'gate')
+    check(_lib.lib().somi_asf_mix_means_nhwc_f32(C.byref(d), _stream()), 'asf_mix_means')
+    return t, pool
+
+
+def asf_mix_backward_sums(dt, x1, c, dt_coff=0, x1_coff=0):
+    """ds[b,c] = sum over the pixels of dt * x1: the gradient of the gate."""
+    B, H, W, _ = x1.shape
+    _map_check(dt, (B, H, W), 'asf_mix_backward_sums: dt')
+    ds = torch.empty(B, c, device=x1.device, dtype=torch.float32)
+    d, ws = _asfatt_desc(B, H, W, c, x1.device)                   # noqa: F841
+    d.x1, d.t, d.ds = _slice(x1, x1_coff), _slice(dt, dt_coff), _ptr(ds)
+    check(_lib.lib().somi_asf_mix_bwd_sums_nhwc_f32(C.byref(d), _stream()), 'asf_mix_backward_sums')
+    return ds
+
+
+def asf_mix_backward_input(dt, gate, davg, c, dt_coff=0, *, out=None, dx_coff=0, accumulate=False):
+    """dx1 = dt * gate + davg / (H W), written into out's slice at dx_coff, or added to it with `accumulate`."""
+    B, H, W, _ = dt.shape
+    if out is None:
+        if accumulate:
+            raise RuntimeError('asf_mix_backward_input: accumulate needs the tensor to add to')
+        out = torch.empty(B, H, W, c, device=dt.device, dtype=torch.float32)
+    _map_check(out, (B, H, W), 'asf_mix_backward_input: dx1')
+    d, _ = _asfatt_desc(B, H, W, c)
+    d.t, d.dx1, d.accumulate = _slice(dt, dt_coff), _slice(out, dx_coff), int(accumulate)
+    d.gate, d.davg = _gate_check(gate, B, c, 'gate'), _gate_check(davg, B, c, 'davg')
+    check(_lib.lib().somi_asf_mix_bwd_input_nhwc_f32(C.byref(d), _stream()), 'asf_mix_backward_input')
     return out
 
 
