@@ -592,6 +592,30 @@ int somi_asf_mix_means_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream)
 int somi_asf_mix_bwd_sums_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream);
 int somi_asf_mix_bwd_input_nhwc_f32(const somi_asfatt_desc *d, somi_stream_t stream);
 
+/* Slim-neck GSConv (models/common.py:9586-9610; gsconv.hip).  With Ch = c2 / 2 (a multiple of 4), x1 = cv1(x) and x_2 = cv2_2(cv2_1(x1)), two
+ * stacked depthwise 3x3 Conv blocks, the module returns the fixed channel de-interleave of s = cat(x1, x_2): out[o] = s[2 o] for o < Ch and
+ * s[2 (o - Ch) + 1] otherwise (not channel_shuffle(groups=2), which interleaves).  A source quad J of s (channels [4 J, 4 J + 4), J < Ch / 2)
+ * therefore lands as two float2: its even channels at out[2 J, 2 J + 2), its odd ones at out[Ch + 2 J, Ch + 2 J + 2).  All three entries walk
+ * source quads that way, so no width has a special case.  `out` / `dout` / `residual` are slices of width 2 Ch, the others of width Ch.  fp32,
+ * deterministic (no atomics), no workspace.
+ *
+ * tail (somi_gs_tail_nhwc_f32), inference: reads x1 once per tile and writes the whole module output,
+ *   t = act(dw1(x1) + b1) inside the image and ZERO outside it (cv2_2 pads its input with zeros; evaluating dw1 on the padded x1 there would give
+ *   act(b1)), x_2 = act(dw2(t) + b2), out = shuffle(x1, x_2) [+ residual].  w1 / w2: the depthwise weights with BatchNorm folded, [9][w_cs]
+ *   (pack_gconv_weight), w_cs % 4 == 0, w_cs >= Ch; b1 / b2: Ch floats; all 16-byte aligned.  One workgroup owns 16 x 16 pixels x 4 quads (8 x 16
+ *   pixels x 8 quads from Ch = 32 up): x1 with a 2-pixel halo and t with a 1-pixel halo live in LDS, nothing between x1 and out reaches memory.
+ *   out must not overlap x1.
+ * shuffle (somi_gs_shuffle_affine_act_nhwc_f32), training forward: out = shuffle(z1, act(y2 * scale + shift)) [+ residual]; z1 = cv1's activated
+ *   output, y2 = cv2_2's raw conv output, scale / shift its BatchNorm's (Ch floats each, 16-byte aligned; both NULL: the identity).
+ * unshuffle (somi_gs_unshuffle_nhwc_f32), training backward: d1[s] / d2[s] = dout[where s went], the exact inverse permutation.
+ * The two streaming entries walk somi_gs_tiles_per_workgroup(npix, Ch) pixel tiles per workgroup (host arithmetic; 0 for sizes they refuse). */
+int somi_gs_tiles_per_workgroup(long npix, int Ch);
+int somi_gs_tail_nhwc_f32(somi_slice x1, const float *w1, const float *b1, const float *w2, const float *b2, int w_cs, int act, somi_slice out,
+                          somi_slice residual, int B, int H, int W, int Ch, somi_stream_t stream);
+int somi_gs_shuffle_affine_act_nhwc_f32(somi_slice z1, somi_slice y2, const float *scale, const float *shift, int act, somi_slice out,
+                                        somi_slice residual, long npix, int Ch, somi_stream_t stream);
+int somi_gs_unshuffle_nhwc_f32(somi_slice dout, somi_slice d1, somi_slice d2, long npix, int Ch, somi_stream_t stream);
+
 /* BiFPN fusion (models/common.py:3695-3704) with the preceding nn.Upsample(2,'nearest') folded in:
  * y = sum_i wn[i] * src_i, where source i is read at (h>>up[i], w>>up[i]).  wn = w / (sum swish(w) + eps) is computed
  * inside the kernel from the raw parameter w_dev (n_in floats on the device; no host copy of it is needed).

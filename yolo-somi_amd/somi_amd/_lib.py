@@ -302,6 +302,10 @@ SIGNATURES = {
     'somi_asf_mix_means_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
     'somi_asf_mix_bwd_sums_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
     'somi_asf_mix_bwd_input_nhwc_f32': (I, [C.POINTER(AsfAttDesc), S]),
+    'somi_gs_tiles_per_workgroup': (I, [C.c_long, I]),
+    'somi_gs_tail_nhwc_f32': (I, [Slice, P, P, P, P, I, I, Slice, Slice, I, I, I, I, S]),
+    'somi_gs_shuffle_affine_act_nhwc_f32': (I, [Slice, Slice, P, P, I, Slice, Slice, C.c_long, I, S]),
+    'somi_gs_unshuffle_nhwc_f32': (I, [Slice, Slice, Slice, C.c_long, I, S]),
     'somi_spp_pool_nhwc_f32':(I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_spp_pool_bwd_nhwc_f32': (I, [P, P, I, I, I, I, I, I, I, I, I, I, S]),
     'somi_carafe_nhwc_f32': (I, [P, P, P, P] + [I] * 11 + [S]),

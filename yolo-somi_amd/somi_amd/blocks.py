@@ -1843,6 +1843,168 @@ class C3Ghost(C3):
         self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
 
 
+class GSConv(nn.Module):
+    """Slim-neck GSConv (models/common.py:9586-9610): x1 = cv1(x), x_2 = cv2_2(cv2_1(x1)) - two stacked depthwise 3x3 Convs, not the paper's
+    one 5x5 - and the fixed de-interleave of cat(x1, x_2): output channel o reads source 2 o for o < c_, 2 (o - c_) + 1 otherwise.
+    Eval: cv1's launch, then ONE launch for everything behind it (ops.gs_tail: both depthwise convs with their folded BatchNorms and
+    activations, the shuffle, the residual).  Training: the three Convs' own passes, cv2_2's BatchNorm + activation pass being the one that also
+    shuffles (ops.gs_shuffle_affine_act); backward is one un-shuffle pass in front of the three Convs' backward chain.
+    act=False switches the activation off on all three convs."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, p, g, d, act)
+        self.cv2_1 = Conv(c_, c_, 3, 1, p, c_, d, act)
+        self.cv2_2 = Conv(c_, c_, 3, 1, p, c_, d, act)
+
+    accumulates = folds_pooled = False                            # Conv's own are True: the shuffle stands between this block's output and a Conv
+    reduction = property(lambda self: self.cv1.reduction)
+
+    def forward(self, x, out=None, residual=None):
+        """out: the 2 c_ wide slice to write (a tensor of its own when None); residual: an Act of 2 c_ channels added to the shuffled output."""
+        c_ = self.cv1.conv.out_channels
+        if c_ % 4:
+            raise NotImplementedError(f'GSConv half width {c_} (c2 // 2) must be a multiple of 4 on the MI355X path')
+        x1 = self.cv1(x)
+        if out is None:
+            out = new_act(x1.t, x1.shape[1], x1.shape[2], 2 * c_)
+        res_t, res_coff = (None, 0) if residual is None else (residual.t, residual.coff)
+        act = _act_name(self.cv2_2.act)
+        if not self.training:
+            (w1, b1), (w2, b2) = self.cv2_1._packed(x1.t.device), self.cv2_2._packed(x1.t.device)
+            ops.gs_tail(x1.t, w1, b1, w2, b2, c_, act, x1.coff, out=out.t, o_coff=out.coff, residual=res_t, res_coff=res_coff)
+            return Act(out.t, out.coff, 2 * c_)
+        t = self.cv2_1(x1)
+        m = self.cv2_2                                            # Conv._forward_train up to its BatchNorm + activation pass, which the shuffle is
+        pk = m._packed(t.t.device)
+        B, H, W, _ = t.shape
+        y = torch.empty(B, H, W, c_, device=t.t.device, dtype=torch.float32)
+        st = {'pivot': pk['rm']}
+        ops.gconv2d_nhwc(t.t, pk['gw'], c1=c_, c2=c_, groups=c_, k=3, stride=1, x_coff=t.coff, out=y, cw=c_, bn_stats=st)
+        (mean, rstd, scale, shift), commit = _bn_train(m.bn, c_, y, partials=st, npix=B * H * W, vec=pk)
+        commit()
+        m.__dict__['_ctx'] = (t, y, mean, rstd, scale, shift, pk)
+        ops.gs_shuffle_affine_act(x1.t, y, c_, scale, shift, act, x1.coff, 0, out=out.t, o_coff=out.coff, residual=res_t, res_coff=res_coff)
+        return Act(out.t, out.coff, 2 * c_)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True, also_add=None):
+        """x1's gradient is its half of the un-shuffled dout plus what flows back through the two depthwise convs: cv2_1's dgrad pass writes the sum."""
+        c_ = self.cv1.conv.out_channels
+        d1, d2 = ops.gs_unshuffle(dout.t, c_, dout.coff)
+        dt = self.cv2_2.backward(Act(d2, 0, c_))
+        dx1 = self.cv2_1.backward(dt, also_add=Act(d1, 0, c_))
+        return self.cv1.backward(dx1, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=also_add)
+
+
+class GSBottleneck(nn.Module):
+    """conv_lighting(x) + shortcut(x) (models/common.py:9628-9642): GSConv 1x1 -> GSConv 3x3 without activation, and a 1x1 Conv without
+    activation as the shortcut, always added: it rides the second GSConv's output pass."""
+
+    def __init__(self, c1, c2, k=3, s=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.conv_lighting = nn.Sequential(GSConv(c1, c_, 1, 1), GSConv(c_, c2, 3, 1, act=False))
+        self.shortcut = Conv(c1, c2, 1, 1, act=False)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x, out=None):
+        g1, g2 = self.conv_lighting
+        return g2(g1(x), out=out, residual=self.shortcut(x))
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        g1, g2 = self.conv_lighting
+        dx = g1.backward(g2.backward(dout), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+        self.shortcut.backward(dout, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return dx
+
+
+class VoVGSCSP(nn.Module):
+    """cv3(cat(cv2(x), gsb(cv1(x)))) (models/common.py:9665-9681), cv2's branch first.  cv2 and the last bottleneck write the two halves of
+    cv3's input buffer.  `res` is built, loaded and saved like the reference's and, like there, never runs: no gradient, its running statistics
+    and step counter stay as loaded, and no optimizer step moves it (never_runs, read by optim.FusedAdamEMA)."""
+    never_runs = ('res',)
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.gsb = nn.Sequential(*(GSBottleneck(c_, c_, e=1.0) for _ in range(n)))
+        self.res = Conv(c_, c_, 3, 1, act=False)
+        self.cv3 = Conv(2 * c_, c2, 1)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x):
+        c_ = self.cv1.conv.out_channels
+        if c_ % 4:
+            raise NotImplementedError(f'{type(self).__name__} hidden width {c_} must be a multiple of 4 on the MI355X path')
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, 2 * c_)
+        n = len(self.gsb)
+        self.cv2(x, out=cat.slice(0, c_))
+        t = self.cv1(x, out=cat.slice(c_, c_) if n == 0 else None)
+        for i, blk in enumerate(self.gsb):
+            t = blk(t, out=cat.slice(c_, c_) if i == n - 1 else None)
+        return self.cv3(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        c_ = self.cv1.conv.out_channels
+        dcat = self.cv3.backward(dout)
+        dx = self.cv2.backward(dcat.slice(0, c_), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+        d = dcat.slice(c_, c_)
+        for blk in reversed(self.gsb):
+            d = blk.backward(d)
+        self.cv1.backward(d, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return dx
+
+
+class GSCBAMBottleneck(nn.Module):
+    """GSConv -> channel attention -> spatial attention -> GSConv without activation (+ x) (models/common.py:737-757): CBAMBottleneck's layout
+    without its step-C-in-BatchNorm fusion, which needs a Conv right in front of the attention.  The CBAM training path works on whole
+    unpadded tensors, so the hidden width c_ must be a multiple of 4 (of 8 for the GSConv that writes it)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5, k=(1, 3), ratio=8, kernel_size=3):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = GSConv(c1, c_, k[0], 1)
+        self.cv2 = GSConv(c_, c2, k[1], 1, act=False)
+        self.add = shortcut and c1 == c2
+        self.channel_attention = ChannelAttentionModule(c_, ratio)
+        self.spatial_attention = SpatialAttentionModule(kernel_size)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x, out=None):
+        t = self.cv1(x)
+        ca = self.channel_attention(t)
+        t2 = self.spatial_attention(t, ca)                        # eval: t scaled in place; training: a new tensor, t is kept
+        return self.cv2(t2, out=out, residual=x if self.add else None)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = self.cv2.backward(dout)                               # d(t * ca * sa), a whole tensor of its own
+        dca, amaxp = self.spatial_attention.backward(d.t, t_max=self.channel_attention.__dict__['_ctx'][2], bn=None)
+        self.channel_attention.backward(dca, d, amaxp)            # adds the pooled paths into d in place
+        c1 = self.cv1.cv1.conv.in_channels
+        fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0  # the shortcut's gradient rides cv1's dgrad epilogue
+        dx = self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if self.add and not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class VoVGSCSPCBAM(VoVGSCSP):
+    """VoVGSCSP whose bottlenecks are GSCBAMBottleneck(c_, c_, e=1.0) (models/common.py:2697-2711); `shortcut` is ignored there too, and
+    `res` is as unused."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.gsb = nn.Sequential(*(GSCBAMBottleneck(c_, c_, e=1.0) for _ in range(n)))
+
+
 class C2f(nn.Module):
     """cv2(cat(cv1(x).chunk(2), m_1, ..., m_n)) (models/common.py:2638-2658), laid out like C2fCBAM: all (2+n) pieces live in one buffer,
     block i reads piece i+1 and writes piece i+2.  In backward a block's data gradient is added into the piece that already holds cv2's."""

@@ -177,6 +177,17 @@ def yolov5_asf_cfg(depth=0.33, nc=80, anchors=None):
     return cfg
 
 
+def yolov5_slimneck_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
+    """yolov5s 6.0 with the slim-neck head (GSConv, models/common.py:9586-9610; VoVGSCSPCBAM, :2697-2711).  The reference registers both in its
+    parser (models/yolo.py:1473-1474, VoVGSCSPCBAM among the modules repeated inside, :1489) but ships no yaml that names them.  The head's
+    four Conv rows become GSConv with the same arguments and its four C3 rows [c, False] VoVGSCSPCBAM with the same arguments and n; the
+    backbone and Detect are yolov5_cfg's."""
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    for row in cfg['head']:
+        row[2] = {'Conv': 'GSConv', 'C3': 'VoVGSCSPCBAM'}.get(row[2], row[2])
+    return cfg
+
+
 def yolov5_swin_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-transformer.yaml (yolov5s with the Focus stem and SPP(5,9,13), a transformer C3 as the last
     backbone row) with C3STR - the Swin variant, models/common.py:1632-1637 - where that file has C3TR (row 9).  The reference registers C3STR

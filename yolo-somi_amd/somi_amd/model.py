@@ -16,7 +16,8 @@ channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.
 (from -1 only, arguments as written), `SimAMWithSlicing` and `SimAMWithFlexibleSlicing` rows (sized by their input; the channel count the row
 names must be the input's), `Conv_SWS` (a Conv behind sliding-window SimAM, width-scaled like Conv) and `PSSimAM` (arguments as written);
 and the ASF-YOLO neck: `Zoom_cat` (three inputs at strides 2 : 1 : 1/2, c2 = 3 * args[0]), `ScalSeq` (three inputs of args[0], 512 and 1024
-channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] channels), none of them width-scaled.
+channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] channels), none of them width-scaled; and the slim-neck
+pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repeated inside).
 """
 import math
 from copy import deepcopy
@@ -41,10 +42,13 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'ASPP': B.ASPP, 'C2f_DWR': B.C2f_DWR,                      # the dilated-conv context blocks, models/yolo.py:1472-1492
        'MultiSEAM': B.MultiSEAM,                                  # in SEAM's branch (models/yolo.py:1475), not repeated inside (:1487-1490)
        'C3CPCA': B.C3CPCA,                                        # models/yolo.py:1477, repeated inside (:1490)
-       'Conv_SWS': B.Conv_SWS}                                    # models/yolo.py:1472, not repeated inside
+       'Conv_SWS': B.Conv_SWS,                                    # models/yolo.py:1472, not repeated inside
+       # the slim-neck pair, models/yolo.py:1473-1474; VoVGSCSPCBAM repeated inside (:1489).  VoVGSCSP and GSBottleneck are in no list of the
+       # reference's parser: its generic branch would build them from the yaml arguments alone, without c1
+       'GSConv': B.GSConv, 'VoVGSCSPCBAM': B.VoVGSCSPCBAM}
 _SIMAM_SLICED = {'SimAMWithSlicing': B.SimAMWithSlicing, 'SimAMWithFlexibleSlicing': B.SimAMWithFlexibleSlicing}      # models/yolo.py:1504-1513
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA')
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution

@@ -1496,6 +1496,63 @@ def gconv2d_wgrad_nhwc(x, dy, *, c1, c2, groups, k, stride=1, x_coff=0, dy_coff=
     return out
 
 
+# ---------------------------------------------------------------------------------------------- slim-neck GSConv (gsconv.hip)
+# ch is the half width c2 // 2 of a GSConv: x1 / x_2 / d1 / d2 are slices of ch channels, the shuffled output and its gradient of 2 * ch.
+_NO_SLICE = _lib.Slice(None, 0, 0)
+
+
+def gs_tiles_per_workgroup(npix, ch):
+    """Pixel tiles a workgroup of gs_shuffle_affine_act / gs_unshuffle walks at this size (host arithmetic; 0 for a size they refuse)."""
+    return _lib.lib().somi_gs_tiles_per_workgroup(int(npix), int(ch))
+
+
+def _gs_map(t, shape, what):
+    if t.dim() != 4 or tuple(t.shape[:3]) != tuple(shape):
+        raise RuntimeError(f'{what} must be ({shape[0]}, {shape[1]}, {shape[2]}, .), got {tuple(t.shape)}')
+
+
+def gs_tail(x1, w1, b1, w2, b2, ch, act='silu', x_coff=0, *, out=None, o_coff=0, residual=None, res_coff=0):
+    """Inference tail of a GSConv behind its first conv: x_2 = act(dw2(act(dw1(x1) + b1)) + b2) with the intermediate zero outside the image,
+    and out's slice [o_coff, o_coff + 2 ch) = shuffle(x1, x_2) (+ residual's slice).  w1 / w2: pack_gconv_weight's [9][1][w_cs] with the
+    BatchNorm folded, b1 / b2 the folded biases (at least ch floats).  out must not be x1."""
+    B, H, W, _ = x1.shape
+    if out is None:
+        out = torch.empty(B, H, W, 2 * ch, device=x1.device, dtype=torch.float32)
+    _gs_map(out, (B, H, W), 'gs_tail: output')
+    if residual is not None:
+        _gs_map(residual, (B, H, W), 'gs_tail: residual')
+    if w1.shape != w2.shape or w1.numel() != 9 * w1.shape[-1] or min(b1.numel(), b2.numel()) < ch:
+        raise RuntimeError(f'gs_tail: weights must be two [9][1][w_cs] packs and the biases {ch} floats')
+    check(_lib.lib().somi_gs_tail_nhwc_f32(_slice(x1, x_coff), _ptr(_f32c(w1)), _ptr(_f32c(b1)), _ptr(_f32c(w2)), _ptr(_f32c(b2)), w1.shape[-1],
+                                           ACT[act], _slice(out, o_coff), _NO_SLICE if residual is None else _slice(residual, res_coff),
+                                           B, H, W, ch, _stream()), 'gs_tail')
+    return out
+
+
+def gs_shuffle_affine_act(z1, y2, ch, scale=None, shift=None, act='none', z_coff=0, y_coff=0, *, out=None, o_coff=0, residual=None, res_coff=0):
+    """Training forward: out's slice = shuffle(z1, act(y2 * scale + shift)) (+ residual's slice); scale = shift = None is the identity."""
+    if out is None:
+        out = torch.empty(*z1.shape[:3], 2 * ch, device=z1.device, dtype=torch.float32)
+    for t, what in ((y2, 'y2'), (out, 'output')) + (() if residual is None else ((residual, 'residual'),)):
+        _gs_map(t, z1.shape[:3], f'gs_shuffle_affine_act: {what}')
+    if (scale is None) != (shift is None) or (scale is not None and min(scale.numel(), shift.numel()) < ch):
+        raise RuntimeError(f'gs_shuffle_affine_act: scale and shift come together, {ch} floats each')
+    check(_lib.lib().somi_gs_shuffle_affine_act_nhwc_f32(_slice(z1, z_coff), _slice(y2, y_coff), _ptr(scale), _ptr(shift), ACT[act],
+                                                         _slice(out, o_coff), _NO_SLICE if residual is None else _slice(residual, res_coff),
+                                                         _npix(z1), ch, _stream()), 'gs_shuffle_affine_act')
+    return out
+
+
+def gs_unshuffle(dout, ch, do_coff=0, *, d1=None, d2=None, d1_coff=0, d2_coff=0):
+    """Training backward: the gradient of the shuffled output's slice [do_coff, do_coff + 2 ch) -> (d1, d2), the gradients of x1 and x_2."""
+    d1, d2 = (torch.empty(*dout.shape[:3], ch, device=dout.device, dtype=torch.float32) if d is None else d for d in (d1, d2))
+    for t, what in ((d1, 'd1'), (d2, 'd2')):
+        _gs_map(t, dout.shape[:3], f'gs_unshuffle: {what}')
+    check(_lib.lib().somi_gs_unshuffle_nhwc_f32(_slice(dout, do_coff), _slice(d1, d1_coff), _slice(d2, d2_coff), _npix(dout), ch, _stream()),
+          'gs_unshuffle')
+    return d1, d2
+
+
 # ---------------------------------------------------------------------------------------------- PSA attention
 # fp32 always, key_dim 32 / head_dim 64 (attention.hip).
 def psa_attention(qkv, heads, *, qkv_coff=0, out=None, o_coff=0, lse=False, v_out=False):

@@ -78,10 +78,13 @@ class FusedAdamEMA:
             raise RuntimeError('FusedAdamEMA runs on the MI355X only (no CPU fallback)')
         self.model = model
         g0, g1, g2 = reference_param_groups(model)
+        # children a block builds and never calls (VoVGSCSP.res, never_runs): autograd leaves their parameters without a gradient, so the
+        # reference's optimizer skips them, weight decay included.  They stay out of the flat buffers like the ungrouped ones below
+        idle = {id(p) for m in model.modules() for name in getattr(m, 'never_runs', ()) for p in getattr(m, name).parameters()}
         seen = set()
         groups = []
         for plist, wd in ((g0, 0.0), (g1, weight_decay), (g2, 0.0)):
-            plist = [p for p in plist if id(p) not in seen and not seen.add(id(p))]
+            plist = [p for p in plist if id(p) not in idle and id(p) not in seen and not seen.add(id(p))]
             groups.append((plist, wd))
         # a Parameter that is neither a `.weight` nor a `.bias` (WindowAttention.relative_position_bias_table) is in no group of the reference's
         # either (train.py:125-133): its gradient is computed, no step moves it, it stays outside the flat buffers and the EMA shadow equals it
