@@ -814,13 +814,15 @@ __global__ __launch_bounds__(MAX_DET_CAP) void nms_merge_compact_kernel(const Nm
     if (tid == MAX_DET_CAP - 1) a.count[b] = pos + f;
 }
 
-// boxes + scores form: key = descending-order image of the score bits (any sign), val = index
+// boxes + scores form: key = descending-order image of the score bits (any sign), val = index.  -0.0 takes the key of +0.0: the
+// reference's sort compares them equal and leaves them in index order
 __global__ void nms_boxes_prep_kernel(const NmsArgs a, uint32_t *sortV, int identity) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) a.total[0] = a.n;
     if (i >= a.n) return;
     if (identity) { sortV[i] = (uint32_t)i; return; }
-    const uint32_t u = __float_as_uint(a.scores[i]);
+    uint32_t u = __float_as_uint(a.scores[i]);
+    if (u == 0x80000000u) u = 0u;
     a.keyA[i] = ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
     a.valA[i] = (uint32_t)i;
 }
