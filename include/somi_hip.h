@@ -898,6 +898,40 @@ int somi_gconv2d_wgrad_nhwc_f32(const float *x, int x_cs, int x_coff, int B, int
                                 size_t workspace_floats, somi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Large-kernel depthwise convolution (ConvNextBlock's 7x7, models/common.py:6755; ConvMix's 9x9, :7153; dwlk.hip).  NHWC fp32, C channels
+ * (any multiple of 4) in and out, k in {7, 9}, stride 1, pad k/2, dilation 1.  Weights are tap-major [k*k][w_cs] (pack_gconv_weight's layout
+ * at cin_g = 1; w_cs % 4 == 0, w_cs >= C).  Slices are taken by value (somi_slice) and follow the slice rule above, every slice C wide; an
+ * optional slice is absent when its p is NULL.  A lane owns a channel quad of a
+ * strip of somi_dwlk_strip_length() adjacent outputs of one image row and holds one row of k taps at a time; a workgroup walks
+ * somi_dwlk_strips_per_workgroup(B, H, W, C, wgrad) rows of strips (host arithmetic; wgrad != 0: the weight gradient's plan; 0 for sizes the
+ * family refuses).  Deterministic: fixed-order reductions, no float atomics.  fp32 only.  Refused before any launch: SOMI_ENOTIMPL for another
+ * k, C % 4 != 0, an activation other than none / gelu, a tensor of more than 2^30 floats (B * H * W * its channel stride); SOMI_EINVAL for
+ * null or misaligned pointers and slices that break the slice rule; SOMI_EWORKSPACE for a short workspace.
+ *
+ * Forward: y = post_scale * act(conv + bias) + post_shift [+ residual], act in {SOMI_ACT_NONE, SOMI_ACT_GELU}; bias, post_scale, post_shift
+ * (C floats each, 16-byte aligned) and residual are optional, each on its own.  y must not overlap x.
+ * stat_sum / stat_sumsq (optional, [somi_dwlk_stat_rows][C] each): per-channel partial sums of (act(conv + bias) - stat_pivot) and its
+ * square - what a BatchNorm behind the activation normalises -, in the format somi_bn_stats_partials_f32 reads.  When statistics are asked for,
+ * the tensor WRITTEN is the pre-activation conv + bias: the GELU backward needs it, and the BatchNorm pass applies the activation.
+ * post_scale, post_shift and residual must then be NULL. */
+int somi_dwlk_strip_length(void);
+int somi_dwlk_strips_per_workgroup(int B, int H, int W, int C, int wgrad);
+int somi_dwlk_stat_rows(int B, int H, int W, int C);
+int somi_dwlk_nhwc_f32(somi_slice x, const float *w, int w_cs, const float *bias, int k, int act, const float *post_scale, const float *post_shift,
+                       somi_slice y, somi_slice residual, int B, int H, int W, int C, float *stat_sum, float *stat_sumsq, const float *stat_pivot,
+                       somi_stream_t stream);
+/* Data gradient: dx = conv^T(dy) [+ acc1] [+ acc2], the forward's stencil with the taps mirrored; acc1 may be dx itself (accumulate in
+ * place).  w is the forward packing. */
+int somi_dwlk_dgrad_nhwc_f32(somi_slice dy, const float *w, int w_cs, int k, somi_slice dx, somi_slice acc1, somi_slice acc2, int B, int H, int W,
+                             int C, somi_stream_t stream);
+/* Weight and bias gradient from one pass over x and dy: dw (C, 1, k, k) - the nn.Conv2d layout - and db (C; NULL: not wanted) = the
+ * per-channel sum of dy, both written, or added to when accumulate != 0.  A lane keeps k accumulators, one tap row at a time; one partial row
+ * per workgroup goes to the workspace (somi_dwlk_wgrad_workspace_floats, 16-byte aligned) and a second kernel adds the rows in a fixed order. */
+size_t somi_dwlk_wgrad_workspace_floats(int B, int H, int W, int C, int k);
+int somi_dwlk_wgrad_nhwc_f32(somi_slice x, somi_slice dy, int B, int H, int W, int C, int k, float *dw, float *db, int accumulate, float *workspace,
+                             size_t workspace_floats, somi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * PSA multi-head spatial self-attention (AttentionPSA, models/common.py:7203-7230; yolov10.yaml).  NHWC fp32, key_dim 32 and head_dim
  * 64 fixed (scale 32^-0.5).  q, k and v are read in place from the qkv Conv's output: per pixel (row stride qkv_cs), head h's channels
  * qkv_coff + h*128 + [0,32) are q, + [32,64) k and + [64,128) v.  N = H*W tokens per image, any N >= 1.  Slices of heads*128 (qkv, dqkv)

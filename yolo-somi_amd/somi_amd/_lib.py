@@ -232,6 +232,13 @@ SIGNATURES = {
     'somi_gconv2d_dgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, P, I, I, I, I, I, I, P, I, I, P, I, I, S]),
     'somi_gconv2d_wgrad_workspace_floats': (Z, [I, I, I, I, I, I]),
     'somi_gconv2d_wgrad_nhwc_f32': (I, [P, I, I, I, I, I, I, P, I, I, I, I, I, I, I, I, P, I, P, Z, S]),
+    'somi_dwlk_strip_length': (I, []),
+    'somi_dwlk_strips_per_workgroup': (I, [I, I, I, I, I]),
+    'somi_dwlk_stat_rows': (I, [I, I, I, I]),
+    'somi_dwlk_nhwc_f32': (I, [Slice, P, I, P, I, I, P, P, Slice, Slice, I, I, I, I, P, P, P, S]),
+    'somi_dwlk_dgrad_nhwc_f32': (I, [Slice, P, I, I, Slice, Slice, Slice, I, I, I, I, S]),
+    'somi_dwlk_wgrad_workspace_floats': (Z, [I, I, I, I, I]),
+    'somi_dwlk_wgrad_nhwc_f32': (I, [Slice, Slice, I, I, I, I, I, P, P, I, P, Z, S]),
     'somi_psa_attention_f32': (I, [P, I, I, I, I, I, P, I, I, P, P, S]),
     'somi_psa_attention_backward_f32': (I, [P, I, I, P, I, I, P, I, I, P, I, I, I, P, I, I, P, P, S]),
     'somi_swin_attention_lse_floats': (Z, [I, I, I, I]),

@@ -2454,6 +2454,283 @@ class C3STR(C3):
         return dx
 
 
+# ------------------------------------------------------------------------------------------------ ConvNeXt / ConvMixer blocks (dwlk.hip)
+def _whole4(a, c, what):
+    """The tensor of an Act that is a whole (B,H,W,c) tensor with c % 4 == 0 - what the large-kernel depthwise blocks read."""
+    if a.coff != 0 or a.c != c or a.t.shape[3] != c or c % 4:
+        raise NotImplementedError(f'{what} takes a whole (B,H,W,{c}) tensor with c % 4 == 0, got channels [{a.coff}, {a.coff + a.c}) of '
+                                  f'{a.t.shape[3]}')
+    return a.t
+
+
+def _out_slice(out, like, c):
+    """(tensor, channel offset) a block writes: the given Act, else a new (B,H,W,c) tensor."""
+    return (torch.empty(*like.shape[:3], c, device=like.device, dtype=torch.float32), 0) if out is None else (out.t, out.coff)
+
+
+class LayerNorm_s(nn.Module):
+    """LayerNorm over the channels of an NHWC map with a free eps (models/common.py:6728-6748), channels_last form only - the form
+    ConvNextBlock uses; channels_first is refused.  On a whole (B,H,W,C) tensor."""
+
+    def __init__(self, normalized_shape, eps=1e-6, data_format='channels_last'):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(normalized_shape))
+        self.bias = nn.Parameter(torch.zeros(normalized_shape))
+        self.eps = eps
+        self.data_format = data_format
+        if data_format == 'channels_first':
+            raise NotImplementedError('LayerNorm_s(data_format="channels_first") is not on the path (nothing here uses it): channels_last only')
+        if data_format != 'channels_last':
+            raise NotImplementedError
+        self.normalized_shape = (normalized_shape,)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x):
+        c = self.normalized_shape[0]
+        xt = _whole(x, c, 'LayerNorm_s')
+        w, b = _f32dev(self.weight, xt.device), _f32dev(self.bias, xt.device)
+        if self.training:
+            self.__dict__['_ctx'] = (xt, w)
+        return Act(ops.layernorm_act(xt, w, b, self.eps), 0, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        if dx_out is not None or accumulate:
+            raise NotImplementedError('LayerNorm_s writes its own input gradient')
+        xt, w = self.__dict__.pop('_ctx')
+        c = xt.shape[3]
+        (gw, gb), fin = _grad_targets(self.weight, self.bias)
+        dx = ops.layernorm_backward(xt, w, self.eps, _whole(dout, c, 'LayerNorm_s.backward'), gw, gb)
+        fin()
+        return Act(dx, 0, c) if need_dx else None
+
+
+class ConvNextBlock(_Packed):
+    """x + gamma * pwconv2(GELU(pwconv1(LayerNorm(dwconv7x7(x))))) (models/common.py:6751-6777), on the NHWC map the reference permutes to.
+    The 7x7 depthwise conv is ops.dwlk; the Linear layers are 1x1 convolutions as in Mlp.  Eval: four launches - GELU rides pwconv1's
+    epilogue, gamma and the shortcut pwconv2's (post_scale / residual).  Training keeps pwconv1's output for the GELU backward and pwconv2's
+    for dgamma, and scales + adds in a pass of its own; backward: one reduce + apply pair gives dgamma (a per-channel sum of dout * pwconv2's
+    output) and gamma * dout, the shortcut's gradient rides the depthwise data-gradient pass.  gamma is a bare Parameter: like the reference's,
+    it is in none of the optimizer's groups (train.py:125-133) - it takes a gradient and no step moves it."""
+
+    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6):
+        super().__init__()
+        if drop_path > 0.:
+            raise NotImplementedError(f'ConvNextBlock(drop_path={drop_path}): stochastic depth is not on the path (drop_path = 0 only)')
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = LayerNorm_s(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones((dim)), requires_grad=True) if layer_scale_init_value > 0 else None
+        self.drop_path = nn.Identity()
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack(self, dev):
+        c = self.dwconv.in_channels
+        pk = dict(dw=pack_gconv_weight(self.dwconv.weight.detach().float()).to(dev), db=_f32dev(self.dwconv.bias, dev),
+                  lw=_f32dev(self.norm.weight, dev), lb=_f32dev(self.norm.bias, dev), w1=_f32dev(self.pwconv1.weight, dev),
+                  b1=_f32dev(self.pwconv1.bias, dev), w2=_f32dev(self.pwconv2.weight, dev), b2=_f32dev(self.pwconv2.bias, dev),
+                  gamma=None if self.gamma is None else _f32dev(self.gamma, dev), zero_c=torch.zeros(c, device=dev))
+        if self.training:
+            pk.update(w1_t=_f32dev(self.pwconv1.weight.t(), dev), w2_t=_f32dev(self.pwconv2.weight.t(), dev), one=torch.ones(4 * c, device=dev),
+                      zero=torch.zeros(4 * c, device=dev), one_c=torch.ones(c, device=dev))
+        return pk
+
+    def forward(self, x, out=None):
+        """out: the Act (channel slice) the block writes (CNeB: the first half of cv3's input)."""
+        c = self.dwconv.in_channels
+        xt = _whole4(x, c, 'ConvNextBlock')
+        pk = self._packed(xt.device)
+        yt, y_coff = _out_slice(out, xt, c)
+        u = ops.dwlk(xt, pk['dw'], pk['db'], c=c, k=7)
+        n = ops.layernorm_act(u, pk['lw'], pk['lb'], self.norm.eps)
+        if not self.training:
+            g = ops.conv2d_nhwc(n, pk['w1'], pk['b1'], kh=1, kw=1, act='gelu')
+            ops.conv2d_nhwc(g, pk['w2'], pk['b2'], kh=1, kw=1, post_scale=pk['gamma'], post_shift=None if pk['gamma'] is None else pk['zero_c'],
+                            residual=xt, out=yt, cout=c, y_coff=y_coff)
+            return Act(yt, y_coff, c)
+        h = ops.conv2d_nhwc(n, pk['w1'], pk['b1'], kh=1, kw=1)
+        g = ops.chan_affine_act(h, 4 * c, 0, pk['one'], pk['zero'], 'gelu', 0, torch.empty_like(h))
+        if pk['gamma'] is None:
+            v = None
+            ops.conv2d_nhwc(g, pk['w2'], pk['b2'], kh=1, kw=1, residual=xt, out=yt, cout=c, y_coff=y_coff)
+        else:
+            v = ops.conv2d_nhwc(g, pk['w2'], pk['b2'], kh=1, kw=1)
+            ops.chan_affine_act(v, c, 0, pk['gamma'], pk['zero_c'], 'none', 0, yt, y_coff, residual=xt)
+        self.__dict__['_ctx'] = (xt, u, n, h, g, v, pk)
+        return Act(yt, y_coff, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        xt, u, n, h, g, v, pk = self.__dict__.pop('_ctx')
+        c = xt.shape[3]
+        if v is not None:
+            # the layer scale as a frozen per-channel affine map of v (mean 0, rstd 1, scale gamma): its backward's reduce half is
+            # dgamma = sum dout * v, its apply half dv = gamma * dout - which also makes a whole tensor of a channel slice
+            (gg,), fin = _grad_targets(self.gamma)
+            dv = ops.bn_act_backward(dout.t, dout.coff, v, 0, c, pk['zero_c'], pk['one_c'], pk['gamma'], pk['zero_c'], 'none', 0, False,
+                                     torch.empty_like(v), 0, gg, torch.zeros(c, device=v.device))
+            fin()
+        elif dout.coff != 0 or dout.t.shape[3] != c:
+            dv = torch.empty_like(xt)
+            ops.resample_slice(dout.t, dout.coff, dv, 0, c)
+        else:
+            dv = dout.t
+        dg = _linear_backward(self.pwconv2, g, dv, pk['w2_t'])
+        dn = _linear_backward(self.pwconv1, n, ops.gelu_backward_(h, dg), pk['w1_t'])
+        (gw, gb), fin = _grad_targets(self.norm.weight, self.norm.bias)
+        du = ops.layernorm_backward(u, pk['lw'], self.norm.eps, dn, gw, gb)
+        fin()
+        (gw, gb), fin = _grad_targets(self.dwconv.weight, self.dwconv.bias)
+        ops.dwlk_wgrad(xt, du, c=c, k=7, dw=gw, db=gb, accumulate=True)
+        fin()
+        if not need_dx:
+            return None
+        dxt, dx_coff = _out_slice(dx_out, xt, c)
+        ops.dwlk_dgrad(du, pk['dw'], c=c, k=7, out=dxt, dx_coff=dx_coff, accumulate=dout.t, acc_coff=dout.coff,      # + the shortcut's gradient
+                       accumulate2=dxt if accumulate else None, acc2_coff=dx_coff)
+        return Act(dxt, dx_coff, c)
+
+
+class _CSPLargeKernel(nn.Module):
+    """What CNeB and CSPCM share: cv3(cat(m(cv1(x)), cv2(x))), the block branch FIRST (models/common.py:6790-6791, 7179-7180), C3's layout:
+    the last block of m and cv2 write the two halves of cv3's input buffer."""
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _build(self, c1, c2, e, blocks):
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.cv3 = Conv(2 * c_, c2, 1)
+        self.m = nn.Sequential(*blocks(c_))
+
+    def forward(self, x):
+        c_ = self.cv1.conv.out_channels
+        if c_ % 4:
+            raise NotImplementedError(f'{type(self).__name__} hidden width {c_} must be a multiple of 4 on the MI355X path')
+        B, H, W, _ = x.shape
+        cat = concat_act(x.t, H, W, 2 * c_)
+        n = len(self.m)
+        t = self.cv1(x)
+        for i, blk in enumerate(self.m):
+            t = blk(t, out=cat.slice(0, c_) if i == n - 1 else None)
+        self.cv2(x, out=cat.slice(c_, c_))
+        return self.cv3(cat)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        c_ = self.cv1.conv.out_channels
+        dcat = self.cv3.backward(dout)
+        dx = self.cv2.backward(dcat.slice(c_, c_), dx_out=dx_out, accumulate=accumulate, need_dx=need_dx)
+        d = dcat.slice(0, c_)
+        for blk in reversed(self.m):
+            d = blk.backward(d)
+        self.cv1.backward(d, dx_out=dx, accumulate=True, need_dx=need_dx)
+        return dx
+
+
+class CNeB(_CSPLargeKernel):
+    """The ConvNeXt C3 (models/common.py:6780-6791): C3 whose bottlenecks are n ConvNextBlock(c_).  shortcut and g are ignored there too."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        self._build(c1, c2, e, lambda c_: (ConvNextBlock(c_) for _ in range(n)))
+
+
+def _act_bn_train(u, bn, act, yt, y_coff, residual=None, partials=None, vec=None):
+    """yt's slice at y_coff = BN_batch(act(u)) [+ residual], the activation IN FRONT of the norm; u a whole tensor.  partials: the sums of
+    act(u) the producing launch left (around vec['rm']); else the statistics pass reads u.  Under sync-BN, whose statistics entries take no
+    activation, act(u) is materialised first.  -> the saved statistics."""
+    c = u.shape[3]
+    if ops.SYNC_BN is None:
+        st, commit = _bn_train(bn, c, None if partials is not None else u, act=act, partials=partials, npix=ops._npix(u), vec=vec)
+        ops.chan_affine_act(u, c, 0, st[2], st[3], act, 1, yt, y_coff, residual=residual)
+    else:
+        g = ops.chan_affine_act(u, c, 0, torch.ones(c, device=u.device), torch.zeros(c, device=u.device), act, 0, torch.empty_like(u))
+        st, commit = _bn_train(bn, c, g, vec=vec)
+        ops.chan_affine_act(g, c, 0, st[2], st[3], 'none', 0, yt, y_coff, residual=residual)
+    commit()
+    return st
+
+
+class ConvMix(_Packed):
+    """ConvMixer layer (models/common.py:7149-7166): x = x + BN(GELU(dwconv_k(x))), then BN(GELU(conv1x1(x))) - both BatchNorms BEHIND their
+    activation.  dim1 is ignored, as in the reference: the module returns dim channels.  k = 9 (the default) or 7, ops.dwlk.
+    Eval: two launches - the stencil with bias, GELU, the folded BatchNorm as post-affine and the residual; the 1x1 with bias, GELU and
+    post-affine.  Training: the stencil's epilogue leaves the BatchNorm's partial sums (of GELU(conv + bias)) and writes the pre-activation,
+    which the GELU backward needs; under sync-BN the activated tensor is materialised instead."""
+
+    def __init__(self, dim, dim1, kernel_size=9):
+        super().__init__()
+        if kernel_size not in (7, 9):
+            raise NotImplementedError(f'ConvMix(kernel_size={kernel_size}): the large-kernel depthwise kernels have k = 7 and k = 9 only')
+        self.Resnet = nn.Sequential(nn.Conv2d(dim, dim, kernel_size=kernel_size, groups=dim, padding='same'), nn.GELU(), nn.BatchNorm2d(dim))
+        self.Conv_1x1 = nn.Sequential(nn.Conv2d(dim, dim, kernel_size=1), nn.GELU(), nn.BatchNorm2d(dim))
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack(self, dev):
+        dwc, pwc = self.Resnet[0], self.Conv_1x1[0]
+        pk = dict(dw=pack_gconv_weight(dwc.weight.detach().float()).to(dev), db=_f32dev(dwc.bias, dev), pw=_f32dev(pwc.weight.flatten(1), dev),
+                  pb=_f32dev(pwc.bias, dev))
+        if self.training:
+            pk['pwt'] = pack_dgrad_weight(pwc.weight.detach().float()).to(dev)
+        else:
+            pk['bn1'] = tuple(_f32dev(t, dev) for t in bn_fold(self.Resnet[2]))
+            pk['bn2'] = tuple(_f32dev(t, dev) for t in bn_fold(self.Conv_1x1[2]))
+        return pk
+
+    def forward(self, x, out=None):
+        """out: the Act (channel slice) the block writes (CSPCM: the first half of cv3's input)."""
+        c, k = self.Resnet[0].in_channels, self.Resnet[0].kernel_size[0]
+        xt = _whole4(x, c, 'ConvMix')
+        pk = self._packed(xt.device)
+        yt, y_coff = _out_slice(out, xt, c)
+        if not self.training:
+            y1 = ops.dwlk(xt, pk['dw'], pk['db'], c=c, k=k, act='gelu', post_scale=pk['bn1'][0], post_shift=pk['bn1'][1], residual=xt)
+            ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1, act='gelu', post_scale=pk['bn2'][0], post_shift=pk['bn2'][1], out=yt, cout=c,
+                            y_coff=y_coff)
+            return Act(yt, y_coff, c)
+        bn1, bn2 = self.Resnet[2], self.Conv_1x1[2]
+        y1 = torch.empty_like(xt)
+        if ops.SYNC_BN is None:
+            vec = _bn_vectors(bn1, xt.device, c)
+            part = {'pivot': vec['rm']}
+            u1 = ops.dwlk(xt, pk['dw'], pk['db'], c=c, k=k, act='gelu', bn_stats=part)
+            s1 = _act_bn_train(u1, bn1, 'gelu', y1, 0, residual=xt, partials=part, vec=vec)
+        else:
+            u1 = ops.dwlk(xt, pk['dw'], pk['db'], c=c, k=k)
+            s1 = _act_bn_train(u1, bn1, 'gelu', y1, 0, residual=xt)
+        u2 = ops.conv2d_nhwc(y1, pk['pw'], pk['pb'], kh=1, kw=1)
+        s2 = _act_bn_train(u2, bn2, 'gelu', yt, y_coff)
+        self.__dict__['_ctx'] = (xt, u1, s1, y1, u2, s2, pk)
+        return Act(yt, y_coff, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        xt, u1, s1, y1, u2, s2, pk = self.__dict__.pop('_ctx')
+        c, k = xt.shape[3], self.Resnet[0].kernel_size[0]
+        du2 = _bn_backward(self.Conv_1x1[2], dout.t, dout.coff, u2, s2, 'gelu', torch.empty_like(u2), c, order=1)
+        dy1 = _plain_conv_backward(self.Conv_1x1[0], Act(y1), du2, pk['pwt'], direct=('bias',)).t
+        du1 = _bn_backward(self.Resnet[2], dy1, 0, u1, s1, 'gelu', torch.empty_like(u1), c, order=1)
+        (gw, gb), fin = _grad_targets(self.Resnet[0].weight, self.Resnet[0].bias)
+        ops.dwlk_wgrad(xt, du1, c=c, k=k, dw=gw, db=gb, accumulate=True)
+        fin()
+        if not need_dx:
+            return None
+        dxt, dx_coff = _out_slice(dx_out, xt, c)
+        ops.dwlk_dgrad(du1, pk['dw'], c=c, k=k, out=dxt, dx_coff=dx_coff, accumulate=dy1,                           # + the residual branch
+                       accumulate2=dxt if accumulate else None, acc2_coff=dx_coff)
+        return Act(dxt, dx_coff, c)
+
+
+class CSPCM(_CSPLargeKernel):
+    """The ConvMixer C3 (models/common.py:7169-7180): n ConvMix(c_, c_) (k = 9) between cv1 and the concatenation, the block branch first."""
+
+    def __init__(self, c1, c2, n=1, e=0.5):
+        super().__init__()
+        self._build(c1, c2, e, lambda c_: (ConvMix(c_, c_) for _ in range(n)))
+
+
 class _CoordGates(_Packed):
     """The coordinate attention both CoorAttention and CABottleneck carry (models/common.py:1425-1450, 4902-4922), on the children `conv1`, `bn1`,
     `conv_h`, `conv_w` of the class that mixes this in:  out = [res +] x1 * a_h[b,h,c] * a_w[b,w,c]  with

@@ -188,6 +188,24 @@ def yolov5_slimneck_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     return cfg
 
 
+CONVNEXT_WHERE = {'cneb': 'CNeB', 'cspcm': 'CSPCM'}
+
+
+def yolov5_convnext_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='cneb'):
+    """yolov5s 6.0 whose four backbone C3 rows are the large-kernel depthwise blocks: where='cneb' the ConvNeXt C3 (CNeB, models/common.py:6780-6791,
+    a 7x7 depthwise conv per block), where='cspcm' the ConvMixer C3 (CSPCM, :7169-7180, 9x9).  The reference registers both in its parser
+    (models/yolo.py:1523-1535) but ships no yaml that names them.  The rows keep their arguments and n: CNeB repeats its blocks inside; the
+    parser does not insert n for CSPCM, so n > 1 there is n whole modules in a row - legal here, where every swapped row has c1 == c2.  The
+    head and Detect are yolov5_cfg's."""
+    if where not in CONVNEXT_WHERE:
+        raise ValueError(f'where must be one of {tuple(CONVNEXT_WHERE)}, got {where!r}')
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    for row in cfg['backbone']:
+        if row[2] == 'C3':
+            row[2] = CONVNEXT_WHERE[where]
+    return cfg
+
+
 def yolov5_swin_cfg(width=0.50, depth=0.33, nc=80, anchors=None):
     """The layer table of models/hub/yolov5s-transformer.yaml (yolov5s with the Focus stem and SPP(5,9,13), a transformer C3 as the last
     backbone row) with C3STR - the Swin variant, models/common.py:1632-1637 - where that file has C3TR (row 9).  The reference registers C3STR

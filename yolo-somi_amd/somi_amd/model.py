@@ -17,7 +17,9 @@ channels passing through (CPCA, CPCABottleneck, CPCA_ChannelAttention in blocks.
 names must be the input's), `Conv_SWS` (a Conv behind sliding-window SimAM, width-scaled like Conv) and `PSSimAM` (arguments as written);
 and the ASF-YOLO neck: `Zoom_cat` (three inputs at strides 2 : 1 : 1/2, c2 = 3 * args[0]), `ScalSeq` (three inputs of args[0], 512 and 1024
 channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] channels), none of them width-scaled; and the slim-neck
-pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repeated inside).
+pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repeated inside); and the large-kernel depthwise blocks `CNeB`
+(repeated inside), `ConvMix` and `CSPCM` (n > 1 a Repeat of whole modules; a `ConvMix` row must name the channels behind it, which it passes
+through).
 """
 import math
 from copy import deepcopy
@@ -45,10 +47,13 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'Conv_SWS': B.Conv_SWS,                                    # models/yolo.py:1472, not repeated inside
        # the slim-neck pair, models/yolo.py:1473-1474; VoVGSCSPCBAM repeated inside (:1489).  VoVGSCSP and GSBottleneck are in no list of the
        # reference's parser: its generic branch would build them from the yaml arguments alone, without c1
-       'GSConv': B.GSConv, 'VoVGSCSPCBAM': B.VoVGSCSPCBAM}
+       'GSConv': B.GSConv, 'VoVGSCSPCBAM': B.VoVGSCSPCBAM,
+       # the ConvNeXt / ConvMixer blocks: CNeB has a branch of its own that repeats inside (models/yolo.py:1523-1530); ConvMix and CSPCM share
+       # one that does not (:1531-1535), so n > 1 is an nn.Sequential of n whole modules
+       'CNeB': B.CNeB, 'ConvMix': B.ConvMix, 'CSPCM': B.CSPCM}
 _SIMAM_SLICED = {'SimAMWithSlicing': B.SimAMWithSlicing, 'SimAMWithFlexibleSlicing': B.SimAMWithFlexibleSlicing}      # models/yolo.py:1504-1513
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM')
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM', 'CNeB')
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
@@ -74,6 +79,12 @@ def parse_model(d, ch):
             if name in _REPEAT_INSIDE:
                 args.insert(2, n)
                 n = 1
+            elif name == 'ConvMix' and c2 != c1:                  # the module ignores dim1 and returns its input's width
+                raise ValueError(f"a 'ConvMix' row that names {c2} channels (scaled) behind {c1}: the module passes its input's width through, "
+                                 f'and the reference would size the following rows by {c2}')
+            elif name == 'CSPCM' and n > 1 and c1 != c2:
+                raise NotImplementedError(f'{n} repeats of CSPCM from {c1} to {c2} channels: the reference repeats the whole block with the same '
+                                          f'(c1, c2) (models/yolo.py:1531-1535, 1650), so its second block gets {c2} channels where it expects {c1}')
             elif name == 'C3_CA' and n > 1 and c1 != c2:
                 raise NotImplementedError(f'{n} repeats of C3_CA from {c1} to {c2} channels: the reference repeats the whole block with the same '
                                           f'(c1, c2) (models/yolo.py:1487-1490, 1650), so its second block gets {c2} channels where it expects {c1}')

@@ -359,6 +359,9 @@ def _slice(t, coff):
     return _lib.Slice(_ptr(_f32c(t)), t.shape[3], coff)
 
 
+_NO_SLICE = _lib.Slice(None, 0, 0)                              # an optional slice that is absent
+
+
 def maxpool3s2_out_size(size):
     """Output size of F.max_pool2d(., 3, stride=2, padding=1), floor mode."""
     return (size - 1) // 2 + 1
@@ -1496,11 +1499,95 @@ def gconv2d_wgrad_nhwc(x, dy, *, c1, c2, groups, k, stride=1, x_coff=0, dy_coff=
     return out
 
 
+# ---------------------------------------------------------------------------------------------- large-kernel depthwise conv (dwlk.hip)
+# k = 7 or 9, stride 1, pad k // 2, c % 4 == 0; w packed [k*k][1][w_cs] (pack.pack_gconv_weight).  fp32 always.
+def dwlk_strip_length():
+    """Adjacent outputs of one image row a lane of the dwlk kernels owns."""
+    return _lib.lib().somi_dwlk_strip_length()
+
+
+def dwlk_strips_per_workgroup(B, H, W, c, wgrad=False):
+    """Rows of strips a workgroup of dwlk / dwlk_dgrad (wgrad: of dwlk_wgrad) walks at this size (host arithmetic; 0 for a size they refuse)."""
+    return _lib.lib().somi_dwlk_strips_per_workgroup(int(B), int(H), int(W), int(c), int(bool(wgrad)))
+
+
+def _dwlk_maps(B, H, W, what, *tensors):
+    for t in tensors:
+        if t is not None and (t.dim() != 4 or tuple(t.shape[:3]) != (B, H, W)):
+            raise RuntimeError(f'{what}: every map must be ({B}, {H}, {W}, .), got {tuple(t.shape)}')
+
+
+def _dwlk_work(name, B, H, W, c, k, passes):
+    """-> _timed's info: (kernel name, algorithmic FLOPs, shape key)."""
+    return lambda: (f'{name}_k{k}', 2.0 * B * H * W * c * k * k, (B, H, W, c, c, k, 1, passes))
+
+
+def dwlk(x, w, bias=None, *, c, k, x_coff=0, act='none', post_scale=None, post_shift=None, out=None, o_coff=0, residual=None, res_coff=0,
+         bn_stats=None):
+    """out's slice [o_coff, o_coff + c) = post_scale * act(dwconv_k(x's slice) + bias) + post_shift (+ residual's slice); act 'none' or
+    'gelu'.  bn_stats: dict filled in place with the partial channel sums of act(conv + bias) around bn_stats['pivot'] ('part' (2, rows, c),
+    'rows'), for bn_stats_from_partials; the tensor written is then the PRE-activation conv + bias, and post_scale / post_shift / residual
+    must be None."""
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    _dwlk_maps(B, H, W, 'dwlk', out, residual)
+    if w.numel() != k * k * w.shape[-1]:
+        raise RuntimeError(f'dwlk: the weight must be a [{k * k}][1][w_cs] pack, got {tuple(w.shape)}')
+    for v, what in ((bias, 'bias'), (post_scale, 'post_scale'), (post_shift, 'post_shift')):
+        if v is not None and (v.numel() < c or v.dtype != torch.float32 or not v.is_contiguous()):
+            raise RuntimeError(f'dwlk: {what} must be at least {c} contiguous floats')
+    L = _lib.lib()
+    ss = sq = piv = None
+    if bn_stats is not None:
+        rows = L.somi_dwlk_stat_rows(B, H, W, c)
+        part = torch.empty(2, max(rows, 1), c, device=x.device, dtype=torch.float32)
+        ss, sq, piv = part[0].data_ptr(), part[1].data_ptr(), _ptr(bn_stats.get('pivot'))
+        bn_stats['part'], bn_stats['rows'] = part, rows
+    with _timed(_dwlk_work('dwlk_fwd', B, H, W, c, k, 1)):
+        check(L.somi_dwlk_nhwc_f32(_slice(x, x_coff), _ptr(_f32c(w, 'weight')), w.shape[-1], _ptr(bias), k, ACT[act], _ptr(post_scale), _ptr(post_shift),
+                                   _slice(out, o_coff), _NO_SLICE if residual is None else _slice(residual, res_coff), B, H, W, c, ss, sq, piv,
+                                   _stream()), 'dwlk')
+    return out
+
+
+def dwlk_dgrad(dy, w, *, c, k, dy_coff=0, out=None, dx_coff=0, accumulate=None, acc_coff=0, accumulate2=None, acc2_coff=0):
+    """Data gradient of dwlk into out's slice [dx_coff, dx_coff + c) (+ accumulate's and accumulate2's slices; accumulate may be out)."""
+    B, H, W, _ = dy.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=dy.device, dtype=torch.float32)
+    a1, a2 = accumulate, accumulate2
+    _dwlk_maps(B, H, W, 'dwlk_dgrad', out, a1, a2)
+    with _timed(_dwlk_work('dwlk_dgrad', B, H, W, c, k, 2)):
+        check(_lib.lib().somi_dwlk_dgrad_nhwc_f32(_slice(dy, dy_coff), _ptr(_f32c(w, 'weight')), w.shape[-1], k, _slice(out, dx_coff),
+                                                  _NO_SLICE if a1 is None else _slice(a1, acc_coff), _NO_SLICE if a2 is None else _slice(a2, acc2_coff),
+                                                  B, H, W, c, _stream()), 'dwlk_dgrad')
+    return out
+
+
+def dwlk_wgrad(x, dy, *, c, k, x_coff=0, dy_coff=0, dw=None, db=None, accumulate=False, bias=True):
+    """-> (dw (c, 1, k, k), db (c)): weight and bias gradients of dwlk from one pass, written into dw / db (or added to them when accumulate).
+    bias=False and db None: no bias gradient (db comes back None)."""
+    B, H, W, _ = x.shape
+    _dwlk_maps(B, H, W, 'dwlk_wgrad', dy)
+    if dw is None:
+        dw = (torch.zeros if accumulate else torch.empty)(c, 1, k, k, device=x.device, dtype=torch.float32)
+    if db is None and bias:
+        db = (torch.zeros if accumulate else torch.empty)(c, device=x.device, dtype=torch.float32)
+    if dw.numel() != c * k * k or (db is not None and db.numel() != c):
+        raise RuntimeError(f'dwlk_wgrad: dw must hold {c * k * k} floats and db {c}')
+    L = _lib.lib()
+    n = L.somi_dwlk_wgrad_workspace_floats(B, H, W, c, k)
+    ws = torch.empty(max(n, 4), device=x.device, dtype=torch.float32)
+    with _timed(_dwlk_work('dwlk_wgrad', B, H, W, c, k, 3)):
+        check(L.somi_dwlk_wgrad_nhwc_f32(_slice(x, x_coff), _slice(dy, dy_coff), B, H, W, c, k, _ptr(_f32c(dw, 'weight gradient')),
+                                         _ptr(None if db is None else _f32c(db, 'bias gradient')), int(accumulate), _ptr(ws), ws.numel(), _stream()),
+              'dwlk_wgrad')
+    return dw, db
+
+
 # ---------------------------------------------------------------------------------------------- slim-neck GSConv (gsconv.hip)
 # ch is the half width c2 // 2 of a GSConv: x1 / x_2 / d1 / d2 are slices of ch channels, the shuffled output and its gradient of 2 * ch.
-_NO_SLICE = _lib.Slice(None, 0, 0)
-
-
 def gs_tiles_per_workgroup(npix, ch):
     """Pixel tiles a workgroup of gs_shuffle_affine_act / gs_unshuffle walks at this size (host arithmetic; 0 for a size they refuse)."""
     return _lib.lib().somi_gs_tiles_per_workgroup(int(npix), int(ch))
