@@ -58,7 +58,7 @@ enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_AC
                                        coordinate attention: taken wherever SOMI_ACT_LEAKY is */ };
 
 /* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
- * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_simam_desc, the asf.hip descriptors).  An input slice is only read. */
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_ema_desc, somi_simam_desc, the asf.hip descriptors).  An input slice is only read. */
 typedef struct somi_slice {
     float *p;
     int32_t cs, coff;
@@ -404,6 +404,55 @@ int somi_coordatt_means_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stre
 int somi_coordatt_apply_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
 int somi_coordatt_bwd_gates_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
 int somi_coordatt_bwd_input_nhwc_f32(const somi_coordatt_desc *d, somi_stream_t stream);
+
+/* Efficient multi-scale attention (EMA, models/common.py:5263-5292; ema.hip): the passes over the map x (B,H,W,.) that are EMA's own.  With
+ * g = factor, cg = C / g, channel c = gi * cg + j and N = H * W: the means pass is somi_coordatt_means_nhwc_f32, conv1x1 (cg -> cg, shared by
+ * the groups, with bias and a sigmoid epilogue) runs on the conv entry over the (B, H + W, g, cg) view and leaves sg = sigmoid(hw)
+ * (B, H + W, .) in pool's layout, conv3x3 (cg -> cg, shared) leaves x2 (B,H,W,.).  Every slice is C wide.  gamma, beta: gn's affine, cg floats.
+ * stats    (somi_ema_stats_nhwc_f32):    reads x, sg and x2 (optional) once.  stats (B, 3, C): the mean of t = x * sg_h * sg_w per (b, c), its sum
+ *          of squared deviations (around a pivot, t at pixel (0, 0); never sum t^2 - (sum t)^2 / N) and the mean of x2.  vec (B, 4, C): mean,
+ *          rstd = 1 / sqrt(M2 / N + eps), x21 = softmax over the group of the x2 means, x11 = softmax over cg of beta (the mean of the normalised
+ *          map is its shift); both softmaxes subtract the maximum.
+ * gate     (somi_ema_gate_nhwc_f32):     y = [res +] x * sigmoid(wgt), wgt[b,gi,h,w] = sum_j x11[j] x2[..j] + x21[b,gi,j] x1[..j],
+ *          x1 = gamma * (t - mean) * rstd + beta rebuilt in registers.  x1, the expanded gates and wgt never reach memory.
+ * bwd gate (somi_ema_bwd_gate_nhwc_f32): y holds dout (read).  dx = dout * sigmoid(wgt), written or added with `accumulate`; dw = dwgt =
+ *          s (1 - s) sum_j dout x, the same value over the cg channels of a group; sums (B, 3, C) = sum dwgt * that, sum dwgt, sum dwgt * x2 per
+ *          (b, c) (that = (t - mean) * rstd); bvec (B, 3, C): what the next pass needs per (b, c); dgamma, dbeta (cg floats) ADDED to, (b, gi) in order.
+ * bwd norm (somi_ema_bwd_norm_nhwc_f32): reads x, sg, dw.  y = dt, the gradient of t (the instance-norm backward), written; dw becomes
+ *          dx2 = dwgt * x11 + the softmax term / N in place; dsg (B, H + W, .) = the gradient of hw (in front of the sigmoid): the row and
+ *          column sums of dt * t, times 1 - sg.  The input gradient is then finished by the conv backward of conv3x3 (accumulating into dx),
+ *          of conv1x1 and by somi_coordatt_bwd_input_nhwc_f32(y = dt, a_h / a_w = sg, r_h / r_w = d means, accumulate).
+ * Two passes of EMA's own forward (stats, gate) and two backward.  Reductions go through per-workgroup partials in `workspace`
+ * (somi_ema_workspace_floats(B, H, W, C) floats, 16-byte aligned), somi_ema_partials(B, H, W, C) per (b, c), and a fixed-order second stage.  No
+ * float atomics: two launches are bit-identical.  SOMI_ENOTIMPL before any launch: C % factor != 0, cg % 4 != 0, cg > 64 (what a group
+ * reduction holds), C > 1024 with a cg / 4 that does not divide 256, a tensor of more than 2^30 floats. */
+typedef struct somi_ema_desc {
+    somi_slice x;              /* the map (B,H,W,.), read by all four */
+    somi_slice x2;             /* conv3x3(x) + bias, read: stats (x2.p NULL: no mean of x2), gate, bwd gate */
+    somi_slice sg;             /* sigmoid(conv1x1(means)) (B, H + W, .), read by all four */
+    somi_slice y;              /* gate: the output, written; bwd gate: dout, read; bwd norm: dt, written */
+    somi_slice res;            /* gate only; res.p NULL: no residual */
+    somi_slice dx;             /* bwd gate only */
+    somi_slice dw;             /* bwd gate: dwgt, written; bwd norm: dwgt read, dx2 written */
+    somi_slice dsg;            /* bwd norm only: (B, H + W, .), written */
+    const float *gamma, *beta;
+    float *stats, *vec;        /* stats: written; the others read vec */
+    float *sums, *bvec;        /* bwd gate: written; bwd norm reads bvec */
+    float *dgamma, *dbeta;     /* bwd gate: added to */
+    float eps;
+    int32_t factor;
+    int32_t accumulate;        /* bwd gate: add to what dx holds */
+    int32_t B, H, W, C;
+    float *workspace;          /* all but gate */
+    uint64_t workspace_floats;
+} somi_ema_desc;
+size_t somi_ema_desc_bytes(void);        /* sizeof(somi_ema_desc) as the library was compiled */
+size_t somi_ema_workspace_floats(int B, int H, int W, int C);
+int somi_ema_partials(int B, int H, int W, int C);      /* host arithmetic: partials per (b, c) of the reductions over the map (0: bad sizes) */
+int somi_ema_stats_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
+int somi_ema_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
+int somi_ema_bwd_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
+int somi_ema_bwd_norm_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
 
 /* Channel prior convolutional attention (CPCA, CPCABottleneck: models/common.py:5753-5859; cpca.hip): the strip part
  *   s = u + V7(H7(u)) + V11(H11(u)) + V21(H21(u)),  H_k the depthwise (1,k) conv along W, V_k the depthwise (k,1) conv along H, zero padding k / 2,

@@ -69,6 +69,15 @@ class CoordAttDesc(C.Structure):
                 ('workspace_floats', C.c_uint64)]
 
 
+class EmaDesc(C.Structure):
+    """struct somi_ema_desc (include/somi_hip.h)."""
+    _fields_ = [('x', Slice), ('x2', Slice), ('sg', Slice), ('y', Slice), ('res', Slice), ('dx', Slice), ('dw', Slice), ('dsg', Slice),
+                ('gamma', C.c_void_p), ('beta', C.c_void_p), ('stats', C.c_void_p), ('vec', C.c_void_p), ('sums', C.c_void_p),
+                ('bvec', C.c_void_p), ('dgamma', C.c_void_p), ('dbeta', C.c_void_p), ('eps', C.c_float), ('factor', C.c_int32),
+                ('accumulate', C.c_int32), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('workspace', C.c_void_p),
+                ('workspace_floats', C.c_uint64)]
+
+
 class CpcaStripDesc(C.Structure):
     """struct somi_cpca_strip_desc (include/somi_hip.h)."""
     _fields_ = [('src', Slice * 4), ('dst', Slice * 3), ('w', C.c_void_p * 3), ('bias', C.c_void_p * 3), ('taps', C.c_int32 * 3),
@@ -275,6 +284,13 @@ SIGNATURES = {
     'somi_coordatt_apply_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
     'somi_coordatt_bwd_gates_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
     'somi_coordatt_bwd_input_nhwc_f32': (I, [C.POINTER(CoordAttDesc), S]),
+    'somi_ema_desc_bytes': (Z, []),
+    'somi_ema_workspace_floats': (Z, [I, I, I, I]),
+    'somi_ema_partials': (I, [I, I, I, I]),
+    'somi_ema_stats_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
+    'somi_ema_gate_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
+    'somi_ema_bwd_gate_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
+    'somi_ema_bwd_norm_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
     'somi_cpca_strip_desc_bytes': (Z, []),
     'somi_cpca_wgrad_desc_bytes': (Z, []),
     'somi_cpca_fanout_nhwc_f32': (I, [C.POINTER(CpcaStripDesc), S]),
@@ -364,6 +380,7 @@ def lib():
         if not lax and (L.somi_sizeof_desc(0) != C.sizeof(ConvDesc) or L.somi_sizeof_desc(1) != C.sizeof(LossDesc)
                         or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)
                         or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)
+                        or L.somi_ema_desc_bytes() != C.sizeof(EmaDesc)
                         or L.somi_cpca_strip_desc_bytes() != C.sizeof(CpcaStripDesc)
                         or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)
                         or L.somi_simam_desc_bytes() != C.sizeof(SimamDesc)

@@ -2900,6 +2900,256 @@ class C3_CA(C3):
     accumulates, folds_pooled, reduction = False, False, 1       # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
 
 
+class EMA(_Packed):
+    """Efficient multi-scale attention (models/common.py:5263-5292) on the children `gn`, `conv1x1`, `conv3x3`: the map, seen as `factor`
+    groups of cg = channels / factor channels that share every weight, is gated per (image, group, pixel) by
+    sigmoid(softmax(mean x1) . x2 + softmax(mean x2) . x1), x1 = gn(x * sigmoid(hw_h) * sigmoid(hw_w)), hw = conv1x1(cat(mean over W, mean
+    over H)), x2 = conv3x3(x).  nn.GroupNorm(cg, cg) on the (B * factor, cg, H, W) view is a norm per (image, channel).
+    Forward: ops.coordatt_means, conv1x1 with its sigmoid as ONE 1x1 conv over the (B, H + W, factor, cg) view of the means, conv3x3, then
+    ops.ema_stats and ops.ema_gate; x1, the expanded gates and the weight map never reach memory.  Backward: ops.ema_backward_gate and
+    ops.ema_backward_norm, the conv backward of conv3x3 (its data gradient added into dx) and conv1x1, and ops.coordatt_backward_input, which
+    adds dt * gates and the means' broadcast.  conv3x3 runs on the dense implicit-GEMM kernels, one launch per group slice with the one shared
+    weight set, the weight gradient chained through `accumulate` (the grouped kernels with replicated weights measured 2.5 to 6.5 times slower
+    per block)."""
+
+    def __init__(self, channels, factor=8):
+        super().__init__()
+        self.groups = factor
+        assert channels // self.groups > 0
+        cg = channels // self.groups
+        self.gn = nn.GroupNorm(cg, cg)
+        self.conv1x1 = nn.Conv2d(cg, cg, kernel_size=1, stride=1, padding=0)
+        self.conv3x3 = nn.Conv2d(cg, cg, kernel_size=3, stride=1, padding=1)
+
+    accumulates, folds_pooled, reduction = False, False, 1       # takes dx_out / accumulate, not walked that way
+
+    def _pack(self, dev):
+        w1, w3 = self.conv1x1.weight.detach().float(), self.conv3x3.weight.detach().float()
+        pk = dict(w1=pack_conv_weight(w1).to(dev), b1=_f32dev(self.conv1x1.bias, dev), w3=pack_conv_weight(w3).to(dev),
+                  b3=_f32dev(self.conv3x3.bias, dev), gamma=_f32dev(self.gn.weight, dev), beta=_f32dev(self.gn.bias, dev))
+        if self.training:
+            pk['wt1'], pk['wt3'] = pack_dgrad_weight(w1).to(dev), pack_dgrad_weight(w3).to(dev)
+        return pk
+
+    def _check(self, x):
+        c, g = self.groups * self.conv3x3.in_channels, self.groups
+        cg = self.conv3x3.in_channels
+        if x.c != c or x.c % g:
+            raise NotImplementedError(f'EMA over {g} groups of {cg} channels got a map of {x.c}: the reference\'s reshape to (B * {g}, {cg}, H, W) '
+                                      f'needs channels % factor == 0 and the width it was built for (models/common.py:5280)')
+        if cg % 4 or cg > 64 or x.up:
+            raise NotImplementedError(f'EMA with {cg} channels per group is not on the SOMI path (a multiple of 4, at most 64, a real tensor)')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd EMA runs on the MI355X only (no CPU fallback)')
+        return c, g, cg
+
+    def forward(self, x, out=None, residual=None):
+        """x: the attended map (Act); out: the Act to write (a new one when None); residual: an Act added to the result in the gate pass."""
+        c, g, cg = self._check(x)
+        pk = self._packed(x.t.device)
+        B, H, W, _ = x.shape
+        pool = ops.coordatt_means(x.t, c, x.coff)
+        sg = ops.conv2d_nhwc(pool.view(B, H + W, g, cg), pk['w1'], pk['b1'], kh=1, kw=1, act='sigmoid', cin=cg, cout=cg).view(B, H + W, c)
+        x2 = torch.empty(B, H, W, c, device=x.t.device, dtype=torch.float32)
+        for gi in range(g):
+            ops.conv2d_nhwc(x.t, pk['w3'], pk['b3'], kh=3, kw=3, pad=1, cin=cg, x_coff=x.coff + gi * cg, out=x2, cout=cg, y_coff=gi * cg)
+        _, vec = ops.ema_stats(x.t, sg, c, g, pk['gamma'], pk['beta'], self.gn.eps, x.coff, x2=x2)
+        if out is None:
+            out = new_act(x.t, H, W, c)
+            if out.t.shape[3] != c:
+                out.t.zero_()                                     # pad channels of a tensor of its own
+        ops.ema_gate(x.t, x2, sg, vec, c, g, pk['gamma'], pk['beta'], x.coff, res=None if residual is None else residual.t,
+                     res_coff=0 if residual is None else residual.coff, out=out.t, o_coff=out.coff)
+        if self.training:
+            self.__dict__['_ctx'] = (x, pool, sg, x2, vec, pk)
+        return Act(out.t, out.coff, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """dout: the gradient of x * sigmoid(wgt) (a residual's share is the caller's).  -> the gradient of x as an Act: a whole padded tensor of
+        its own (pad channels zero) when dx_out is None, else written into dx_out, added to it with `accumulate`.  Parameter gradients into .grad."""
+        x, pool, sg, x2, vec, pk = self.__dict__.pop('_ctx')
+        g, cg = self.groups, self.conv3x3.in_channels
+        c = g * cg
+        B, H, W, _ = x.shape
+        dev = x.t.device
+        if dx_out is None:
+            dx_out = new_act(x.t, H, W, c)
+            if dx_out.t.shape[3] != c:
+                dx_out.t.zero_()
+            accumulate = False
+        (dgam, dbet), fin = _grad_targets(self.gn.weight, self.gn.bias)
+        _, dw, _, bvec = ops.ema_backward_gate(dout.t, x.t, x2, sg, vec, c, g, pk['gamma'], pk['beta'], dgam, dbet, dout.coff, x.coff,
+                                               dx=dx_out.t, dx_coff=dx_out.coff, accumulate=accumulate)
+        fin()
+        dt, dx2, dsg = ops.ema_backward_norm(x.t, sg, dw, vec, bvec, c, g, pk['gamma'], pk['beta'], x.coff)
+        # conv3x3: bias, weight (summed over the groups that share it), data gradient added into dx
+        db3 = torch.zeros(c, device=dev)
+        ops.chan_sum_(dx2, c, 0, db3)
+        _acc_grad(self.conv3x3.bias, db3.view(g, cg).sum(0))
+        dw3 = torch.empty(cg, 9 * cg, device=dev, dtype=torch.float32)
+        for gi in range(g):
+            ops.conv2d_wgrad_nhwc(x.t, dx2, kh=3, kw=3, pad=1, cin=cg, x_coff=x.coff + gi * cg, cout=cg, dy_coff=gi * cg, out=dw3,
+                                  accumulate=dw3 if gi else None)
+            ops.conv2d_dgrad_nhwc(dx2, pk['wt3'], B=B, H=H, W=W, cin=cg, kh=3, kw=3, pad=1, cout=cg, dy_coff=gi * cg, out=dx_out.t,
+                                  dx_coff=dx_out.coff + gi * cg, accumulate=dx_out.t, acc_coff=dx_out.coff + gi * cg)
+        _acc_grad(self.conv3x3.weight, dw3.view(cg, 3, 3, cg).permute(0, 3, 1, 2))
+        # conv1x1 on the (B, H + W, g, cg) view; dsg is the gradient in front of its sigmoid
+        dsv, plv = dsg.view(B, H + W, g, cg), pool.view(B, H + W, g, cg)
+        db1 = torch.zeros(cg, device=dev)
+        ops.chan_sum_(dsv, cg, 0, db1)
+        _acc_grad(self.conv1x1.bias, db1)
+        dw1 = ops.conv2d_wgrad_nhwc(plv, dsv, kh=1, kw=1, cin=cg, cout=cg)
+        _acc_grad(self.conv1x1.weight, dw1.view(cg, cg, 1, 1))
+        dpool = ops.conv2d_dgrad_nhwc(dsv, pk['wt1'], B=B, H=H + W, W=g, cin=cg, kh=1, kw=1, cout=cg).view(B, H + W, c)
+        ops.coordatt_backward_input(dt, (sg, 0, 0), (sg, 0, H), (dpool, 0, 0), (dpool, 0, H), c, 0, out=dx_out.t, dx_coff=dx_out.coff,
+                                    accumulate=True)
+        return Act(dx_out.t, dx_out.coff, c)
+
+
+class _ConvNormAct(Conv):
+    """The reference's ConvNormAct (models/common.py:5387-5406) at what iRMB_EMA builds of it: conv (no bias) -> BatchNorm -> activation, the
+    children named `conv` and `norm`.  Runs as Conv does; `bn` is `norm` under Conv's name."""
+
+    def __init__(self, dim, k, g, act):
+        super().__init__(dim, dim, k, 1, g=g, act=act)
+        self.norm = self._modules.pop('bn')
+        self.norm.eps = 1e-6                                      # get_norm's eps, until initialize_weights sets 1e-3 / 0.03
+
+    bn = property(lambda self: self.norm)
+    accumulates, folds_pooled, reduction = False, False, 1
+
+
+class _Proj(nn.Module):
+    """ConvNormAct(dim, dim, 1, norm_layer='none', act_layer='none'): a 1x1 conv without bias, the child `conv`."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.conv = nn.Conv2d(dim, dim, 1, 1, 0, bias=False)
+
+
+class iRMB_EMA(_Packed):
+    """Inverted residual mobile block with EMA as its attention (models/common.py:5409-5451), at the reference's defaults:
+    out = x + proj(e + SiLU(BN(dw3x3(e)))), e = EMA(norm(x)), norm a BatchNorm without activation, proj a 1x1 conv without bias; the shortcut is
+    the input BEFORE norm.  norm and conv_local.norm go through the one BatchNorm train path (eval: norm is a per-channel affine, conv_local's
+    folds at pack time); the first residual rides the depthwise conv's output pass, the second proj's epilogue; in backward the first rides the
+    depthwise data gradient, the second is one add behind the norm's backward."""
+
+    def __init__(self, dim_in, norm_in=True, has_skip=True, exp_ratio=1.0, norm_layer='bn_2d', act_layer='relu', v_proj=True, dw_ks=3, stride=1,
+                 dilation=1, se_ratio=0.0, attn_s=True, qkv_bias=False, drop=0., drop_path=0.):
+        super().__init__()
+        given = dict(norm_in=norm_in, has_skip=has_skip, exp_ratio=exp_ratio, norm_layer=norm_layer, dw_ks=dw_ks, stride=stride, dilation=dilation,
+                     se_ratio=se_ratio, attn_s=attn_s, drop=drop, drop_path=drop_path)
+        want = dict(norm_in=True, has_skip=True, exp_ratio=1.0, norm_layer='bn_2d', dw_ks=3, stride=1, dilation=1, se_ratio=0.0, attn_s=True,
+                    drop=0., drop_path=0.)
+        off = {k: v for k, v in given.items() if v != want[k]}
+        if off:
+            raise NotImplementedError(f'iRMB_EMA({dim_in}, {off}): only the reference\'s defaults are on the SOMI path '
+                                      f'(models/common.py:5411-5413: {want})')
+        self.norm = nn.BatchNorm2d(dim_in, eps=1e-6)             # get_norm's eps; initialize_weights sets 1e-3 / 0.03 on every BatchNorm2d
+        self.ema = EMA(dim_in)
+        self.conv_local = _ConvNormAct(dim_in, dw_ks, dim_in, nn.SiLU())
+        self.proj = _Proj(dim_in)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def _pack_params(self):
+        return [*self.norm.parameters(), *self.proj.parameters()]
+
+    def _pack(self, dev):
+        w = self.proj.conv.weight.detach().float()
+        pk = dict(wp=pack_conv_weight(w).to(dev))
+        if self.training:
+            pk['wtp'] = pack_dgrad_weight(w).to(dev)
+        else:
+            pk['norm'] = tuple(_f32dev(t, dev) for t in bn_fold(self.norm))
+        return pk
+
+    def forward(self, x, out=None, residual=None):
+        """residual: a further Act added to the result (the bottleneck's shortcut), by one add behind proj."""
+        c = self.norm.num_features
+        if x.c != c or c % 4 or pad4(c) != c or x.up:
+            raise NotImplementedError(f'iRMB_EMA({c}) takes a real map of {c} channels (a multiple of 32), got {x.c}')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd iRMB_EMA runs on the MI355X only (no CPU fallback)')
+        pk = self._packed(x.t.device)
+        B, H, W, _ = x.shape
+        xn = torch.empty(B, H, W, c, device=x.t.device, dtype=torch.float32)
+        if self.training:
+            st, commit = _bn_train(self.norm, c, x.t, coff=x.coff)
+            commit()
+            ops.chan_affine_act(x.t, c, x.coff, st[2], st[3], 'none', 0, xn)
+        else:
+            st = None
+            ops.chan_affine_act(x.t, c, x.coff, pk['norm'][0], pk['norm'][1], 'none', 0, xn)
+        e = self.ema(Act(xn, 0, c))
+        t2 = self.conv_local(e, residual=e)
+        if out is None:
+            out = new_act(x.t, H, W, c)
+        ops.conv2d_nhwc(t2.t, pk['wp'], None, kh=1, kw=1, cin=c, x_coff=t2.coff, out=out.t, cout=c, y_coff=out.coff, residual=x.t, res_coff=x.coff)
+        if residual is not None:
+            ops.add_(out.t, out.coff, residual.t, residual.coff, c)
+        if self.training:
+            self.__dict__['_ctx'] = (x, st, t2, pk)
+        return Act(out.t, out.coff, c)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        x, st, t2, pk = self.__dict__.pop('_ctx')
+        c = self.norm.num_features
+        dt2 = _plain_conv_backward(self.proj.conv, t2, dout.t, pk['wtp'], dy_coff=dout.coff, direct=('weight',))
+        de = self.conv_local.backward(dt2, also_add=dt2)         # e + conv_local(e): the residual's share rides the depthwise data gradient
+        dxn = self.ema.backward(de)
+        dxb = torch.empty_like(x.t)
+        _bn_backward(self.norm, dxn.t, dxn.coff, x.t, st, 'none', dxb, c, coff=x.coff)
+        if dx_out is None:
+            ops.add_(dxb, x.coff, dout.t, dout.coff, c)
+            return Act(dxb, x.coff, c)
+        if accumulate:
+            ops.add_(dx_out.t, dx_out.coff, dxb, x.coff, c)
+            ops.add_(dx_out.t, dx_out.coff, dout.t, dout.coff, c)
+        else:
+            ops.add_(dxb, x.coff, dout.t, dout.coff, c, out=dx_out.t, out_coff=dx_out.coff)
+        return Act(dx_out.t, dx_out.coff, c)
+
+
+class iRMB_EMABottleneck(nn.Module):
+    """cv1 -> cv2 -> iRMB_EMA (+x) (models/common.py:5454-5470); the shortcut is one add behind the block's proj (forward) and rides cv1's dgrad
+    epilogue (backward)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, k[0], 1)
+        self.cv2 = Conv(c_, c2, k[1], 1, g=g)
+        self.add = shortcut and c1 == c2
+        self.iRMB = iRMB_EMA(c2)
+
+    accumulates, folds_pooled, reduction = False, False, 1
+
+    def forward(self, x, out=None):
+        return self.iRMB(self.cv2(self.cv1(x)), out=out, residual=x if self.add else None)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d = self.cv2.backward(self.iRMB.backward(dout))
+        c1 = self.cv1.conv.in_channels
+        fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0
+        dx = self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if self.add and not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class C2f_iRMB_EMA(C2f):
+    """C2f whose blocks are iRMB_EMABottleneck(c, c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) (models/common.py:5473-5497); the branches are
+    written into the concat buffer in place, as C2f's.  The reference's parser builds it from the yaml arguments as written
+    (models/yolo.py:1648-1650)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(iRMB_EMABottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
+
+    accumulates, folds_pooled, reduction = False, False, 1       # C2f's backward, dx_out / accumulate included; the walk adds its gradient itself
+
+
 class CPCA_ChannelAttention(_Packed):
     """t * (sigmoid(MLP(avgpool t)) + sigmoid(MLP(maxpool t))) (models/common.py:5753-5779): the shared MLP - two 1x1 convs with bias on a 1x1
     map, i.e. two small dense layers - runs once on the 2B rows (averages, then maxima) one pooling pass leaves; each half gets its own sigmoid

@@ -235,6 +235,29 @@ def yolov5_ca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
     return cfg
 
 
+def yolov5_ema_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c2f'):
+    """yolov5s 6.0 with efficient multi-scale attention (EMA, models/common.py:5263-5292; iRMB_EMA, iRMB_EMABottleneck and C2f_iRMB_EMA,
+    :5409-5497).  The reference's parser registers none of them: its generic branch builds them from the yaml arguments as written and records the
+    input's width (models/yolo.py:1648-1650), and it ships no yaml that names them.  where='c2f': the four backbone C3 rows become
+    [-1, 1, 'C2f_iRMB_EMA', [c, c, n, True]] with c and n written out already scaled, since that branch scales nothing; where='row': an
+    [-1, 1, 'EMA', [c]] row behind SPPF, c the scaled width there, the head's absolute indices one up."""
+    if where not in ('c2f', 'row'):
+        raise ValueError(f"where must be 'c2f' or 'row', got {where!r}")
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    scaled = lambda c: math.ceil(c * width / 8) * 8              # noqa: E731  (make_divisible(c * gw, 8), models/yolo.py:1481)
+    if where == 'c2f':
+        for row in cfg['backbone']:
+            if row[2] == 'C3':
+                n = max(round(row[1] * depth), 1) if row[1] > 1 else row[1]
+                row[1:] = [1, 'C2f_iRMB_EMA', [scaled(row[3][0]), scaled(row[3][0]), n, True]]
+        return cfg
+    cfg['backbone'].append([-1, 1, 'EMA', [scaled(1024)]])
+    for row in cfg['head']:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+    return cfg
+
+
 def yolov5_context_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='aspp'):
     """yolov5s 6.0 with the dilated-convolution context blocks (ASPP, models/common.py:1829-1843; C2f_DWR, :7431-7511).  The reference registers
     both in its parser (models/yolo.py:1472-1492, C2f_DWR among the modules repeated inside) but ships no yaml that names them.  where='aspp': a

@@ -19,7 +19,8 @@ and the ASF-YOLO neck: `Zoom_cat` (three inputs at strides 2 : 1 : 1/2, c2 = 3 *
 channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] channels), none of them width-scaled; and the slim-neck
 pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repeated inside); and the large-kernel depthwise blocks `CNeB`
 (repeated inside), `ConvMix` and `CSPCM` (n > 1 a Repeat of whole modules; a `ConvMix` row must name the channels behind it, which it passes
-through).
+through); and efficient multi-scale attention: `EMA`, `iRMB_EMA`, `iRMB_EMABottleneck` and `C2f_iRMB_EMA` rows, built from the yaml
+arguments as written (the reference's generic branch), which must name the width of their input.
 """
 import math
 from copy import deepcopy
@@ -54,6 +55,9 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
 _SIMAM_SLICED = {'SimAMWithSlicing': B.SimAMWithSlicing, 'SimAMWithFlexibleSlicing': B.SimAMWithFlexibleSlicing}      # models/yolo.py:1504-1513
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
 _REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM', 'CNeB')
+# efficient multi-scale attention: none of the four is in a list of the reference's parser, so its generic branch builds them from the yaml
+# arguments as written and records the input's width for the rows behind (models/yolo.py:1648-1650)
+_EMA = {'EMA': B.EMA, 'iRMB_EMA': B.iRMB_EMA, 'iRMB_EMABottleneck': B.iRMB_EMABottleneck, 'C2f_iRMB_EMA': B.C2f_iRMB_EMA}
 _PASS_THROUGH = {'nn.MaxPool2d': B.MaxPool2d, 'nn.ZeroPad2d': B.ZeroPad2d}      # the generic branch, models/yolo.py:1647-1648
 _HEADS = {'DecoupledDetect': B.DecoupledDetect, 'Detect': B.Detect, 'ASFF_Detect': B.ASFF_Detect}       # ASFF_Detect: models/yolo.py:1611-1615
 _ALIASES = {'C2fEACBAM': 'C2fCBAM'}     # undefined in the reference (SURVEY "five facts" #2); documented substitution
@@ -131,6 +135,14 @@ def parse_model(d, ch):
         elif name == 'PSSimAM':                                   # the generic branch, models/yolo.py:1647-1648: arguments as written
             m = B.PSSimAM
             c2 = ch[f]
+        elif name in _EMA:                                        # the generic branch, models/yolo.py:1648-1650: arguments as written, c2 = ch[f]
+            m = _EMA[name]
+            c2 = ch[f]
+            if not args or args[0] != c2 or (name in ('C2f_iRMB_EMA', 'iRMB_EMABottleneck') and (len(args) < 2 or args[1] != c2)):
+                named = args[:1] if name in ('EMA', 'iRMB_EMA') else args[:2]
+                raise ValueError(f'a {name!r} row that names {named} channels behind {c2}: the reference builds it from the yaml arguments as '
+                                 f'written, unscaled, and sizes the rows behind it by its input (models/yolo.py:1648-1650), so the block would '
+                                 f'read or leave another width than the graph records')
         elif name in _PASS_THROUGH:                               # parameter-free, channels pass through
             m = _PASS_THROUGH[name]
             c2 = ch[f]

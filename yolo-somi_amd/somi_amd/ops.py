@@ -539,6 +539,112 @@ def coordatt_backward_input(dout, a_h, a_w, gh, gw, c, do_coff=0, *, out=None, d
     return out
 
 
+# ---------------------------------------------------------------------------------------------- EMA (ema.hip)
+def ema_partials(B, H, W, c):
+    """Partials per (image, channel) of the EMA kernels' reductions over the map at this size (host arithmetic; 0 for bad sizes)."""
+    return _lib.lib().somi_ema_partials(int(B), int(H), int(W), int(c))
+
+
+def _ema_rows(t, B, n, coff, what):
+    """sg / dsg: a contiguous (B, H + W, cs) or (B, H + W, 1, cs) tensor -> Slice."""
+    if t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[2] != 1) or t.shape[0] != B or t.shape[1] != n:
+        raise RuntimeError(f'{what}: a ({B}, {n}, cs) tensor is expected, got {tuple(t.shape)}')
+    return _lib.Slice(_ptr(_f32c(t)), t.shape[-1], coff)
+
+
+def _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, what, workspace=True):
+    B, H, W, _ = x.shape
+    cg = c // max(factor, 1)
+    if gamma.numel() != cg or beta.numel() != cg:
+        raise RuntimeError(f'{what}: gamma and beta hold {gamma.numel()} and {beta.numel()} values, a group has {cg} channels')
+    d = _lib.EmaDesc()
+    d.B, d.H, d.W, d.C, d.factor = B, H, W, c, factor
+    d.x, d.sg = _slice(x, x_coff), _ema_rows(sg, B, H + W, sg_coff, what + ': sg')
+    d.gamma, d.beta, d.vec = _ptr(_f32c(gamma)), _ptr(_f32c(beta)), _ptr(_f32c(vec))
+    ws = None
+    if workspace:
+        ws = torch.empty(max(_lib.lib().somi_ema_workspace_floats(B, H, W, c), 4), device=x.device, dtype=torch.float32)
+        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return d, ws
+
+
+def _ema_check(rc, what):
+    if rc == -2:                                                  # SOMI_ENOTIMPL: a configuration the kernels refuse before any launch
+        raise NotImplementedError(f'{what}: {_lib.lib().somi_last_error().decode(errors="replace")}')
+    check(rc, what)
+
+
+def _ema_map(t, like, what):
+    if tuple(t.shape[:3]) != tuple(like.shape[:3]):
+        raise RuntimeError(f'{what}: every map must be {tuple(like.shape[:3])} + (.,), got {tuple(t.shape)}')
+    return t
+
+
+def ema_stats(x, sg, c, factor, gamma, beta, eps, x_coff=0, *, sg_coff=0, x2=None, x2_coff=0):
+    """Per (image, channel) of t = x * sg_h[b,h,:] * sg_w[b,w,:]: -> (stats (B, 3, c): mean of t, its sum of squared deviations, the mean of
+    x2 (zero without x2); vec (B, 4, c): mean, rstd, x21 = the softmax of the x2 means over each group of c / factor channels, x11 = the
+    softmax of beta).  sg (B, H + W, .): the sigmoided gates, rows [0, H) by row and [H, H + W) by column."""
+    B = x.shape[0]
+    stats = torch.empty(B, 3, c, device=x.device, dtype=torch.float32)
+    vec = torch.empty(B, 4, c, device=x.device, dtype=torch.float32)
+    d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_stats')     # noqa: F841  (ws alive until the launch is enqueued)
+    d.stats, d.eps = _ptr(stats), float(eps)
+    if x2 is not None:
+        d.x2 = _slice(_ema_map(x2, x, 'ema_stats'), x2_coff)
+    _ema_check(_lib.lib().somi_ema_stats_nhwc_f32(C.byref(d), _stream()), 'ema_stats')
+    return stats, vec
+
+
+def ema_gate(x, x2, sg, vec, c, factor, gamma, beta, x_coff=0, *, x2_coff=0, sg_coff=0, res=None, res_coff=0, out=None, o_coff=0):
+    """out = [res +] x * sigmoid(wgt), wgt per (image, group, pixel) = sum_j x11[j] x2[j] + x21[j] x1[j] with x1 = gamma * (t - mean) * rstd + beta
+    rebuilt from x, sg and vec (ema_stats)."""
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    d, _ = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_gate', workspace=False)
+    d.x2, d.y = _slice(_ema_map(x2, x, 'ema_gate'), x2_coff), _slice(_ema_map(out, x, 'ema_gate'), o_coff)
+    if res is not None:
+        d.res = _slice(_ema_map(res, x, 'ema_gate'), res_coff)
+    _ema_check(_lib.lib().somi_ema_gate_nhwc_f32(C.byref(d), _stream()), 'ema_gate')
+    return out
+
+
+def ema_backward_gate(dout, x, x2, sg, vec, c, factor, gamma, beta, dgamma, dbeta, do_coff=0, x_coff=0, *, x2_coff=0, sg_coff=0, dx=None,
+                      dx_coff=0, accumulate=False, dw=None, dw_coff=0):
+    """From dout = d(x * sigmoid(wgt)): dx = dout * sigmoid(wgt) (written, or added with `accumulate`), dw = dwgt over the channels of each group,
+    sums (B, 3, c) = sum dwgt * that, sum dwgt, sum dwgt * x2, bvec (B, 3, c) for ema_backward_norm; dgamma / dbeta (c / factor) are ADDED to.
+    -> (dx, dw, sums, bvec)."""
+    B, H, W, _ = x.shape
+    if dx is None:
+        if accumulate:
+            raise RuntimeError('ema_backward_gate: accumulate needs the tensor to add to')
+        dx = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    dw = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dw is None else dw
+    sums = torch.empty(B, 3, c, device=x.device, dtype=torch.float32)
+    bvec = torch.empty(B, 3, c, device=x.device, dtype=torch.float32)
+    d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_backward_gate')     # noqa: F841
+    d.x2, d.y = _slice(_ema_map(x2, x, 'ema_backward_gate'), x2_coff), _slice(_ema_map(dout, x, 'ema_backward_gate'), do_coff)
+    d.dx, d.dw = _slice(_ema_map(dx, x, 'ema_backward_gate'), dx_coff), _slice(_ema_map(dw, x, 'ema_backward_gate'), dw_coff)
+    d.sums, d.bvec, d.dgamma, d.dbeta, d.accumulate = _ptr(sums), _ptr(bvec), _ptr(_f32c(dgamma)), _ptr(_f32c(dbeta)), int(accumulate)
+    if dgamma.numel() != gamma.numel() or dbeta.numel() != beta.numel():
+        raise RuntimeError('ema_backward_gate: dgamma / dbeta must have gamma\'s / beta\'s size')
+    _ema_check(_lib.lib().somi_ema_bwd_gate_nhwc_f32(C.byref(d), _stream()), 'ema_backward_gate')
+    return dx, dw, sums, bvec
+
+
+def ema_backward_norm(x, sg, dw, vec, bvec, c, factor, gamma, beta, x_coff=0, *, sg_coff=0, dw_coff=0, dt=None, dt_coff=0, dsg=None, dsg_coff=0):
+    """The instance-norm backward: dt = the gradient of t (written), dw: dwgt -> dx2 = the gradient of conv3x3's output IN PLACE,
+    dsg (B, H + W, .) = the gradient of conv1x1's output in front of its sigmoid.  -> (dt, dw, dsg)."""
+    B, H, W, _ = x.shape
+    dt = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dt is None else dt
+    dsg = torch.empty(B, H + W, c, device=x.device, dtype=torch.float32) if dsg is None else dsg
+    d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_backward_norm')     # noqa: F841
+    d.dw, d.y = _slice(_ema_map(dw, x, 'ema_backward_norm'), dw_coff), _slice(_ema_map(dt, x, 'ema_backward_norm'), dt_coff)
+    d.dsg, d.bvec = _ema_rows(dsg, B, H + W, dsg_coff, 'ema_backward_norm: dsg'), _ptr(_f32c(bvec))
+    _ema_check(_lib.lib().somi_ema_bwd_norm_nhwc_f32(C.byref(d), _stream()), 'ema_backward_norm')
+    return dt, dw, dsg
+
+
 # ---------------------------------------------------------------------------------------------- SimAM (simam.hip)
 SIMAM_MAX_COVER = 4     # regions over one pixel along an axis (SA_COVER of simam.hip)
 
