@@ -58,7 +58,7 @@ enum somi_act { SOMI_ACT_NONE = 0, SOMI_ACT_SILU = 1, SOMI_ACT_GELU = 2, SOMI_AC
                                        coordinate attention: taken wherever SOMI_ACT_LEAKY is */ };
 
 /* A channel slice as one argument (the slice rule above: p 16-byte aligned, cs and coff multiples of 4), for the entry points that take their
- * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_ema_desc, somi_simam_desc, the asf.hip descriptors).  An input slice is only read. */
+ * slices by value or in a descriptor (somi_maxpool3s2_*, somi_asff_desc, somi_coordatt_desc, somi_ema_desc, somi_acmix_desc, somi_simam_desc, the asf.hip descriptors).  An input slice is only read. */
 typedef struct somi_slice {
     float *p;
     int32_t cs, coff;
@@ -453,6 +453,55 @@ int somi_ema_stats_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
 int somi_ema_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
 int somi_ema_bwd_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
 int somi_ema_bwd_norm_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream);
+
+/* ACmix (models/common.py:7281-7365; acmix.hip): a 7x7 sliding-window attention over 4 heads with reflection padding 3 and a linear position
+ * term, mixed with a grouped 3x3 conv over the same q, k, v.  C = out_planes, D = C / 4, channel (head h, dim d) = h * D + d, s = D ** -0.5; q, k, v
+ * are slices C wide (in the block: thirds of the stacked 1x1 projection).  wp: conv_p.weight, (D, 2) floats, column 0 for x; rate1, rate2: one
+ * float each, read on the device.  r(.) reflects an index, lx(x) = -1 + 2 x / (W - 1), ly(y) likewise.
+ * attn    (somi_acmix_attn_nhwc_f32):        score_j = s * (q_p . k_r(p+j) + (q_p . wp[:, 0]) (lx(p) - lx(r(p+j))) + (q_p . wp[:, 1]) (ly(p) - ly(r(p+j))))
+ *         over the 49 taps j, a = softmax (maximum subtracted), out = rate1 * sum_j a_j v_r(p+j) [+ rate2 * mix].  lse (optional, 4 wide): the
+ *         log-sum-exp per (pixel, head), written.  conv_p.bias cancels and the position map is never built.
+ * bwd q   (somi_acmix_attn_bwd_q_nhwc_f32):  out holds dout (read).  dq written (added with `accumulate`); aux (24 wide) written per (pixel, head):
+ *         delta = sum_j a_j (rate1 dout_p . v_j), q . wp[:, 0], q . wp[:, 1], sum_j dS_j dx_j, sum_j dS_j dy_j, 1 / sum_j exp(score_j - lse) (the fp32 lse leaves that sum off 1); dwp (D, 2) and
+ *         drates = (sum dout . att, sum dout . mix (0 without mix)) WRITTEN, from partials in `workspace` folded in a fixed order.
+ * bwd kv  (somi_acmix_attn_bwd_kv_nhwc_f32): reads q, k, v, dout, lse and the aux bwd q wrote.  dk, dv written (added with `accumulate`) by the
+ *         owner pixel: each query of the clipped window around it counts once per tap that reflects onto the owner.
+ * conv    (somi_acmix_conv_nhwc_f32):        mix[., 4 d + o] = bias[4 d + o] + sum_(t, tap) weff[t][tap][d][o] * src_t[p + tap][d] with zero padding,
+ *         the 12 sources t = 4 * (q, k, v) + head: dep_conv(fc(.)) as ONE grouped conv, the 9 D-channel fc output never exists.
+ *         weff: (12, 9, D, 4) floats from somi_acmix_fold_weff_f32(fc.weight (9, 12), dep_conv.weight (C, 9, 3, 3)).
+ * conv bwd data / weight: out holds dout.  data: dq, dk, dv = rate2 * the transposed conv of dout, written (added with `accumulate`).  weight:
+ *         dweff (weff's layout) and dbias (C) = rate2 * the sums over the map, WRITTEN, partials in `workspace` folded in order;
+ *         somi_acmix_split_dweff_f32 turns dweff into the gradients of fc.weight and dep_conv.weight (written).
+ * Workspace: somi_acmix_workspace_floats(B, H, W, C) floats, 16-byte aligned (bwd q, conv bwd weight).  The reductions use partials folded in
+ * a fixed order: two launches are bit-identical.  SOMI_ENOTIMPL before any launch: C % 16 != 0, C > 1024, a tensor of more than 2^30
+ * floats; SOMI_EINVAL: H < 4 or W < 4 (the reflection pad of 3), a broken slice, a missing pointer or workspace. */
+typedef struct somi_acmix_desc {
+    somi_slice q, k, v;        /* (B,H,W,.), read (conv bwd data: unused) */
+    somi_slice mix;            /* conv: written; attn, bwd q: read, optional */
+    somi_slice out;            /* attn: the output, written; every backward pass: dout, read */
+    somi_slice lse;            /* 4 wide; attn: written (optional); bwd q, bwd kv: read */
+    somi_slice aux;            /* 24 wide; bwd q: written; bwd kv: read */
+    somi_slice dq, dk, dv;     /* bwd q: dq; bwd kv: dk, dv; conv bwd data: all three */
+    const float *wp, *rate1, *rate2;
+    const float *weff, *bias;  /* conv, conv bwd data (weff) */
+    float *dwp, *drates;       /* bwd q: written */
+    float *dweff, *dbias;      /* conv bwd weight: written */
+    int32_t accumulate;        /* bwd q, bwd kv, conv bwd data: add to what dq / dk / dv hold */
+    int32_t B, H, W, C;
+    float *workspace;          /* bwd q, conv bwd weight */
+    uint64_t workspace_floats;
+} somi_acmix_desc;
+size_t somi_acmix_desc_bytes(void);      /* sizeof(somi_acmix_desc) as the library was compiled */
+size_t somi_acmix_workspace_floats(int B, int H, int W, int C);    /* 0: sizes outside the path */
+int somi_acmix_plan(int H, int W, int *tile, int *tiles_y, int *tiles_x);   /* host arithmetic: the square pixel tile of a workgroup and their count per image */
+int somi_acmix_attn_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_attn_bwd_q_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_attn_bwd_kv_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_conv_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_conv_bwd_data_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_conv_bwd_weight_nhwc_f32(const somi_acmix_desc *d, somi_stream_t stream);
+int somi_acmix_fold_weff_f32(const float *fc, const float *dep, float *weff, int C, somi_stream_t stream);
+int somi_acmix_split_dweff_f32(const float *dweff, const float *fc, const float *dep, float *dfc, float *ddep, int C, somi_stream_t stream);
 
 /* Channel prior convolutional attention (CPCA, CPCABottleneck: models/common.py:5753-5859; cpca.hip): the strip part
  *   s = u + V7(H7(u)) + V11(H11(u)) + V21(H21(u)),  H_k the depthwise (1,k) conv along W, V_k the depthwise (k,1) conv along H, zero padding k / 2,

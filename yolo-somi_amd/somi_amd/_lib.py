@@ -78,6 +78,14 @@ class EmaDesc(C.Structure):
                 ('workspace_floats', C.c_uint64)]
 
 
+class AcmixDesc(C.Structure):
+    """struct somi_acmix_desc (include/somi_hip.h)."""
+    _fields_ = [(n, Slice) for n in ('q', 'k', 'v', 'mix', 'out', 'lse', 'aux', 'dq', 'dk', 'dv')] + \
+               [(n, C.c_void_p) for n in ('wp', 'rate1', 'rate2', 'weff', 'bias', 'dwp', 'drates', 'dweff', 'dbias')] + \
+               [('accumulate', C.c_int32), ('B', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32), ('workspace', C.c_void_p),
+                ('workspace_floats', C.c_uint64)]
+
+
 class CpcaStripDesc(C.Structure):
     """struct somi_cpca_strip_desc (include/somi_hip.h)."""
     _fields_ = [('src', Slice * 4), ('dst', Slice * 3), ('w', C.c_void_p * 3), ('bias', C.c_void_p * 3), ('taps', C.c_int32 * 3),
@@ -291,6 +299,17 @@ SIGNATURES = {
     'somi_ema_gate_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
     'somi_ema_bwd_gate_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
     'somi_ema_bwd_norm_nhwc_f32': (I, [C.POINTER(EmaDesc), S]),
+    'somi_acmix_desc_bytes': (Z, []),
+    'somi_acmix_workspace_floats': (Z, [I, I, I, I]),
+    'somi_acmix_plan': (I, [I, I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'somi_acmix_attn_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_attn_bwd_q_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_attn_bwd_kv_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_conv_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_conv_bwd_data_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_conv_bwd_weight_nhwc_f32': (I, [C.POINTER(AcmixDesc), S]),
+    'somi_acmix_fold_weff_f32': (I, [P, P, P, I, S]),
+    'somi_acmix_split_dweff_f32': (I, [P, P, P, P, P, I, S]),
     'somi_cpca_strip_desc_bytes': (Z, []),
     'somi_cpca_wgrad_desc_bytes': (Z, []),
     'somi_cpca_fanout_nhwc_f32': (I, [C.POINTER(CpcaStripDesc), S]),
@@ -381,6 +400,7 @@ def lib():
                         or L.somi_sizeof_desc(2) != C.sizeof(LossBoxRule) or L.somi_asff_desc_bytes() != C.sizeof(AsffDesc)
                         or L.somi_coordatt_desc_bytes() != C.sizeof(CoordAttDesc)
                         or L.somi_ema_desc_bytes() != C.sizeof(EmaDesc)
+                        or L.somi_acmix_desc_bytes() != C.sizeof(AcmixDesc)
                         or L.somi_cpca_strip_desc_bytes() != C.sizeof(CpcaStripDesc)
                         or L.somi_cpca_wgrad_desc_bytes() != C.sizeof(CpcaWgradDesc)
                         or L.somi_simam_desc_bytes() != C.sizeof(SimamDesc)

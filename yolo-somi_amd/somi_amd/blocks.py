@@ -3006,6 +3006,140 @@ class EMA(_Packed):
         return Act(dx_out.t, dx_out.coff, c)
 
 
+class ACmix(_Packed):
+    """Self-attention and convolution mixed (models/common.py:7281-7365) with the reference's constructor, parameter names and initial values:
+    out = rate1 * att + rate2 * conv over q, k, v = conv1(x), conv2(x), conv3(x).  att: per head (4) and pixel a softmax attention over the 7x7
+    window around it, reflection padding 3, scores s * q . (k_j + pe_p - pe_j) with pe = conv_p(position map), s = head_dim ** -0.5; conv:
+    dep_conv(fc(.)), fc a 1x1 conv over the 12 (q, k, v) x head maps of every head dim, dep_conv a grouped 3x3 conv.
+    Forward: the three projections as ONE 1x1 conv c1 -> 3 c2 on the dense kernels, ops.acmix_conv (fc and dep_conv folded into one grouped conv,
+    the 9 x head_dim-channel fc output never exists) and ops.acmix_attn with the mix in its epilogue; the unfolded windows, the position map and
+    the scores never reach memory.  Only differences of pe enter, so conv_p.bias cancels: its gradient is exactly zero.  Backward:
+    ops.acmix_conv_backward_data writes the gradient of the stacked q, k, v, ops.acmix_attn_backward_q and _kv add theirs, then the plain conv
+    backward of the stacked projection.  The reference's reset_parameters leaves dep_conv WITHOUT a bias (`self.dep_conv.bias =
+    init_rate_0(...)` assigns the helper's None, models/common.py:7321), and so does this class; a bias given to dep_conv later is honoured.
+    rate1 / rate2 are plain parameters: they take a gradient and the reference puts them in no optimizer group (train.py:125-133)."""
+
+    def __init__(self, in_planes, out_planes, kernel_att=7, head=4, kernel_conv=3, stride=1, dilation=1):
+        super().__init__()
+        for name, got, want in (('kernel_att', kernel_att, 7), ('head', head, 4), ('kernel_conv', kernel_conv, 3), ('stride', stride, 1),
+                                ('dilation', dilation, 1)):
+            if got != want:
+                raise NotImplementedError(f'ACmix({in_planes}, {out_planes}, {name}={got}): only {name}={want}, the reference\'s default, is on '
+                                          f'the SOMI path')
+        self.in_planes, self.out_planes, self.head, self.kernel_att, self.kernel_conv = in_planes, out_planes, head, kernel_att, kernel_conv
+        self.stride, self.dilation = stride, dilation
+        self.rate1 = nn.Parameter(torch.Tensor(1))
+        self.rate2 = nn.Parameter(torch.Tensor(1))
+        self.head_dim = out_planes // head
+        self.conv1 = nn.Conv2d(in_planes, out_planes, kernel_size=1)
+        self.conv2 = nn.Conv2d(in_planes, out_planes, kernel_size=1)
+        self.conv3 = nn.Conv2d(in_planes, out_planes, kernel_size=1)
+        self.conv_p = nn.Conv2d(2, self.head_dim, kernel_size=1)
+        self.padding_att = (dilation * (kernel_att - 1) + 1) // 2
+        self.fc = nn.Conv2d(3 * head, kernel_conv * kernel_conv, kernel_size=1, bias=False)
+        self.dep_conv = nn.Conv2d(kernel_conv * kernel_conv * self.head_dim, out_planes, kernel_size=kernel_conv, bias=True,
+                                  groups=self.head_dim, padding=1, stride=stride)
+        self.reset_parameters()
+
+    accumulates, folds_pooled, reduction = False, False, 1       # takes dx_out / accumulate, not walked that way
+
+    def reset_parameters(self):
+        """models/common.py:7313-7321: rates 0.5, dep_conv.weight the shift kernel (tap i of input i), dep_conv.bias removed."""
+        self.rate1.data.fill_(0.5)
+        self.rate2.data.fill_(0.5)
+        k = self.kernel_conv
+        kernel = torch.zeros(k * k, k, k)
+        for i in range(k * k):
+            kernel[i, i // k, i % k] = 1.
+        self.dep_conv.weight = nn.Parameter(kernel.repeat(self.out_planes, 1, 1, 1), requires_grad=True)
+        self.dep_conv.bias = None
+
+    def _pack(self, dev):
+        c1, c2 = self.in_planes, self.out_planes
+        w = torch.cat([m.weight.detach().float() for m in (self.conv1, self.conv2, self.conv3)], 0)
+        bdep = self.dep_conv.bias
+        pk = dict(w=pack_conv_weight(w).to(dev), b=torch.cat([_f32dev(m.bias, dev) for m in (self.conv1, self.conv2, self.conv3)]),
+                  wp=_f32dev(self.conv_p.weight, dev).view(self.head_dim, 2), rate1=_f32dev(self.rate1, dev), rate2=_f32dev(self.rate2, dev),
+                  fc=_f32dev(self.fc.weight, dev).view(9, 12), dep=_f32dev(self.dep_conv.weight, dev),
+                  bdep=torch.zeros(c2, device=dev) if bdep is None else _f32dev(bdep, dev))
+        pk['weff'] = ops.acmix_fold_weff(pk['fc'], pk['dep'], c2)
+        if self.training:
+            pk['wt'] = pack_dgrad_weight(w).to(dev)
+        return pk
+
+    def _check(self, x):
+        c1, c2 = self.in_planes, self.out_planes
+        if x.c != c1 or x.up:
+            raise NotImplementedError(f'ACmix({c1}, {c2}) takes a real map of {c1} channels, got {x.c}')
+        if c2 % 16 or c2 > 1024:
+            raise NotImplementedError(f'ACmix with {c2} output channels is not on the SOMI path: 4 heads of a multiple of 4 channels '
+                                      f'(out_planes % 16 == 0), at most 1024')
+        B, H, W, _ = x.shape
+        if H <= self.padding_att or W <= self.padding_att:        # nn.ReflectionPad2d(3), models/common.py:7302, 7343
+            raise RuntimeError(f'Padding size should be less than the corresponding input dimension, but got: padding ({self.padding_att}, '
+                               f'{self.padding_att}) at dimension {3 if W <= self.padding_att else 2} of input {[B * 4, c2 // 4, H, W]} '
+                               f'(ACmix\'s ReflectionPad2d({self.padding_att}), models/common.py:7302)')
+        if not x.t.is_cuda:
+            raise RuntimeError('somi_amd ACmix runs on the MI355X only (no CPU fallback)')
+        return c1, c2
+
+    def forward(self, x, out=None):
+        """x: the input map (Act); out: the Act to write (a new one when None)."""
+        c1, c2 = self._check(x)
+        pk = self._packed(x.t.device)
+        B, H, W, _ = x.shape
+        qkv = ops.conv2d_nhwc(x.t, pk['w'], pk['b'], kh=1, kw=1, cin=pad4(c1), x_coff=x.coff, cout=3 * c2)
+        mix = ops.acmix_conv(qkv, c2, pk['weff'], pk['bdep'])
+        if out is None:
+            out = new_act(x.t, H, W, c2)
+            if out.t.shape[3] != c2:
+                out.t.zero_()                                     # pad channels of a tensor of its own
+        _, lse = ops.acmix_attn(qkv, c2, pk['wp'], pk['rate1'], pk['rate2'], mix=mix, out=out.t, o_coff=out.coff, want_lse=self.training)
+        if self.training:
+            self.__dict__['_ctx'] = (x, qkv, mix, lse, pk)
+        return Act(out.t, out.coff, c2)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """dout: the gradient of the output.  -> the gradient of x as an Act (None without need_dx): a padded tensor of its own when dx_out is
+        None, else written into dx_out, added to it with `accumulate`.  Parameter gradients into .grad."""
+        x, qkv, mix, lse, pk = self.__dict__.pop('_ctx')
+        c1, c2, D = self.in_planes, self.out_planes, self.head_dim
+        c1p = pad4(c1)
+        B, H, W, _ = x.shape
+        dev = x.t.device
+        dqkv = torch.empty_like(qkv)
+        ops.acmix_conv_backward_data(dout.t, c2, pk['weff'], pk['rate2'], dqkv, do_coff=dout.coff)
+        _, aux, dwp, drates = ops.acmix_attn_backward_q(dout.t, qkv, c2, pk['wp'], pk['rate1'], pk['rate2'], lse, do_coff=dout.coff, mix=mix,
+                                                        dq=dqkv, dq_coff=0, accumulate=True)
+        ops.acmix_attn_backward_kv(dout.t, qkv, c2, pk['wp'], pk['rate1'], pk['rate2'], lse, aux, do_coff=dout.coff, dk=dqkv, dk_coff=c2,
+                                   dv=dqkv, dv_coff=2 * c2, accumulate=True)
+        dweff, dbdep = ops.acmix_conv_backward_weight(dout.t, qkv, c2, pk['rate2'], do_coff=dout.coff)
+        dfc, ddep = ops.acmix_split_dweff(dweff, pk['fc'], pk['dep'], c2)
+        _acc_grad(self.rate1, drates[0:1])
+        _acc_grad(self.rate2, drates[1:2])
+        _acc_grad(self.conv_p.weight, dwp.view(D, 2, 1, 1))
+        _acc_grad(self.conv_p.bias, torch.zeros(D, device=dev))   # only differences of pe enter the scores
+        _acc_grad(self.fc.weight, dfc.view(9, 12, 1, 1))
+        _acc_grad(self.dep_conv.weight, ddep)
+        if self.dep_conv.bias is not None:
+            _acc_grad(self.dep_conv.bias, dbdep)
+        # the stacked projection: a plain 1x1 conv c1 -> 3 c2 with bias
+        dw = ops.conv2d_wgrad_nhwc(x.t, dqkv, kh=1, kw=1, cin=c1p, x_coff=x.coff, cout=3 * c2)
+        db = torch.zeros(3 * c2, device=dev)
+        ops.chan_sum_(dqkv, 3 * c2, 0, db)
+        for i, m in enumerate((self.conv1, self.conv2, self.conv3)):
+            _acc_grad(m.weight, dw[i * c2:(i + 1) * c2, :c1].reshape(c2, c1, 1, 1))
+            _acc_grad(m.bias, db[i * c2:(i + 1) * c2])
+        if not need_dx:
+            return None
+        if dx_out is None:
+            dx_out = Act(torch.empty(B, H, W, c1p, device=dev, dtype=torch.float32), 0, c1)
+            accumulate = False
+        ops.conv2d_dgrad_nhwc(dqkv, pk['wt'], B=B, H=H, W=W, cin=c1p, kh=1, kw=1, cout=3 * c2, out=dx_out.t, dx_coff=dx_out.coff,
+                              accumulate=dx_out.t if accumulate else None, acc_coff=dx_out.coff)
+        return Act(dx_out.t, dx_out.coff, c1)
+
+
 class _ConvNormAct(Conv):
     """The reference's ConvNormAct (models/common.py:5387-5406) at what iRMB_EMA builds of it: conv (no bias) -> BatchNorm -> activation, the
     children named `conv` and `norm`.  Runs as Conv does; `bn` is `norm` under Conv's name."""

@@ -258,6 +258,28 @@ def yolov5_ema_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c2f'):
     return cfg
 
 
+def yolov5_acmix_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='row'):
+    """yolov5s 6.0 with ACmix (models/common.py:7281-7365), which the reference registers in its parser with a scaled width (models/yolo.py:
+    1496-1501) but names in no yaml it ships.  where='row': a [-1, 1, 'ACmix', [1024]] row behind SPPF as row 10, the head's absolute indices
+    one up; where='p3': a [-1, 1, 'ACmix', [256]] row behind the P3 head C3 (row 17) as row 18 - the rows behind it move one down, the next Conv
+    reads the new row and Detect reads [18, 21, 24]."""
+    if where not in ('row', 'p3'):
+        raise ValueError(f"where must be 'row' or 'p3', got {where!r}")
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    if where == 'row':
+        cfg['backbone'].append([-1, 1, 'ACmix', [1024]])
+        for row in cfg['head']:
+            if isinstance(row[0], list):
+                row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+        return cfg
+    at = 18 - len(cfg['backbone'])                                # head position of the new row 18
+    cfg['head'].insert(at, [-1, 1, 'ACmix', [256]])
+    for row in cfg['head'][at + 1:]:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 17 else j for j in row[0]]
+    return cfg
+
+
 def yolov5_context_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='aspp'):
     """yolov5s 6.0 with the dilated-convolution context blocks (ASPP, models/common.py:1829-1843; C2f_DWR, :7431-7511).  The reference registers
     both in its parser (models/yolo.py:1472-1492, C2f_DWR among the modules repeated inside) but ships no yaml that names them.  where='aspp': a

@@ -20,7 +20,8 @@ channels at strides 1 : 1/2 : 1/4) and `attention_model` (two inputs of args[0] 
 pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repeated inside); and the large-kernel depthwise blocks `CNeB`
 (repeated inside), `ConvMix` and `CSPCM` (n > 1 a Repeat of whole modules; a `ConvMix` row must name the channels behind it, which it passes
 through); and efficient multi-scale attention: `EMA`, `iRMB_EMA`, `iRMB_EMABottleneck` and `C2f_iRMB_EMA` rows, built from the yaml
-arguments as written (the reference's generic branch), which must name the width of their input.
+arguments as written (the reference's generic branch), which must name the width of their input; and `ACmix`, self-attention mixed with
+convolution, width-scaled like Conv (models/yolo.py:1496-1501).
 """
 import math
 from copy import deepcopy
@@ -94,6 +95,12 @@ def parse_model(d, ch):
                                           f'(c1, c2) (models/yolo.py:1487-1490, 1650), so its second block gets {c2} channels where it expects {c1}')
         elif name == 'ODConv_3rd':
             m = B.ODConv_3rd
+            c1, c2 = ch[f], args[0]
+            if c2 != no:
+                c2 = make_divisible(c2 * gw, 8)
+            args = [c1, c2, *args[1:]]
+        elif name == 'ACmix':                                     # models/yolo.py:1496-1501
+            m = B.ACmix
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)

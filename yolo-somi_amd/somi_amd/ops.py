@@ -645,6 +645,169 @@ def ema_backward_norm(x, sg, dw, vec, bvec, c, factor, gamma, beta, x_coff=0, *,
     return dt, dw, dsg
 
 
+# ---------------------------------------------------------------------------------------------- ACmix (acmix.hip)
+ACMIX_AUX = 24          # floats per pixel acmix_attn_backward_q leaves for acmix_attn_backward_kv (AC_AUX of acmix.hip)
+
+
+def acmix_plan(H, W):
+    """-> (tile, tiles_y, tiles_x): the square pixel tile a workgroup of the attention kernels owns and their count per image (host arithmetic)."""
+    t, ny, nx = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.lib().somi_acmix_plan(int(H), int(W), C.byref(t), C.byref(ny), C.byref(nx)), 'acmix_plan')
+    return t.value, ny.value, nx.value
+
+
+def _acmix_desc(qkv, c, what, workspace=False):
+    """qkv: (tensor, q_coff, k_coff, v_coff) or None.  -> (desc, workspace tensor or None)."""
+    d = _lib.AcmixDesc()
+    t = qkv[0]
+    B, H, W, _ = t.shape
+    d.B, d.H, d.W, d.C = B, H, W, c
+    if len(qkv) == 4:
+        d.q, d.k, d.v = _slice(t, qkv[1]), _slice(t, qkv[2]), _slice(t, qkv[3])
+    ws = None
+    if workspace:
+        ws = torch.empty(max(_lib.lib().somi_acmix_workspace_floats(B, H, W, c), 4), device=t.device, dtype=torch.float32)
+        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return d, ws
+
+
+def _acmix_qkv(qkv, c):
+    """A (B,H,W,.) tensor holding q, k, v side by side from channel `coff` -> (tensor, q_coff, k_coff, v_coff); or the 4-tuple itself."""
+    if isinstance(qkv, torch.Tensor):
+        return qkv, 0, c, 2 * c
+    if len(qkv) == 2:
+        return qkv[0], qkv[1], qkv[1] + c, qkv[1] + 2 * c
+    return tuple(qkv)
+
+
+def _acmix_small(t, n, what):
+    if t.numel() != n:
+        raise RuntimeError(f'{what} holds {t.numel()} values, {n} are expected')
+    return _ptr(_f32c(t))
+
+
+def acmix_fold_weff(fc_w, dep_w, c):
+    """fc.weight (9, 12[, 1, 1]) and dep_conv.weight (c, 9, 3, 3) -> weff (12, 9, c / 4, 4): dep_conv(fc(.)) as one grouped 3x3 conv."""
+    weff = torch.empty(12, 9, c // 4, 4, device=fc_w.device, dtype=torch.float32)
+    _ema_check(_lib.lib().somi_acmix_fold_weff_f32(_acmix_small(fc_w, 108, 'fc.weight'), _acmix_small(dep_w, c * 81, 'dep_conv.weight'), _ptr(weff),
+                                                   int(c), _stream()), 'acmix_fold_weff')
+    return weff
+
+
+def acmix_split_dweff(dweff, fc_w, dep_w, c):
+    """The gradient of weff -> (dfc (9, 12), ddep (c, 9, 3, 3))."""
+    dfc = torch.empty(9, 12, device=dweff.device, dtype=torch.float32)
+    ddep = torch.empty(c, 9, 3, 3, device=dweff.device, dtype=torch.float32)
+    _ema_check(_lib.lib().somi_acmix_split_dweff_f32(_acmix_small(dweff, 108 * c, 'dweff'), _acmix_small(fc_w, 108, 'fc.weight'),
+                                                     _acmix_small(dep_w, c * 81, 'dep_conv.weight'), _ptr(dfc), _ptr(ddep), int(c), _stream()),
+               'acmix_split_dweff')
+    return dfc, ddep
+
+
+def acmix_conv(qkv, c, weff, bias, *, out=None, o_coff=0):
+    """The conv half: mix[., 4 d + o] = bias + the grouped 3x3 conv of the 12 sources (q, k, v heads) of dim d with weff (acmix_fold_weff)."""
+    qkv = _acmix_qkv(qkv, c)
+    B, H, W, _ = qkv[0].shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=qkv[0].device, dtype=torch.float32)
+    d, _ = _acmix_desc(qkv, c, 'acmix_conv')
+    d.mix = _slice(_ema_map(out, qkv[0], 'acmix_conv'), o_coff)
+    d.weff, d.bias = _acmix_small(weff, 108 * c, 'weff'), _acmix_small(bias, c, 'bias')
+    _ema_check(_lib.lib().somi_acmix_conv_nhwc_f32(C.byref(d), _stream()), 'acmix_conv')
+    return out
+
+
+def acmix_attn(qkv, c, wp, rate1, rate2, *, mix=None, mix_coff=0, out=None, o_coff=0, lse=None, lse_coff=0, want_lse=False):
+    """out = rate1 * the 7x7 reflected-window attention of q, k, v (4 heads, position term from wp (c / 4, 2)) [+ rate2 * mix].
+    -> (out, lse): lse (B, H, W, 4), the per (pixel, head) log-sum-exp, with want_lse or a given lse."""
+    qkv = _acmix_qkv(qkv, c)
+    x = qkv[0]
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if lse is None and want_lse:
+        lse = torch.empty(B, H, W, 4, device=x.device, dtype=torch.float32)
+    d, _ = _acmix_desc(qkv, c, 'acmix_attn')
+    d.out = _slice(_ema_map(out, x, 'acmix_attn'), o_coff)
+    if mix is not None:
+        d.mix = _slice(_ema_map(mix, x, 'acmix_attn'), mix_coff)
+    if lse is not None:
+        d.lse = _slice(_ema_map(lse, x, 'acmix_attn'), lse_coff)
+    d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
+    _ema_check(_lib.lib().somi_acmix_attn_nhwc_f32(C.byref(d), _stream()), 'acmix_attn')
+    return out, lse
+
+
+def acmix_attn_backward_q(dout, qkv, c, wp, rate1, rate2, lse, *, do_coff=0, lse_coff=0, mix=None, mix_coff=0, dq=None, dq_coff=0,
+                          accumulate=False, aux=None, aux_coff=0):
+    """The query-centred backward.  -> (dq, aux, dwp (c / 4, 2), drates (2,): sum dout . att, sum dout . mix); dq added to with `accumulate`."""
+    qkv = _acmix_qkv(qkv, c)
+    x = qkv[0]
+    B, H, W, _ = x.shape
+    if dq is None:
+        if accumulate:
+            raise RuntimeError('acmix_attn_backward_q: accumulate needs the tensor to add to')
+        dq = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
+    if aux is None:
+        aux = torch.empty(B, H, W, ACMIX_AUX, device=x.device, dtype=torch.float32)
+    dwp = torch.empty(c // 4, 2, device=x.device, dtype=torch.float32)
+    drates = torch.empty(2, device=x.device, dtype=torch.float32)
+    d, ws = _acmix_desc(qkv, c, 'acmix_attn_backward_q', workspace=True)     # noqa: F841  (ws alive until the launch is enqueued)
+    d.out, d.lse = _slice(_ema_map(dout, x, 'acmix_attn_backward_q'), do_coff), _slice(_ema_map(lse, x, 'acmix_attn_backward_q'), lse_coff)
+    d.aux, d.dq = _slice(_ema_map(aux, x, 'acmix_attn_backward_q'), aux_coff), _slice(_ema_map(dq, x, 'acmix_attn_backward_q'), dq_coff)
+    if mix is not None:
+        d.mix = _slice(_ema_map(mix, x, 'acmix_attn_backward_q'), mix_coff)
+    d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
+    d.dwp, d.drates, d.accumulate = _ptr(dwp), _ptr(drates), int(accumulate)
+    _ema_check(_lib.lib().somi_acmix_attn_bwd_q_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_q')
+    return dq, aux, dwp, drates
+
+
+def acmix_attn_backward_kv(dout, qkv, c, wp, rate1, rate2, lse, aux, *, do_coff=0, lse_coff=0, aux_coff=0, dk=None, dk_coff=0, dv=None,
+                           dv_coff=0, accumulate=False):
+    """The key-centred backward (after acmix_attn_backward_q, whose aux it reads).  -> (dk, dv), added to with `accumulate`."""
+    qkv = _acmix_qkv(qkv, c)
+    x = qkv[0]
+    B, H, W, _ = x.shape
+    if (dk is None or dv is None) and accumulate:
+        raise RuntimeError('acmix_attn_backward_kv: accumulate needs the tensors to add to')
+    dk = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dk is None else dk
+    dv = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dv is None else dv
+    d, _ = _acmix_desc(qkv, c, 'acmix_attn_backward_kv')
+    d.out, d.lse = _slice(_ema_map(dout, x, 'acmix_attn_backward_kv'), do_coff), _slice(_ema_map(lse, x, 'acmix_attn_backward_kv'), lse_coff)
+    d.aux = _slice(_ema_map(aux, x, 'acmix_attn_backward_kv'), aux_coff)
+    d.dk, d.dv = _slice(_ema_map(dk, x, 'acmix_attn_backward_kv'), dk_coff), _slice(_ema_map(dv, x, 'acmix_attn_backward_kv'), dv_coff)
+    d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
+    d.accumulate = int(accumulate)
+    _ema_check(_lib.lib().somi_acmix_attn_bwd_kv_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_kv')
+    return dk, dv
+
+
+def acmix_conv_backward_data(dout, c, weff, rate2, dqkv, *, do_coff=0, accumulate=False):
+    """dq, dk, dv = rate2 * the transposed grouped conv of dout, into dqkv = (tensor, q_coff, k_coff, v_coff) (or a tensor holding them side by
+    side), added to with `accumulate`."""
+    dqkv = _acmix_qkv(dqkv, c)
+    d, _ = _acmix_desc((dqkv[0],), c, 'acmix_conv_backward_data')
+    d.out = _slice(_ema_map(dout, dqkv[0], 'acmix_conv_backward_data'), do_coff)
+    d.dq, d.dk, d.dv = _slice(dqkv[0], dqkv[1]), _slice(dqkv[0], dqkv[2]), _slice(dqkv[0], dqkv[3])
+    d.weff, d.rate2, d.accumulate = _acmix_small(weff, 108 * c, 'weff'), _acmix_small(rate2, 1, 'rate2'), int(accumulate)
+    _ema_check(_lib.lib().somi_acmix_conv_bwd_data_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_data')
+    return dqkv[0]
+
+
+def acmix_conv_backward_weight(dout, qkv, c, rate2, *, do_coff=0):
+    """-> (dweff (12, 9, c / 4, 4), dbias (c,)): rate2 * the sums over the map, partials folded in a fixed order."""
+    qkv = _acmix_qkv(qkv, c)
+    x = qkv[0]
+    dweff = torch.empty(12, 9, c // 4, 4, device=x.device, dtype=torch.float32)
+    dbias = torch.empty(c, device=x.device, dtype=torch.float32)
+    d, ws = _acmix_desc(qkv, c, 'acmix_conv_backward_weight', workspace=True)     # noqa: F841
+    d.out = _slice(_ema_map(dout, x, 'acmix_conv_backward_weight'), do_coff)
+    d.rate2, d.dweff, d.dbias = _acmix_small(rate2, 1, 'rate2'), _ptr(dweff), _ptr(dbias)
+    _ema_check(_lib.lib().somi_acmix_conv_bwd_weight_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_weight')
+    return dweff, dbias
+
+
 # ---------------------------------------------------------------------------------------------- SimAM (simam.hip)
 SIMAM_MAX_COVER = 4     # regions over one pixel along an axis (SA_COVER of simam.hip)
 
