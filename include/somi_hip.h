@@ -1233,7 +1233,18 @@ int somi_repulsion_loss_f32(const float *pbox, const float *gtbox, const uint8_t
  * Weighted boxes fusion (wbf.py:68 -> ensemble_boxes.weighted_boxes_fusion, conf_type 'avg').
  * boxes (n,4) xyxy in [0,1], scores (n), labels (n) int32, model (n) int32, already concatenated over models
  * in model order; out_* sized n; out_count 1 int32.  One launch per image; sequential per label by design.
+ *
+ * Float32 contract: weights, iou_thr and skip_box_thr are float32 values.  The kernel widens them exactly and from there on compares and
+ * multiplies in float64 as the package does, so the result equals the package's called with those float32 values (a weight such as 0.7
+ * is the float32 nearest to 0.7, not the double; callers that hold doubles round them first - somi_amd.wbf does).  `score < skip_box_thr`
+ * drops a box and `iou > iou_thr` joins a cluster, both strict, at the float32 values.
+ *
+ * Labels: integers in [0, SOMI_WBF_MAX_LABELS).  A label outside that range is never dropped silently: if any of an image's n member rows
+ * carries one (whether or not the row would pass the score and area filters), the image is not fused, its out_count is SOMI_WBF_BAD_LABEL
+ * and its out_boxes / out_scores / out_labels rows are not written.  Rows at and beyond out_count are never written either.
  */
+#define SOMI_WBF_MAX_LABELS 128  /* label capacity of one image (static LDS tables); the largest nc the repository's configs build is 80 */
+#define SOMI_WBF_BAD_LABEL  (-1) /* out_count of an image that holds a label outside [0, SOMI_WBF_MAX_LABELS) */
 size_t somi_wbf_workspace_bytes(int n);
 int somi_wbf_f32(const float *boxes, const float *scores, const int32_t *labels, const int32_t *model, int n,
                  int n_models, const float *weights_host, float iou_thr, float skip_box_thr, float *out_boxes,
@@ -1243,7 +1254,10 @@ int somi_wbf_f32(const float *boxes, const float *scores, const int32_t *labels,
  * det[t] (B,max_det,6) [x1,y1,x2,y2,conf,cls] in pixels and count[t] (B) are somi_nms_f32's outputs for model t (host arrays of
  * n_models device pointers).  Image b's members are model 0's rows, then model 1's, ... (the order wbf.py:44-59 appends them in),
  * boxes divided by (img_w, img_h) and clipped to [0,1].  Outputs are strided per image by N = n_models * max_det:
- * out_boxes (B,N,4), out_scores (B,N), out_labels (B,N), out_count (B).  Same arithmetic as somi_wbf_f32, image by image.
+ * out_boxes (B,N,4), out_scores (B,N), out_labels (B,N), out_count (B).  Same arithmetic as somi_wbf_f32, image by image, under the same
+ * float32 contract (img_w and img_h are float32 too; the division is a true float32 division).  count[t][b] is clamped to [0, max_det].
+ * The class column is truncated to int32; an image with a class outside [0, SOMI_WBF_MAX_LABELS) among its counted rows gets
+ * out_count[b] = SOMI_WBF_BAD_LABEL and unwritten output rows, the other images of the batch are fused as usual.  No host synchronisation.
  */
 size_t somi_wbf_batch_workspace_bytes(int B, int max_det, int n_models);
 int somi_wbf_batch_f32(const float *const *det, const int32_t *const *count, int B, int max_det, int n_models,

@@ -4,11 +4,16 @@
 // waves take labels in turn.  Arithmetic follows the package bit for bit: member boxes and scores in float64, the
 // running fused box in a float32 accumulator re-rounded after every member (its accumulator is a float32 numpy array),
 // IoU in float64, ties in both sorts resolved as `argsort(stable)[::-1]` does (later element first).
+// weights, iou_thr and skip_box_thr arrive as float32 (the ABI) and are widened exactly; every comparison and product after
+// that is the package's float64 one, so the result is the package's for those float32 values.
+// Labels index LDS tables of SOMI_WBF_MAX_LABELS entries; an image with a label outside [0, SOMI_WBF_MAX_LABELS) is not fused:
+// its out_count is SOMI_WBF_BAD_LABEL and its output rows are left alone.
 #include "common.h"
 
 namespace somi {
 
-constexpr int WBF_MAX_LABELS = 64;
+constexpr int WBF_MAX_LABELS = SOMI_WBF_MAX_LABELS;
+static_assert(WBF_MAX_LABELS <= 256, "one thread per label orders the labels");
 
 struct WbfArgs {
     const float *boxes, *scores;
@@ -37,12 +42,13 @@ __device__ __forceinline__ void wbf_image(const WbfArgs &a) {
     __shared__ int lab_start[WBF_MAX_LABELS];      // start of each label's group in `order` (indexed by label)
     __shared__ int clu_start[WBF_MAX_LABELS];      // start of each label's clusters (indexed by label) == lab_start
     __shared__ int clu_cnt[WBF_MAX_LABELS];
-    __shared__ int nlab_sh, ntot_sh;
+    __shared__ int nlab_sh, ntot_sh, bad_sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
     double wsum_all = 0.0;
     for (int t = 0; t < a.n_models; ++t) wsum_all += (double)a.weights[t];
     for (int i = tid; i < WBF_MAX_LABELS; i += 256) { first_idx[i] = 0x7FFFFFFF; lab_cnt[i] = 0; clu_cnt[i] = 0; }
+    if (tid == 0) { nlab_sh = 0; bad_sh = 0; }
     __syncthreads();
     // ---- A. prefilter (ensemble_boxes: score < thr dropped, corners ordered and clipped, zero area dropped)
     for (int i = tid; i < n; i += 256) {
@@ -54,26 +60,30 @@ __device__ __forceinline__ void wbf_image(const WbfArgs &a) {
         x1 = clip01(x1); y1 = clip01(y1); x2 = clip01(x2); y2 = clip01(y2);
         if ((x2 - x1) * (y2 - y1) == 0.0) ok = 0;
         const int lab = a.labels[i];
-        if (lab < 0 || lab >= WBF_MAX_LABELS) ok = 0;
+        if (lab < 0 || lab >= WBF_MAX_LABELS) { ok = 0; bad_sh = 1; }      // no row may vanish silently: the image is refused below
         const double w = (double)a.weights[a.model[i]];
         a.mx1[i] = x1; a.my1[i] = y1; a.mx2[i] = x2; a.my2[i] = y2;
         a.msc[i] = (double)sc * w; a.mwt[i] = w; a.mlab[i] = lab; a.mvalid[i] = ok;
         if (ok) { atomicMin(&first_idx[lab], i); atomicAdd(&lab_cnt[lab], 1); }
     }
     __syncthreads();
-    // ---- B. label sequence in first-appearance order (dict insertion order of the package), group offsets
+    if (bad_sh) {                                   // the same for every thread of the workgroup
+        if (tid == 0) *a.out_count = SOMI_WBF_BAD_LABEL;
+        return;
+    }
+    // ---- B. label sequence in first-appearance order (dict insertion order of the package), group offsets.  One thread per label:
+    // a present label's place is the number of present labels seen earlier (first indices are distinct), so thread 0 only walks the sums
+    if (tid < WBF_MAX_LABELS && lab_cnt[tid]) {
+        const int mine = first_idx[tid];
+        int rank = 0;
+        for (int l = 0; l < WBF_MAX_LABELS; ++l) rank += first_idx[l] < mine ? 1 : 0;   // absent labels hold INT_MAX
+        lab_seq[rank] = tid;
+        atomicAdd(&nlab_sh, 1);
+    }
+    __syncthreads();
     if (tid == 0) {
-        int nl = 0;
-        for (int l = 0; l < WBF_MAX_LABELS; ++l) if (lab_cnt[l]) lab_seq[nl++] = l;
-        for (int i = 1; i < nl; ++i) {               // insertion sort by first index (<= 64 labels)
-            const int v = lab_seq[i];
-            int j = i - 1;
-            while (j >= 0 && first_idx[lab_seq[j]] > first_idx[v]) { lab_seq[j + 1] = lab_seq[j]; --j; }
-            lab_seq[j + 1] = v;
-        }
         int run = 0;
-        for (int i = 0; i < nl; ++i) { lab_start[lab_seq[i]] = run; clu_start[lab_seq[i]] = run; run += lab_cnt[lab_seq[i]]; }
-        nlab_sh = nl;
+        for (int i = 0; i < nlab_sh; ++i) { lab_start[lab_seq[i]] = run; clu_start[lab_seq[i]] = run; run += lab_cnt[lab_seq[i]]; }
     }
     __syncthreads();
     // ---- C. rank inside the label: descending score, ties -> later member first (argsort(stable)[::-1])

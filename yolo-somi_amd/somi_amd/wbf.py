@@ -3,6 +3,15 @@ weights, iou_thr, skip_box_thr; conf_type 'avg'), executed by somi_wbf_f32 on th
 
 Inputs per model: boxes (n_t,4) xyxy normalised to [0,1], scores (n_t), labels (n_t).  Returns numpy arrays
 (boxes (n,4), scores (n), labels (n)) sorted by descending score, as the package does.
+
+Float32 contract (include/somi_hip.h): `weights`, `iou_thr` and `skip_box_thr` cross the C ABI as float32, so they are rounded to
+float32 here and the result equals the package's called with those rounded values, e.g. with
+`[float(np.float32(w)) for w in weights]`; a weight like 0.7 is not a float32 and the package run on the double can differ in
+the last bits.  Boxes and scores are float32 too; `score < skip_box_thr` drops and `iou > iou_thr` joins, both strict.
+
+Labels are integers in [0, MAX_LABELS) (SOMI_WBF_MAX_LABELS).  A label outside is never dropped silently: `weighted_boxes_fusion`
+raises ValueError before anything is launched; `weighted_boxes_fusion_batch`, whose labels live on the device, marks the image
+with count BAD_LABEL (-1) and leaves its output rows unwritten.
 """
 import ctypes as C
 
@@ -12,6 +21,9 @@ import torch
 from . import _lib
 from ._lib import check
 from .ops import _ptr, _stream
+
+MAX_LABELS = 128         # SOMI_WBF_MAX_LABELS of include/somi_hip.h
+BAD_LABEL = -1           # SOMI_WBF_BAD_LABEL: the count of an image that holds a label outside [0, MAX_LABELS)
 
 
 def weighted_boxes_fusion(boxes_list, scores_list, labels_list, weights=None, iou_thr=0.55, skip_box_thr=0.0,
@@ -30,6 +42,8 @@ def weighted_boxes_fusion(boxes_list, scores_list, labels_list, weights=None, io
         l = torch.as_tensor(np.asarray(labels_list[t])).reshape(-1).to(torch.int32)
         if not (len(b) == len(s) == len(l)):
             raise ValueError('boxes / scores / labels length mismatch')
+        if len(l) and (int(l.min()) < 0 or int(l.max()) >= MAX_LABELS):
+            raise ValueError(f'model {t}: labels have to lie in [0, {MAX_LABELS}) (SOMI_WBF_MAX_LABELS), got {int(l.min())}..{int(l.max())}')
         bs.append(b), ss.append(s), ls.append(l), ms.append(torch.full((len(b),), t, dtype=torch.int32))
     boxes, scores = torch.cat(bs).to(device).contiguous(), torch.cat(ss).to(device).contiguous()
     labels, model = torch.cat(ls).to(device).contiguous(), torch.cat(ms).to(device).contiguous()
@@ -47,13 +61,17 @@ def weighted_boxes_fusion(boxes_list, scores_list, labels_list, weights=None, io
     check(L.somi_wbf_f32(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(model), n, nm, w, float(iou_thr), float(skip_box_thr),
                          _ptr(ob), _ptr(osc), _ptr(ol), _ptr(cnt), _ptr(ws), nbytes, _stream()), 'weighted_boxes_fusion')
     k = int(cnt.item())
+    if k < 0:
+        raise ValueError(f'a label outside [0, {MAX_LABELS}) reached the kernel')
     return ob[:k].cpu().numpy(), osc[:k].cpu().numpy(), ol[:k].cpu().numpy().astype(np.float64)
 
 
 def weighted_boxes_fusion_batch(dets, counts, img_size, weights=None, iou_thr=0.55, skip_box_thr=0.0):
     """wbf.py:44-68 for a whole batch on the device.  dets[t] (B, max_det, 6) / counts[t] (B) = nms.non_max_suppression_raw of model t
     (pixels); img_size = (width, height) the boxes are normalised by.  Returns device tensors (boxes (B,N,4) in [0,1], scores (B,N),
-    labels (B,N) int32, count (B) int32), N = len(dets) * max_det; row order per image = descending fused score.  No host sync."""
+    labels (B,N) int32, count (B) int32), N = len(dets) * max_det; row order per image = descending fused score.  No host sync.
+    counts are clamped to [0, max_det].  count[b] == BAD_LABEL (-1): image b holds a class outside [0, MAX_LABELS) among its counted
+    rows and was not fused (its rows are unwritten); the other images are unaffected.  weights, thresholds and img_size are float32."""
     nm = len(dets)
     if nm < 1 or nm != len(counts):
         raise ValueError('one (det, count) pair per model')
