@@ -110,10 +110,14 @@ typedef struct somi_conv_desc {
     /* Opt-in reduced precision of the products (train.py:263 `amp.autocast`; the default 0 is the exact fp32 path every parity claim is
      * made on): 1 = operands rounded to bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate - autocast's arithmetic), 2 = "bf16x3": each
      * operand split into two bf16 values and hi*hi + hi*lo + lo*hi accumulated in fp32 (~1e-5 relative error).  Tensors stay fp32 in
-     * HBM either way.  Honoured by the plain channel-aligned launches (Cin % 32 == 0, shared weights, no operand modulation) of
-     * somi_conv2d_nhwc_f32 / _dgrad_ / _wgrad_; every other launch computes in exact fp32 - among them the forward and the data gradient of
-     * a patch-embedding conv of more than 32 taps (kh == kw == stride >= 6, pad 0, dil 1: see somi_conv2d_nhwc_f32), whose instantiation
-     * has no reduced-precision form; its weight gradient honours `prec` like any other. */
+     * HBM either way.  Honoured by the launches that have a bf16 form: of somi_conv2d_nhwc_f32 / _dgrad_, the plain channel-aligned ones
+     * (operand channels % 32 == 0, at most 32 taps, no operand modulation; shared or per-sample weights) that plan an 8-wave tile, 128 x 128
+     * or 128 x 64 (somi_conv2d_kernel_name tells) - not the 4-wave tiles, 64 x 128 (more than 64 output channels on fewer than 32768 rows and 512
+     * tiles without the stream-K schedule: no workspace, per-sample weights, a data gradient at stride > 1) and 128 x 32 (at most 32 output
+     * channels); of somi_conv2d_wgrad_nhwc_f32, the shared-weight ones with kh * kw * Cin > 64 (a 128-column tile), at any Cin % 4 == 0.
+     * Every other launch computes in exact fp32, bit for bit what prec = 0 gives - among them the forward and the data gradient of a
+     * patch-embedding conv of more than 32 taps (kh == kw == stride >= 6, pad 0, dil 1: see somi_conv2d_nhwc_f32), whose instantiation has
+     * no reduced-precision form; its weight gradient honours `prec` like any other.  tests/test_conv_amp_gpu.py pins both halves. */
     int32_t prec;
 } somi_conv_desc;
 
