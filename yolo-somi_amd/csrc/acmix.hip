@@ -23,8 +23,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int AC_T = 8;                      // tile edge
 constexpr int AC_HALO = AC_T + 6;            // 14
 constexpr int AC_HP = AC_HALO * AC_HALO;     // 196 halo pixels
@@ -33,10 +31,8 @@ constexpr int AC_AUX = 24;                   // delta, qwx, qwy, gx, gy, 1 / sum
 constexpr int AC_WG_ROWS = 12 * 9 * 4;       // Weff values per d
 constexpr size_t AC_WGRAD_CAP = 4u << 20;    // floats of weight-gradient partials at most
 
-struct AcSl { float *p; int cs, coff; };
-
 struct AcArgs {
-    AcSl q, k, v, mix, out, lse, aux, dq, dk, dv;
+    somi_slice q, k, v, mix, out, lse, aux, dq, dk, dv;
     const float *wp, *rate1, *rate2, *weff, *bias;
     float *dwp, *drates, *dweff, *dbias, *part;
     int accumulate;
@@ -44,14 +40,11 @@ struct AcArgs {
     float scale;
 };
 
-__device__ __forceinline__ f32x4 ac_ld(const AcSl &s, long pix, int c) { return *reinterpret_cast<const f32x4 *>(s.p + pix * s.cs + s.coff + c); }
-__device__ __forceinline__ void ac_st(const AcSl &s, long pix, int c, f32x4 v) { *reinterpret_cast<f32x4 *>(s.p + pix * s.cs + s.coff + c) = v; }
-__device__ __forceinline__ float ac_dot(f32x4 a, f32x4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ int ac_refl(int i, int n) { return i < 0 ? -i : (i > n - 1 ? 2 * (n - 1) - i : i); }
 
 // the tile's halo of `src`, channels h * D + d0 + [0, 4 n4) of every head -> sm[(h * AC_DC4 + i4) * AC_HP + halo pixel]
 template <bool REFLECT>
-__device__ __forceinline__ void ac_stage(const AcArgs &a, const AcSl &src, f32x4 *sm, int b, int y0, int x0, int d0, int n4) {
+__device__ __forceinline__ void ac_stage(const AcArgs &a, const somi_slice &src, f32x4 *sm, int b, int y0, int x0, int d0, int n4) {
     const int per = 4 * n4, total = AC_HP * per;
     for (int i = threadIdx.x; i < total; i += 256) {
         const int hp = i / per, c = i - hp * per, h = c / n4, i4 = c - h * n4;
@@ -66,7 +59,7 @@ __device__ __forceinline__ void ac_stage(const AcArgs &a, const AcSl &src, f32x4
         } else {
             in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
         }
-        if (in) val = ac_ld(src, ((long)b * a.H + gy) * a.W + gx, h * a.D + d0 + 4 * i4);
+        if (in) val = ld4(at_ch(src, ((long)b * a.H + gy) * a.W + gx, h * a.D + d0 + 4 * i4));
         sm[(h * AC_DC4 + i4) * AC_HP + hp] = val;
     }
 }
@@ -98,7 +91,7 @@ __device__ __forceinline__ void ac_dots(const f32x4 *sm, const AcLane &l, const 
 #pragma unroll
         for (int jy = 0; jy < 7; ++jy)
 #pragma unroll
-            for (int jx = 0; jx < 7; ++jx) sc[jy * 7 + jx] += ac_dot(own[i4], row[jy * AC_HALO + jx]);
+            for (int jx = 0; jx < 7; ++jx) sc[jy * 7 + jx] += dot4(own[i4], row[jy * AC_HALO + jx]);
     }
 }
 
@@ -115,9 +108,9 @@ __device__ __forceinline__ void ac_gather(const f32x4 *sm, const AcLane &l, cons
     }
 }
 
-__device__ __forceinline__ void ac_own(const AcSl &s, const AcLane &l, int D, int d0, int n4, f32x4 (&o)[AC_DC4]) {
+__device__ __forceinline__ void ac_own(const somi_slice &s, const AcLane &l, int D, int d0, int n4, f32x4 (&o)[AC_DC4]) {
 #pragma unroll
-    for (int i4 = 0; i4 < AC_DC4; ++i4) o[i4] = (l.on && i4 < n4) ? ac_ld(s, l.pix, l.h * D + d0 + 4 * i4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i4 = 0; i4 < AC_DC4; ++i4) o[i4] = (l.on && i4 < n4) ? ld4(at_ch(s, l.pix, l.h * D + d0 + 4 * i4)) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // scores of the query at this lane over its reflected window: sc = s * (q . k_j + qwx * dx_j + qwy * dy_j); qwx / qwy returned
@@ -183,8 +176,8 @@ __global__ __launch_bounds__(256) void ac_attn_kernel(AcArgs a) {
                 if (i4 >= n4) break;
                 const int c = l.h * a.D + d0 + 4 * i4;
                 f32x4 o = r1 * acc[i4];
-                if (a.mix.p) o += r2 * ac_ld(a.mix, l.pix, c);
-                ac_st(a.out, l.pix, c, o);
+                if (a.mix.p) o += r2 * ld4(at_ch(a.mix, l.pix, c));
+                st4(at_ch_w(a.out, l.pix, c), o);
             }
         }
         __syncthreads();
@@ -232,7 +225,7 @@ __global__ __launch_bounds__(256) void ac_bwd_q_kernel(AcArgs a) {
         if (a.mix.p && l.on)
 #pragma unroll
             for (int i4 = 0; i4 < AC_DC4; ++i4)
-                if (i4 < n4) sums[1] += ac_dot(g[i4], ac_ld(a.mix, l.pix, l.h * a.D + d0 + 4 * i4));
+                if (i4 < n4) sums[1] += dot4(g[i4], ld4(at_ch(a.mix, l.pix, l.h * a.D + d0 + 4 * i4)));
         __syncthreads();
         if (l.on) ac_dots(sm, l, g, n4, e);
         __syncthreads();
@@ -271,8 +264,8 @@ __global__ __launch_bounds__(256) void ac_bwd_q_kernel(AcArgs a) {
                 const float *w = a.wp + 2 * (d0 + 4 * i4);
                 const f32x4 wx = {w[0], w[2], w[4], w[6]}, wy = {w[1], w[3], w[5], w[7]};
                 f32x4 o = a.scale * (acc[i4] + gx * wx + gy * wy);
-                if (a.accumulate) o += ac_ld(a.dq, l.pix, c);
-                ac_st(a.dq, l.pix, c, o);
+                if (a.accumulate) o += ld4(at_ch(a.dq, l.pix, c));
+                st4(at_ch_w(a.dq, l.pix, c), o);
             }
         }
         __syncthreads();
@@ -378,14 +371,14 @@ __global__ __launch_bounds__(256) void ac_bwd_kv_kernel(AcArgs a) {
             if (l.on) {
                 f32x4 acc[AC_DC4] = {};
                 if (pass) ac_gather(sm, l, e, n4, acc); else ac_gather(sm, l, sc, n4, acc);
-                const AcSl &dst = pass ? a.dk : a.dv;
+                const somi_slice &dst = pass ? a.dk : a.dv;
 #pragma unroll
                 for (int i4 = 0; i4 < AC_DC4; ++i4) {
                     if (i4 >= n4) break;
                     const int c = l.h * a.D + d0 + 4 * i4;
                     f32x4 o = acc[i4];
-                    if (a.accumulate) o += ac_ld(dst, l.pix, c);
-                    ac_st(dst, l.pix, c, o);
+                    if (a.accumulate) o += ld4(at_ch(dst, l.pix, c));
+                    st4(at_ch_w(dst, l.pix, c), o);
                 }
             }
             __syncthreads();
@@ -395,7 +388,7 @@ __global__ __launch_bounds__(256) void ac_bwd_kv_kernel(AcArgs a) {
 
 // ------------------------------------------------------------------------------------------------ the conv half
 // weff[((t * 9 + tap) * D + d) * 4 + o].  One lane per (image row, group of 4 columns, d), d fastest.
-__device__ __forceinline__ const AcSl &ac_src(const AcArgs &a, int t) { return t < 4 ? a.q : (t < 8 ? a.k : a.v); }
+__device__ __forceinline__ const somi_slice &ac_src(const AcArgs &a, int t) { return t < 4 ? a.q : (t < 8 ? a.k : a.v); }
 
 __global__ __launch_bounds__(256) void ac_conv_kernel(AcArgs a) {
     const int nxg = (a.W + 3) / 4;
@@ -404,10 +397,10 @@ __global__ __launch_bounds__(256) void ac_conv_kernel(AcArgs a) {
     const int d = (int)(i % a.D);
     const long r = i / a.D;
     const int xg = (int)(r % nxg), y = (int)((r / nxg) % a.H), b = (int)(r / nxg / a.H), x0 = xg * 4;
-    const f32x4 bias = *reinterpret_cast<const f32x4 *>(a.bias + 4 * d);
+    const f32x4 bias = ld4(a.bias + 4 * d);
     f32x4 acc[4] = {bias, bias, bias, bias};
     for (int t = 0; t < 12; ++t) {
-        const AcSl &s = ac_src(a, t);
+        const somi_slice &s = ac_src(a, t);
         const int c = (t & 3) * a.D + d;
         for (int ky = 0; ky < 3; ++ky) {
             const int yy = y + ky - 1;
@@ -420,7 +413,7 @@ __global__ __launch_bounds__(256) void ac_conv_kernel(AcArgs a) {
             }
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                const f32x4 w = *reinterpret_cast<const f32x4 *>(a.weff + (((long)t * 9 + ky * 3 + kx) * a.D + d) * 4);
+                const f32x4 w = ld4(a.weff + (((long)t * 9 + ky * 3 + kx) * a.D + d) * 4);
 #pragma unroll
                 for (int px = 0; px < 4; ++px) acc[px] += w * in[px + kx];
             }
@@ -428,7 +421,7 @@ __global__ __launch_bounds__(256) void ac_conv_kernel(AcArgs a) {
     }
 #pragma unroll
     for (int px = 0; px < 4; ++px)
-        if (x0 + px < a.W) ac_st(a.mix, ((long)b * a.H + y) * a.W + x0 + px, 4 * d, acc[px]);
+        if (x0 + px < a.W) st4(at_ch_w(a.mix, ((long)b * a.H + y) * a.W + x0 + px, 4 * d), acc[px]);
 }
 
 // dsrc_t[p][d] (+)= rate2 * sum_(tap, o) weff[t][tap][d][o] * dout[p - tap][4 d + o]
@@ -451,21 +444,21 @@ __global__ __launch_bounds__(256) void ac_conv_bwd_data_kernel(AcArgs a) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const int xx = x0 - 1 + k;
-            g[k] = (xx >= 0 && xx < a.W) ? ac_ld(a.out, ((long)b * a.H + yy) * a.W + xx, 4 * d) : f32x4{0.f, 0.f, 0.f, 0.f};
+            g[k] = (xx >= 0 && xx < a.W) ? ld4(at_ch(a.out, ((long)b * a.H + yy) * a.W + xx, 4 * d)) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
             for (int t = 0; t < 12; ++t) {
-                const f32x4 w = *reinterpret_cast<const f32x4 *>(a.weff + (((long)t * 9 + ky * 3 + kx) * a.D + d) * 4);
+                const f32x4 w = ld4(a.weff + (((long)t * 9 + ky * 3 + kx) * a.D + d) * 4);
 #pragma unroll
-                for (int px = 0; px < 4; ++px) acc[t][px] += ac_dot(w, g[px - kx + 2]);
+                for (int px = 0; px < 4; ++px) acc[t][px] += dot4(w, g[px - kx + 2]);
             }
     }
     const float r2 = a.rate2[0];
 #pragma unroll
     for (int t = 0; t < 12; ++t) {
-        const AcSl &s = t < 4 ? a.dq : (t < 8 ? a.dk : a.dv);
+        const somi_slice &s = t < 4 ? a.dq : (t < 8 ? a.dk : a.dv);
         const int c = (t & 3) * a.D + d;
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
@@ -480,7 +473,7 @@ __global__ __launch_bounds__(256) void ac_conv_bwd_data_kernel(AcArgs a) {
 __global__ __launch_bounds__(192) void ac_conv_bwd_weight_kernel(AcArgs a) {
     const int t = threadIdx.x >> 4, d = blockIdx.x * 16 + (threadIdx.x & 15);
     if (d >= a.D) return;
-    const AcSl &s = ac_src(a, t);
+    const somi_slice &s = ac_src(a, t);
     const int c = (t & 3) * a.D + d;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc[9], bs = zero;
@@ -490,7 +483,7 @@ __global__ __launch_bounds__(192) void ac_conv_bwd_weight_kernel(AcArgs a) {
     for (int r = r0; r < r1; ++r) {
         const int b = r / a.H, y = r - b * a.H;
         for (int x = 0; x < a.W; ++x) {
-            const f32x4 g = ac_ld(a.out, (long)r * a.W + x, 4 * d);
+            const f32x4 g = ld4(at_ch(a.out, (long)r * a.W + x, 4 * d));
             bs += g;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
@@ -507,8 +500,8 @@ __global__ __launch_bounds__(192) void ac_conv_bwd_weight_kernel(AcArgs a) {
     }
     float *part = a.part + (long)blockIdx.y * (AC_WG_ROWS + 4) * a.D;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) *reinterpret_cast<f32x4 *>(part + (((long)t * 9 + k) * a.D + d) * 4) = acc[k];
-    if (t == 0) *reinterpret_cast<f32x4 *>(part + (long)AC_WG_ROWS * a.D + 4 * d) = bs;
+    for (int k = 0; k < 9; ++k) st4(part + (((long)t * 9 + k) * a.D + d) * 4, acc[k]);
+    if (t == 0) st4(part + (long)AC_WG_ROWS * a.D + 4 * d, bs);
 }
 
 // the partials in order, times rate2 -> dweff (108 C values) and dbias (C values)
@@ -561,8 +554,6 @@ __global__ __launch_bounds__(256) void ac_split_fc_kernel(const float *dweff, co
 
 // ------------------------------------------------------------------------------------------------ host side
 enum AcOp { AC_ATTN, AC_BWD_Q, AC_BWD_KV, AC_CONV, AC_CONV_BWD_DATA, AC_CONV_BWD_WEIGHT };
-
-static AcSl ac_sl(const somi_slice &s) { return AcSl{s.p, s.cs, s.coff}; }
 
 static bool ac_sizes_ok(int B, int H, int W, int C) {
     return B > 0 && H >= 4 && W >= 4 && C >= 16 && C % 16 == 0 && C <= 1024 && B <= 65535 && cdiv(H, AC_T) <= 65535 &&
@@ -636,8 +627,8 @@ static int ac_unpack(const somi_acmix_desc *d, AcOp op, AcArgs &a, const char *w
         SOMI_REQUIRE(d->workspace_floats >= ac_workspace_floats(d->B, d->H, d->W, C), SOMI_EWORKSPACE, "%s: workspace too small", who);
     }
     a = AcArgs{};
-    a.q = ac_sl(d->q); a.k = ac_sl(d->k); a.v = ac_sl(d->v); a.mix = ac_sl(d->mix); a.out = ac_sl(d->out); a.lse = ac_sl(d->lse);
-    a.aux = ac_sl(d->aux); a.dq = ac_sl(d->dq); a.dk = ac_sl(d->dk); a.dv = ac_sl(d->dv);
+    a.q = d->q; a.k = d->k; a.v = d->v; a.mix = d->mix; a.out = d->out; a.lse = d->lse;
+    a.aux = d->aux; a.dq = d->dq; a.dk = d->dk; a.dv = d->dv;
     a.wp = d->wp; a.rate1 = d->rate1; a.rate2 = d->rate2; a.weff = d->weff; a.bias = d->bias;
     a.dwp = d->dwp; a.drates = d->drates; a.dweff = d->dweff; a.dbias = d->dbias; a.part = d->workspace;
     a.accumulate = d->accumulate;

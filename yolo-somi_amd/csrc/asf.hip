@@ -12,7 +12,7 @@
 //   route      lane (4x4 tile of P3, quad): 16 dout / code / u3 reads, 4 u4, 1 u5; writes g3 (16), g4 (4), g5 (1) and, through the same tree,
 //              the workgroup's partial of sum g and sum g xhat; a second kernel adds the partials the same way (sums, dgamma, dbeta).
 //   apply      du_i = scale (g_i - w_i (m1 + xhat_i m2)) in place, lane (pixel of the list, quad).
-// attention    the ECA gate on (B, C); t = x1 gate + x2 with the row and column means of t in the coordinate-attention geometry (a workgroup
+// attention    the ECA gate on (B, C); t = x1 gate + x2 with the row and column means of t in the map-pass geometry of common.h (a workgroup
 //              takes RH rows x NL columns, a lane walks the rows; row sums through LDS, columns in order; partials, then a fixed-order second
 //              kernel); ds = sum dt x1 per (image, channel) in the same geometry; dx1 = dt gate + davg / HW.
 // No float atomics: two launches are bit-identical.
@@ -20,25 +20,7 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 as_ld(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void as_st(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
-__device__ __forceinline__ const float *as_at(const somi_slice &s, long pix, int q) { return s.p + pix * s.cs + s.coff + 4 * q; }
-__device__ __forceinline__ float *as_at_w(const somi_slice &s, long pix, int q) { return s.p + pix * s.cs + s.coff + 4 * q; }
-__device__ __forceinline__ float as_leaky(float v) { return v > 0.f ? v : 0.1f * v; }
 __device__ __forceinline__ float as_slope(float v) { return v > 0.f ? 1.f : 0.1f; }
-
-// lanes x quads of a 256-thread workgroup over C / 4 quads
-struct AsWg { int QW, NL, nQc; };
-static AsWg as_wg(int C) {
-    AsWg g;
-    const int C4 = C / 4;
-    g.QW = C4 < 256 ? C4 : 256;
-    g.NL = 256 / g.QW;
-    g.nQc = cdiv(C4, 256);
-    return g;
-}
 
 // the sum over the NL lanes of a workgroup, fixed tree: at width s lane l takes lane l + s.  Every thread of the workgroup calls it; the
 // result is valid on lane 0.  buf: 256 entries; the caller synchronises before reusing it.
@@ -75,14 +57,14 @@ __global__ __launch_bounds__(256) void zc_fwd_kernel(ZcArgs a, long total) {
     const long bh = pix / a.W;
     const int h = (int)(bh % a.H);
     const long b = bh / a.H;
-    float *o = as_at_w(a.out, pix, q);
+    float *o = at_w(a.out, pix, q);
     if (q < a.Ql) {
         const long p00 = (b * 2 * a.H + 2 * h) * (2L * a.W) + 2 * w;
         f32x4 v[4];
-        v[0] = as_ld(as_at(a.l, p00, q));
-        v[1] = as_ld(as_at(a.l, p00 + 1, q));
-        v[2] = as_ld(as_at(a.l, p00 + 2L * a.W, q));
-        v[3] = as_ld(as_at(a.l, p00 + 2L * a.W + 1, q));
+        v[0] = ld4(at(a.l, p00, q));
+        v[1] = ld4(at(a.l, p00 + 1, q));
+        v[2] = ld4(at(a.l, p00 + 2L * a.W, q));
+        v[3] = ld4(at(a.l, p00 + 2L * a.W + 1, q));
         f32x4 r;
         unsigned code = 0;
 #pragma unroll
@@ -95,13 +77,13 @@ __global__ __launch_bounds__(256) void zc_fwd_kernel(ZcArgs a, long total) {
             r[j] = mx + 0.25f * (v[0][j] + v[1][j] + v[2][j] + v[3][j]);
             code |= best << (2 * j);
         }
-        as_st(o, r);
+        st4(o, r);
         if (a.codes) a.codes[pix * a.Ql + q] = (uint8_t)code;
     } else if (q < a.Ql + a.Qm) {
-        if (a.m.p) as_st(o, as_ld(as_at(a.m, pix, q - a.Ql)));
+        if (a.m.p) st4(o, ld4(at(a.m, pix, q - a.Ql)));
     } else {
         const long ps = (b * a.Hs + (h >> 1)) * a.Ws + (w >> 1);
-        as_st(o, as_ld(as_at(a.s, ps, q - a.Ql - a.Qm)));
+        st4(o, ld4(at(a.s, ps, q - a.Ql - a.Qm)));
     }
 }
 
@@ -116,24 +98,24 @@ __global__ __launch_bounds__(256) void zc_bwd_kernel(ZcArgs a, long total) {
         const int y = (int)(by % (2 * a.H));
         const long b = by / (2 * a.H);
         const long pix = (b * a.H + (y >> 1)) * a.W + (x >> 1);
-        const f32x4 d = as_ld(as_at(a.out, pix, q));
+        const f32x4 d = ld4(at(a.out, pix, q));
         const unsigned code = a.codes[pix * a.Ql + q], pos = (unsigned)((y & 1) * 2 + (x & 1));
         f32x4 r;
 #pragma unroll
         for (int j = 0; j < 4; ++j) r[j] = d[j] * (0.25f + (((code >> (2 * j)) & 3u) == pos ? 1.f : 0.f));
-        float *o = as_at_w(a.l, pl, q);
-        if (a.acc_l) r += as_ld(o);
-        as_st(o, r);
+        float *o = at_w(a.l, pl, q);
+        if (a.acc_l) r += ld4(o);
+        st4(o, r);
         return;
     }
     i -= a.n_l;
     if (i < a.n_m) {                                              // dm = dout's middle slice
         const int q = (int)(i % a.Qm);
         const long pix = i / a.Qm;
-        f32x4 r = as_ld(as_at(a.out, pix, a.Ql + q));
-        float *o = as_at_w(a.m, pix, q);
-        if (a.acc_m) r += as_ld(o);
-        as_st(o, r);
+        f32x4 r = ld4(at(a.out, pix, a.Ql + q));
+        float *o = at_w(a.m, pix, q);
+        if (a.acc_m) r += ld4(o);
+        st4(o, r);
         return;
     }
     i -= a.n_m;                                                   // ds: the children that exist, in row-major order
@@ -147,11 +129,11 @@ __global__ __launch_bounds__(256) void zc_bwd_kernel(ZcArgs a, long total) {
     for (int di = 0; di < 2; ++di)
         for (int dj = 0; dj < 2; ++dj) {
             const int h = 2 * hs + di, w = 2 * ws + dj;
-            if (h < a.H && w < a.W) r += as_ld(as_at(a.out, (b * a.H + h) * a.W + w, a.Ql + a.Qm + q));
+            if (h < a.H && w < a.W) r += ld4(at(a.out, (b * a.H + h) * a.W + w, a.Ql + a.Qm + q));
         }
-    float *o = as_at_w(a.s, ps, q);
-    if (a.acc_s) r += as_ld(o);
-    as_st(o, r);
+    float *o = at_w(a.s, ps, q);
+    if (a.acc_s) r += ld4(o);
+    st4(o, r);
 }
 
 static int zc_unpack(const somi_zoomcat_desc *d, bool bwd, ZcArgs &a, const char *who) {
@@ -211,7 +193,7 @@ __global__ __launch_bounds__(256) void ss_stats_kernel(SsArgs a) {
     const bool on = lane < a.NL && q < a.C4;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 s1 = zero, s2 = zero, piv = zero;
-    if (on && a.rm) piv = as_ld(a.rm + 4 * q);
+    if (on && a.rm) piv = ld4(a.rm + 4 * q);
     const long total = a.n3 + a.n4 + a.n5;
     const long p0 = (long)blockIdx.x * (SS_K * a.NL) + lane;
     f32x4 v[SS_K];
@@ -223,7 +205,7 @@ __global__ __launch_bounds__(256) void ss_stats_kernel(SsArgs a) {
         wgt[k] = 0.f;
         if (on && p < total) {
             const int mp = ss_map(a, p);
-            v[k] = as_ld(as_at(a.u[mp], p, q));
+            v[k] = ld4(at(a.u[mp], p, q));
             wgt[k] = mp == 0 ? 1.f : (mp == 1 ? 4.f : 16.f);
         }
     }
@@ -238,8 +220,8 @@ __global__ __launch_bounds__(256) void ss_stats_kernel(SsArgs a) {
     s2 = as_tree(s2, buf, t, lane, a.QW, a.NL);
     if (on && lane == 0) {
         float *dst = a.part + (long)blockIdx.x * 2 * (4 * a.C4) + 4 * q;
-        as_st(dst, s1);
-        as_st(dst + 4 * a.C4, s2);
+        st4(dst, s1);
+        st4(dst + 4 * a.C4, s2);
     }
 }
 
@@ -251,7 +233,7 @@ __device__ __forceinline__ void ss_sum_parts(const SsArgs &a, double (&s1)[4], d
     for (int j = 0; j < 4; ++j) s1[j] = s2[j] = 0.0;
     for (int k = t; k < a.nparts; k += 256) {
         const float *src = a.part + (long)k * 2 * (4 * a.C4) + 4 * q;
-        const f32x4 v1 = as_ld(src), v2 = as_ld(src + 4 * a.C4);
+        const f32x4 v1 = ld4(src), v2 = ld4(src + 4 * a.C4);
         for (int j = 0; j < 4; ++j) { s1[j] += (double)v1[j]; s2[j] += (double)v2[j]; }
     }
     for (int j = 0; j < 4; ++j) { sh[j][t] = s1[j]; sh[4 + j][t] = s2[j]; }
@@ -295,26 +277,26 @@ __global__ __launch_bounds__(256) void ss_fuse_kernel(SsArgs a, long total) {
     const int h = (int)(bh % a.H);
     const long b = bh / a.H;
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-    if (a.scale) { sc = as_ld(a.scale + 4 * q); sh = as_ld(a.shift + 4 * q); }
+    if (a.scale) { sc = ld4(a.scale + 4 * q); sh = ld4(a.shift + 4 * q); }
     f32x4 v[3];
-    v[0] = as_ld(as_at(a.u[0], pix, q));
-    v[1] = as_ld(as_at(a.u[1], (b * (a.H / 2) + (h >> 1)) * (a.W / 2) + (w >> 1), q));
-    v[2] = as_ld(as_at(a.u[2], (b * (a.H / 4) + (h >> 2)) * (a.W / 4) + (w >> 2), q));
+    v[0] = ld4(at(a.u[0], pix, q));
+    v[1] = ld4(at(a.u[1], (b * (a.H / 2) + (h >> 1)) * (a.W / 2) + (w >> 1), q));
+    v[2] = ld4(at(a.u[2], (b * (a.H / 4) + (h >> 2)) * (a.W / 4) + (w >> 2), q));
     f32x4 r;
     unsigned code = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        float mx = as_leaky(sc[j] * v[0][j] + sh[j]);
+        float mx = apply_act<SOMI_ACT_LEAKY>(sc[j] * v[0][j] + sh[j]);
         unsigned best = 0;
 #pragma unroll
         for (int k = 1; k < 3; ++k) {
-            const float z = as_leaky(sc[j] * v[k][j] + sh[j]);
+            const float z = apply_act<SOMI_ACT_LEAKY>(sc[j] * v[k][j] + sh[j]);
             if (z > mx) { mx = z; best = k; }                     // strictly greater: the first depth index keeps a tie
         }
         r[j] = mx;
         code |= best << (2 * j);
     }
-    as_st(as_at_w(a.out, pix, q), r);
+    st4(at_w(a.out, pix, q), r);
     if (a.codes) a.codes[pix * a.C4 + q] = (uint8_t)code;
 }
 
@@ -331,14 +313,14 @@ __global__ __launch_bounds__(256) void ss_route_kernel(SsArgs a, long tiles) {
         const long bt = tile / W4;
         const int ty = (int)(bt % H4);
         const long b = bt / H4;
-        const f32x4 sc = as_ld(a.scale + 4 * q), sh = as_ld(a.shift + 4 * q), mu = as_ld(a.mean + 4 * q), rs = as_ld(a.rstd + 4 * q);
+        const f32x4 sc = ld4(a.scale + 4 * q), sh = ld4(a.shift + 4 * q), mu = ld4(a.mean + 4 * q), rs = ld4(a.rstd + 4 * q);
         const long p5 = (b * H4 + ty) * W4 + tx;
-        const f32x4 u5 = as_ld(as_at(a.u[2], p5, q));
+        const f32x4 u5 = ld4(at(a.u[2], p5, q));
         f32x4 g5 = zero;
         for (int cy = 0; cy < 2; ++cy)
             for (int cx = 0; cx < 2; ++cx) {
                 const long p4 = (b * H2 + 2 * ty + cy) * W2 + 2 * tx + cx;
-                const f32x4 u4 = as_ld(as_at(a.u[1], p4, q));
+                const f32x4 u4 = ld4(at(a.u[1], p4, q));
                 f32x4 g4 = zero;
                 f32x4 d[4], u3[4];
                 unsigned code[4];
@@ -346,8 +328,8 @@ __global__ __launch_bounds__(256) void ss_route_kernel(SsArgs a, long tiles) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     p3[k] = (b * a.H + 4 * ty + 2 * cy + (k >> 1)) * a.W + 4 * tx + 2 * cx + (k & 1);
-                    d[k] = as_ld(as_at(a.out, p3[k], q));
-                    u3[k] = as_ld(as_at(a.u[0], p3[k], q));
+                    d[k] = ld4(at(a.out, p3[k], q));
+                    u3[k] = ld4(at(a.u[0], p3[k], q));
                     code[k] = a.codes[p3[k] * a.C4 + q];
                 }
 #pragma unroll
@@ -360,19 +342,19 @@ __global__ __launch_bounds__(256) void ss_route_kernel(SsArgs a, long tiles) {
                         g4[j] += sel == 1 ? d[k][j] : 0.f;
                         g5[j] += sel == 2 ? d[k][j] : 0.f;
                     }
-                    as_st(as_at_w(a.g[0], p3[k], q), g3);
+                    st4(at_w(a.g[0], p3[k], q), g3);
                     sg += g3;
                     sgx += g3 * ((u3[k] - mu) * rs);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) g4[j] *= as_slope(sc[j] * u4[j] + sh[j]);
-                as_st(as_at_w(a.g[1], p4, q), g4);
+                st4(at_w(a.g[1], p4, q), g4);
                 sg += g4;
                 sgx += g4 * ((u4 - mu) * rs);
             }
 #pragma unroll
         for (int j = 0; j < 4; ++j) g5[j] *= as_slope(sc[j] * u5[j] + sh[j]);
-        as_st(as_at_w(a.g[2], p5, q), g5);
+        st4(at_w(a.g[2], p5, q), g5);
         sg += g5;
         sgx += g5 * ((u5 - mu) * rs);
     }
@@ -381,8 +363,8 @@ __global__ __launch_bounds__(256) void ss_route_kernel(SsArgs a, long tiles) {
     sgx = as_tree(sgx, buf, t, lane, a.QW, a.NL);
     if (lane == 0 && q < a.C4) {
         float *dst = a.part + (long)blockIdx.x * 2 * (4 * a.C4) + 4 * q;
-        as_st(dst, sg);
-        as_st(dst + 4 * a.C4, sgx);
+        st4(dst, sg);
+        st4(dst + 4 * a.C4, sgx);
     }
 }
 
@@ -407,16 +389,16 @@ __global__ __launch_bounds__(256) void ss_apply_kernel(SsArgs a, long total) {
     const int mp = ss_map(a, p);
     const float wgt = mp == 0 ? 1.f : (mp == 1 ? 4.f : 16.f);
     const float invN = 1.0f / (3.0f * (float)a.n3);
-    const f32x4 sc = as_ld(a.scale + 4 * q), mu = as_ld(a.mean + 4 * q), rs = as_ld(a.rstd + 4 * q);
-    const f32x4 m1 = as_ld(a.sums + 4 * q) * invN, m2 = as_ld(a.sums + 4 * a.C4 + 4 * q) * invN;
-    const f32x4 xh = (as_ld(as_at(a.u[mp], p, q)) - mu) * rs;
-    float *g = as_at_w(a.g[mp], p, q);
-    as_st(g, sc * (as_ld(g) - wgt * (m1 + xh * m2)));
+    const f32x4 sc = ld4(a.scale + 4 * q), mu = ld4(a.mean + 4 * q), rs = ld4(a.rstd + 4 * q);
+    const f32x4 m1 = ld4(a.sums + 4 * q) * invN, m2 = ld4(a.sums + 4 * a.C4 + 4 * q) * invN;
+    const f32x4 xh = (ld4(at(a.u[mp], p, q)) - mu) * rs;
+    float *g = at_w(a.g[mp], p, q);
+    st4(g, sc * (ld4(g) - wgt * (m1 + xh * m2)));
 }
 
 enum SsOp { SS_STATS, SS_FUSE, SS_ROUTE, SS_APPLY };
 
-static int ss_nparts(SsOp op, int B, int H, int W, const AsWg &g) {
+static int ss_nparts(SsOp op, int B, int H, int W, const MapShape &g) {
     const long n3 = (long)B * H * W;
     if (op == SS_STATS) return cdiv(n3 + n3 / 4 + n3 / 16, (long)SS_K * g.NL);
     return cdiv(n3 / 16, g.NL);
@@ -450,7 +432,7 @@ static int ss_unpack(const somi_scalseq_desc *d, SsOp op, SsArgs &a, const char 
         SOMI_REQUIRE(d->workspace && aligned16(d->workspace), SOMI_EINVAL, "%s: a 16-byte aligned workspace is required", who);
         SOMI_REQUIRE(d->workspace_floats >= somi_scalseq_workspace_floats(d->B, d->H, d->W, C), SOMI_EWORKSPACE, "%s: workspace too small", who);
     }
-    const AsWg g = as_wg(C);
+    const MapShape g = map_shape(C);
     a = SsArgs{};
     a.u[0] = d->u3; a.u[1] = d->u4; a.u[2] = d->u5;
     a.out = d->out;
@@ -532,19 +514,6 @@ __global__ __launch_bounds__(256) void eca_dw_kernel(const float *avg, int k, co
 
 constexpr int AM_RU = 4;          // rows in flight per lane
 
-struct AmPlan { int QW, NL, nQc, nWc, nHc, RH; };
-
-static AmPlan am_plan(int B, int H, int W, int C) {
-    AmPlan p;
-    const AsWg g = as_wg(C);
-    p.QW = g.QW; p.NL = g.NL; p.nQc = g.nQc;
-    p.nWc = cdiv(W, p.NL);
-    p.RH = 32;
-    while (p.RH > AM_RU && (long)B * p.nQc * p.nWc * cdiv(H, p.RH) < 1024) p.RH /= 2;
-    p.nHc = cdiv(H, p.RH);
-    return p;
-}
-
 struct AmArgs {
     somi_slice x1, x2, t, pool, dx1;
     const float *gate, *davg;
@@ -553,29 +522,14 @@ struct AmArgs {
     int B, H, W, C4, QW, NL, nQc, nWc, nHc, RH;
 };
 
-struct AmLane { int b, q, w, h0, h1, lane; bool on; };
-
-__device__ __forceinline__ AmLane am_lane(const AmArgs &a) {
-    AmLane l;
-    const int t = threadIdx.x;
-    l.lane = t / a.QW;
-    l.b = blockIdx.z / a.nQc;
-    l.q = (blockIdx.z - l.b * a.nQc) * 256 + (t - l.lane * a.QW);
-    l.w = blockIdx.x * a.NL + l.lane;
-    l.h0 = blockIdx.y * a.RH;
-    l.h1 = min(a.H, l.h0 + a.RH);
-    l.on = l.lane < a.NL && l.q < a.C4 && l.w < a.W;
-    return l;
-}
-
 // t = x1 gate + x2 written; row partials [B][H][nWc][C], column partials [B][nHc][W][C]
 __global__ __launch_bounds__(256) void am_mix_kernel(AmArgs a) {
     __shared__ f32x4 srow[AM_RU][256];
     const int t = threadIdx.x;
-    const AmLane l = am_lane(a);
+    const MapLane l = map_lane(a);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 col = zero, gt = zero;
-    if (l.on) gt = as_ld(a.gate + (long)l.b * (4 * a.C4) + 4 * l.q);
+    if (l.on) gt = ld4(a.gate + (long)l.b * (4 * a.C4) + 4 * l.q);
     for (int g = l.h0; g < l.h1; g += AM_RU) {
         f32x4 v1[AM_RU], v2[AM_RU];
 #pragma unroll
@@ -583,14 +537,14 @@ __global__ __launch_bounds__(256) void am_mix_kernel(AmArgs a) {
             v1[r] = v2[r] = zero;
             if (l.on && g + r < l.h1) {
                 const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                v1[r] = as_ld(as_at(a.x1, pix, l.q));
-                v2[r] = as_ld(as_at(a.x2, pix, l.q));
+                v1[r] = ld4(at(a.x1, pix, l.q));
+                v2[r] = ld4(at(a.x2, pix, l.q));
             }
         }
 #pragma unroll
         for (int r = 0; r < AM_RU; ++r) {
             const f32x4 m = v1[r] * gt + v2[r];
-            if (l.on && g + r < l.h1) as_st(as_at_w(a.t, ((long)l.b * a.H + g + r) * a.W + l.w, l.q), m);
+            if (l.on && g + r < l.h1) st4(at_w(a.t, ((long)l.b * a.H + g + r) * a.W + l.w, l.q), m);
             col += m;
             srow[r][t] = m;
         }
@@ -601,12 +555,12 @@ __global__ __launch_bounds__(256) void am_mix_kernel(AmArgs a) {
             if (g + r < l.h1 && q < a.C4) {
                 f32x4 s = srow[r][qq];
                 for (int k = 1; k < a.NL; ++k) s += srow[r][k * a.QW + qq];
-                as_st(a.rowpart + (((long)l.b * a.H + g + r) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * q, s);
+                st4(a.rowpart + (((long)l.b * a.H + g + r) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * q, s);
             }
         }
         __syncthreads();
     }
-    if (l.on) as_st(a.colpart + (((long)l.b * a.nHc + blockIdx.y) * a.W + l.w) * (4 * a.C4) + 4 * l.q, col);
+    if (l.on) st4(a.colpart + (((long)l.b * a.nHc + blockIdx.y) * a.W + l.w) * (4 * a.C4) + 4 * l.q, col);
 }
 
 __global__ __launch_bounds__(256) void am_mix_finish_kernel(AmArgs a) {
@@ -618,21 +572,21 @@ __global__ __launch_bounds__(256) void am_mix_finish_kernel(AmArgs a) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (r < a.H) {
         const float *p = a.rowpart + ((long)b * a.H + r) * a.nWc * (4 * a.C4) + 4 * q;
-        for (int k = 0; k < a.nWc; ++k) s += as_ld(p + (long)k * (4 * a.C4));
+        for (int k = 0; k < a.nWc; ++k) s += ld4(p + (long)k * (4 * a.C4));
         s = s / (float)a.W;
     } else {
         const float *p = a.colpart + ((long)b * a.nHc * a.W + (r - a.H)) * (4 * a.C4) + 4 * q;
-        for (int k = 0; k < a.nHc; ++k) s += as_ld(p + (long)k * a.W * (4 * a.C4));
+        for (int k = 0; k < a.nHc; ++k) s += ld4(p + (long)k * a.W * (4 * a.C4));
         s = s / (float)a.H;
     }
-    as_st(as_at_w(a.pool, br, q), s);
+    st4(at_w(a.pool, br, q), s);
 }
 
 // ds partials [B][nHc][nWc][C]: a lane's rows in order, then the workgroup's columns by the fixed tree
 __global__ __launch_bounds__(256) void am_sums_kernel(AmArgs a) {
     __shared__ f32x4 buf[256];
     const int t = threadIdx.x;
-    const AmLane l = am_lane(a);
+    const MapLane l = map_lane(a);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc = zero;
     for (int g = l.h0; g < l.h1; g += AM_RU) {
@@ -642,8 +596,8 @@ __global__ __launch_bounds__(256) void am_sums_kernel(AmArgs a) {
             v1[r] = dt[r] = zero;
             if (l.on && g + r < l.h1) {
                 const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                v1[r] = as_ld(as_at(a.x1, pix, l.q));
-                dt[r] = as_ld(as_at(a.t, pix, l.q));
+                v1[r] = ld4(at(a.x1, pix, l.q));
+                dt[r] = ld4(at(a.t, pix, l.q));
             }
         }
 #pragma unroll
@@ -651,7 +605,7 @@ __global__ __launch_bounds__(256) void am_sums_kernel(AmArgs a) {
     }
     acc = as_tree(acc, buf, t, l.lane, a.QW, a.NL);
     if (l.lane == 0 && l.q < a.C4)
-        as_st(a.rowpart + (((long)l.b * a.nHc + blockIdx.y) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * l.q, acc);
+        st4(a.rowpart + (((long)l.b * a.nHc + blockIdx.y) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * l.q, acc);
 }
 
 __global__ __launch_bounds__(256) void am_sums_finish_kernel(AmArgs a) {
@@ -662,8 +616,8 @@ __global__ __launch_bounds__(256) void am_sums_finish_kernel(AmArgs a) {
     const int n = a.nHc * a.nWc;
     const float *p = a.rowpart + b * n * (4 * a.C4) + 4 * q;
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < n; ++k) s += as_ld(p + (long)k * (4 * a.C4));
-    as_st(a.ds + b * (4 * a.C4) + 4 * q, s);
+    for (int k = 0; k < n; ++k) s += ld4(p + (long)k * (4 * a.C4));
+    st4(a.ds + b * (4 * a.C4) + 4 * q, s);
 }
 
 __global__ __launch_bounds__(256) void am_input_kernel(AmArgs a, long total) {
@@ -672,11 +626,11 @@ __global__ __launch_bounds__(256) void am_input_kernel(AmArgs a, long total) {
     const int q = (int)(i % a.C4);
     const long pix = i / a.C4;
     const long b = pix / ((long)a.H * a.W);
-    const f32x4 gt = as_ld(a.gate + b * (4 * a.C4) + 4 * q), da = as_ld(a.davg + b * (4 * a.C4) + 4 * q);
-    f32x4 r = as_ld(as_at(a.t, pix, q)) * gt + da / (float)(a.H * a.W);
-    float *o = as_at_w(a.dx1, pix, q);
-    if (a.accumulate) r += as_ld(o);
-    as_st(o, r);
+    const f32x4 gt = ld4(a.gate + b * (4 * a.C4) + 4 * q), da = ld4(a.davg + b * (4 * a.C4) + 4 * q);
+    f32x4 r = ld4(at(a.t, pix, q)) * gt + da / (float)(a.H * a.W);
+    float *o = at_w(a.dx1, pix, q);
+    if (a.accumulate) r += ld4(o);
+    st4(o, r);
 }
 
 enum AmOp { AM_MIX, AM_SUMS, AM_INPUT };
@@ -699,7 +653,7 @@ static int am_unpack(const somi_asfatt_desc *d, AmOp op, AmArgs &a, const char *
         SOMI_REQUIRE(d->workspace && aligned16(d->workspace), SOMI_EINVAL, "%s: a 16-byte aligned workspace is required", who);
         SOMI_REQUIRE(d->workspace_floats >= somi_asfatt_workspace_floats(d->B, d->H, d->W, C), SOMI_EWORKSPACE, "%s: workspace too small", who);
     }
-    const AmPlan p = am_plan(d->B, d->H, d->W, C);
+    const MapPlan p = map_plan(d->B, d->H, d->W, C, AM_RU);
     a = AmArgs{};
     a.x1 = d->x1; a.x2 = d->x2; a.t = d->t; a.pool = d->pool; a.dx1 = d->dx1;
     a.gate = d->gate; a.davg = d->davg; a.ds = d->ds;
@@ -747,7 +701,7 @@ extern "C" int somi_zoomcat_bwd_nhwc_f32(const somi_zoomcat_desc *d, somi_stream
 
 extern "C" size_t somi_scalseq_workspace_floats(int B, int H, int W, int C) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 || H % 4 || W % 4) return 0;
-    const AsWg g = as_wg(C);
+    const MapShape g = map_shape(C);
     const int n = ss_nparts(SS_STATS, B, H, W, g), m = ss_nparts(SS_ROUTE, B, H, W, g);
     return (size_t)(n > m ? n : m) * 2 * C;
 }
@@ -786,7 +740,7 @@ extern "C" int somi_scalseq_apply_bwd_f32(const somi_scalseq_desc *d, somi_strea
 
 extern "C" size_t somi_asfatt_workspace_floats(int B, int H, int W, int C) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4) return 0;
-    const AmPlan p = am_plan(B, H, W, C);
+    const MapPlan p = map_plan(B, H, W, C, AM_RU);
     return ((size_t)B * H * p.nWc + (size_t)B * p.nHc * W) * C;      // also covers the B * nHc * nWc rows of the backward sums
 }
 

@@ -13,8 +13,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int ASFF_TP = 64;       // output pixels per workgroup
 constexpr int ASFF_VC = 16;       // channels of a weight map
 constexpr int ASFF_NW = 3 * 3 * ASFF_VC + 3;      // dW (3 x 48) and db (3) of one workgroup
@@ -65,10 +63,10 @@ __global__ __launch_bounds__(256) void asff_fuse_fwd_kernel(AsffArgs a) {
             const float *vp = a.v[j] + asff_src_pixel(a, b, h, w, a.v_up[j]) * a.v_cs[j] + a.v_coff[j];
 #pragma unroll
             for (int q = 0; q < ASFF_VC / 4; ++q) {
-                const f32x4 x = *reinterpret_cast<const f32x4 *>(vp + 4 * q);
-                const f32x4 w0 = *reinterpret_cast<const f32x4 *>(a.w + 0 * 48 + j * ASFF_VC + 4 * q);
-                const f32x4 w1 = *reinterpret_cast<const f32x4 *>(a.w + 1 * 48 + j * ASFF_VC + 4 * q);
-                const f32x4 w2 = *reinterpret_cast<const f32x4 *>(a.w + 2 * 48 + j * ASFF_VC + 4 * q);
+                const f32x4 x = ld4(vp + 4 * q);
+                const f32x4 w0 = ld4(a.w + 0 * 48 + j * ASFF_VC + 4 * q);
+                const f32x4 w1 = ld4(a.w + 1 * 48 + j * ASFF_VC + 4 * q);
+                const f32x4 w2 = ld4(a.w + 2 * 48 + j * ASFF_VC + 4 * q);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { l0 += w0[e] * x[e]; l1 += w1[e] * x[e]; l2 += w2[e] * x[e]; }
             }
@@ -96,11 +94,12 @@ __global__ __launch_bounds__(256) void asff_fuse_fwd_kernel(AsffArgs a) {
         const int lp = it / C4, c = (it - lp * C4) * 4;
         const long pix = spix[lp][3];
         if (pix < 0) continue;
-        const f32x4 x0 = *reinterpret_cast<const f32x4 *>(a.r[0] + spix[lp][0] * a.r_cs[0] + a.r_coff[0] + c);
-        const f32x4 x1 = *reinterpret_cast<const f32x4 *>(a.r[1] + spix[lp][1] * a.r_cs[1] + a.r_coff[1] + c);
-        const f32x4 x2 = *reinterpret_cast<const f32x4 *>(a.r[2] + spix[lp][2] * a.r_cs[2] + a.r_coff[2] + c);
+        const f32x4 x0 = ld4(a.r[0] + spix[lp][0] * a.r_cs[0] + a.r_coff[0] + c);
+        const f32x4 x1 = ld4(a.r[1] + spix[lp][1] * a.r_cs[1] + a.r_coff[1] + c);
+        const f32x4 x2 = ld4(a.r[2] + spix[lp][2] * a.r_cs[2] + a.r_coff[2] + c);
         const float p0 = sp[lp][0], p1 = sp[lp][1], p2 = sp[lp][2];
-        *reinterpret_cast<f32x4 *>(a.out + pix * a.o_cs + a.o_coff + c) = x0 * p0 + x1 * p1 + x2 * p2;
+        const f32x4 o = x0 * p0 + x1 * p1 + x2 * p2;
+        st4(a.out + pix * a.o_cs + a.o_coff + c, o);
     }
 }
 
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(256) void asff_fuse_bwd_kernel(AsffArgs a) {
     for (int it = t; it < ASFF_TP * 3 * (ASFF_VC / 4); it += 256) {
         const int lp = it / 12, q = it - lp * 12, i = q >> 2, c = (q & 3) * 4;
         f32x4 x = {0.f, 0.f, 0.f, 0.f};
-        if (spix[lp][3] >= 0) x = *reinterpret_cast<const f32x4 *>(a.v[i] + svpix[lp][i] * a.v_cs[i] + a.v_coff[i] + c);
+        if (spix[lp][3] >= 0) x = ld4(a.v[i] + svpix[lp][i] * a.v_cs[i] + a.v_coff[i] + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) scat[lp][i * ASFF_VC + c + e] = x[e];
     }
@@ -149,10 +148,10 @@ __global__ __launch_bounds__(256) void asff_fuse_bwd_kernel(AsffArgs a) {
             const float *r1 = a.r[1] + spix[lp][1] * a.r_cs[1] + a.r_coff[1];
             const float *r2 = a.r[2] + spix[lp][2] * a.r_cs[2] + a.r_coff[2];
             for (int q = sub; q < C4; q += 16) {
-                const f32x4 d = *reinterpret_cast<const f32x4 *>(dp + 4 * q);
-                const f32x4 x0 = *reinterpret_cast<const f32x4 *>(r0 + 4 * q);
-                const f32x4 x1 = *reinterpret_cast<const f32x4 *>(r1 + 4 * q);
-                const f32x4 x2 = *reinterpret_cast<const f32x4 *>(r2 + 4 * q);
+                const f32x4 d = ld4(dp + 4 * q);
+                const f32x4 x0 = ld4(r0 + 4 * q);
+                const f32x4 x1 = ld4(r1 + 4 * q);
+                const f32x4 x2 = ld4(r2 + 4 * q);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { d0 += d[e] * x0[e]; d1 += d[e] * x1[e]; d2 += d[e] * x2[e]; }
             }
@@ -181,11 +180,11 @@ __global__ __launch_bounds__(256) void asff_fuse_bwd_kernel(AsffArgs a) {
             for (int cy = 0; cy < side; ++cy)
                 for (int cx = 0; cx < side; ++cx) {
                     const int lp = asff_child(j, u, U, cy, cx);
-                    acc += *reinterpret_cast<const f32x4 *>(a.out + spix[lp][3] * a.o_cs + a.o_coff + c) * sp[lp][i];
+                    acc += ld4(a.out + spix[lp][3] * a.o_cs + a.o_coff + c) * sp[lp][i];
                 }
             float *dst = a.dr[i] + spix[first][i] * a.dr_cs[i] + a.dr_coff[i] + c;
-            if (a.dr_acc[i]) acc += *reinterpret_cast<const f32x4 *>(dst);
-            *reinterpret_cast<f32x4 *>(dst) = acc;
+            if (a.dr_acc[i]) acc += ld4(dst);
+            st4(dst, acc);
         }
     }
     // dv_i = W^T (sum over the children of dL), 16 channels per weight-map pixel
@@ -201,10 +200,11 @@ __global__ __launch_bounds__(256) void asff_fuse_bwd_kernel(AsffArgs a) {
                     const int lp = asff_child(j, u, U, cy, cx);
                     g0 += sdl[lp][0]; g1 += sdl[lp][1]; g2 += sdl[lp][2];
                 }
-            const f32x4 w0 = *reinterpret_cast<const f32x4 *>(a.w + 0 * 48 + i * ASFF_VC + c);
-            const f32x4 w1 = *reinterpret_cast<const f32x4 *>(a.w + 1 * 48 + i * ASFF_VC + c);
-            const f32x4 w2 = *reinterpret_cast<const f32x4 *>(a.w + 2 * 48 + i * ASFF_VC + c);
-            *reinterpret_cast<f32x4 *>(a.dv[i] + svpix[first][i] * a.dv_cs[i] + a.dv_coff[i] + c) = w0 * g0 + w1 * g1 + w2 * g2;
+            const f32x4 w0 = ld4(a.w + 0 * 48 + i * ASFF_VC + c);
+            const f32x4 w1 = ld4(a.w + 1 * 48 + i * ASFF_VC + c);
+            const f32x4 w2 = ld4(a.w + 2 * 48 + i * ASFF_VC + c);
+            const f32x4 dvi = w0 * g0 + w1 * g1 + w2 * g2;
+            st4(a.dv[i] + svpix[first][i] * a.dv_cs[i] + a.dv_coff[i] + c, dvi);
         }
     }
     // this workgroup's dW[k][m] = sum_pixels dL_k * cat(v)[m] and db[k] = sum_pixels dL_k, pixels in order

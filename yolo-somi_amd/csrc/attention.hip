@@ -19,9 +19,6 @@
 namespace somi {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int KD = 32, HD = 64, QKV_H = 2 * KD + HD;              // per head: q 32 | k 32 | v 64 channels
 constexpr int TILE = 32, WAVES = 4, THREADS = 64 * WAVES, ROWS_WG = TILE * WAVES;
 constexpr int KLD = KD + 4, VLD = HD + 4;                         // padded LDS row strides (floats)

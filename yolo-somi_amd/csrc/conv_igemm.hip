@@ -34,12 +34,6 @@
 
 namespace somi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BK = 32;                    // K-tile (floats)
 constexpr int OP_LD = BK;                 // operand image row stride in floats (128 B, chunks XOR-swizzled)
 constexpr unsigned OOB = 0xFFFFFFE0u;     // byte offset beyond every descriptor: the load returns 0
@@ -419,7 +413,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (conv_waves_per_simd<BM, BN
         };
         auto store_split = [&](float *rowp, const f32x4 &v) {           // 4 floats -> 4 bf16 hi (8 B) [+ 4 bf16 lo in the chunk slot ^ 4]
             const __bf16 h0 = (__bf16)v[0], h1 = (__bf16)v[1], h2 = (__bf16)v[2], h3 = (__bf16)v[3];
-            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
             *reinterpret_cast<bf16x4 *>(rowp + st_off) = bf16x4{h0, h1, h2, h3};
             if constexpr (NS == 2) {
                 const bf16x4 lo = {(__bf16)(v[0] - (float)h0), (__bf16)(v[1] - (float)h1), (__bf16)(v[2] - (float)h2), (__bf16)(v[3] - (float)h3)};

@@ -14,14 +14,6 @@
 
 namespace somi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WG_PIX = 32;                  // pixels per K-tile
 constexpr unsigned W_OOB = 0xFFFFFFE0u;
 constexpr unsigned W_MAX_BUF = 0xE0000000u;

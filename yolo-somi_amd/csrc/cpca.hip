@@ -28,8 +28,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CP_R = 4;                   // outputs per lane along the strip
 constexpr int CP_HALO = 10;               // 21 / 2
 constexpr int CP_TAMAX = 64;              // strip positions of a tile
@@ -90,7 +88,7 @@ __device__ __forceinline__ void cp_load_tile(f32x4 *tile, const somi_slice &s, c
         const int pa = a0 - halo + i, po = o0 + o, qg = qc * CP_QWMAX + qq;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (qg < g.C4 && pa >= 0 && pa < g.LA && po < g.LO)
-            v = *reinterpret_cast<const f32x4 *>(s.p + (img + (long)pa * g.SA + (long)po * g.SO) * s.cs + s.coff + 4 * qg);
+            v = ld4(at(s, img + (long)pa * g.SA + (long)po * g.SO, qg));
         tile[idx] = v;
     }
 }
@@ -174,8 +172,10 @@ __global__ __launch_bounds__(256) void cp_strip_kernel(CpArgs a) {
                 if (pa0 + r >= g.LA) break;
                 const long pix = pix0 + (long)r * g.SA;
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    *reinterpret_cast<f32x4 *>(a.dst[k].p + pix * a.dst[k].cs + a.dst[k].coff + 4 * qg) = acc[k][r] + bs[k];
+                for (int k = 0; k < 3; ++k) {
+                    const f32x4 o = acc[k][r] + bs[k];
+                    st4(at_w(a.dst[k], pix, qg), o);
+                }
             }
         } else {
             f32x4 acc[CP_R];
@@ -184,8 +184,8 @@ __global__ __launch_bounds__(256) void cp_strip_kernel(CpArgs a) {
                 acc[r] = zero;
                 if (lane && pa0 + r < g.LA) {
                     const long pix = pix0 + (long)r * g.SA;
-                    acc[r] = *reinterpret_cast<const f32x4 *>(a.src[3].p + pix * a.src[3].cs + a.src[3].coff + 4 * qg) + (bs[0] + bs[1] + bs[2]);
-                    if (a.accumulate) acc[r] += *reinterpret_cast<const f32x4 *>(a.dst[0].p + pix * a.dst[0].cs + a.dst[0].coff + 4 * qg);
+                    acc[r] = ld4(at(a.src[3], pix, qg)) + (bs[0] + bs[1] + bs[2]);
+                    if (a.accumulate) acc[r] += ld4(at(a.dst[0], pix, qg));
                 }
             }
 #pragma unroll
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void cp_strip_kernel(CpArgs a) {
             for (int r = 0; r < CP_R; ++r) {
                 if (pa0 + r >= g.LA) break;
                 const long pix = pix0 + (long)r * g.SA;
-                *reinterpret_cast<f32x4 *>(a.dst[0].p + pix * a.dst[0].cs + a.dst[0].coff + 4 * qg) = acc[r];
+                st4(at_w(a.dst[0], pix, qg), acc[r]);
             }
         }
     }
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void cp_wgrad_kernel(CpWArgs a) {
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) {
         const int task = tl + rd * NT;
-        if (on && task < a.ntask) *reinterpret_cast<f32x4 *>(a.part + (row * a.ntask + task) * (4L * g.C4) + 4 * qg) = acc[rd];
+        if (on && task < a.ntask) st4(a.part + (row * a.ntask + task) * (4L * g.C4) + 4 * qg, acc[rd]);
     }
 }
 
@@ -347,8 +347,8 @@ __global__ __launch_bounds__(256) void cp_gate_kernel(somi_slice x, somi_slice y
     if (i >= n4) return;
     const long pix = i / C4;
     const int c = 4 * (int)(i - pix * C4);
-    *reinterpret_cast<f32x4 *>(out.p + pix * out.cs + out.coff + c) =
-        *reinterpret_cast<const f32x4 *>(x.p + pix * x.cs + x.coff + c) * *reinterpret_cast<const f32x4 *>(y.p + pix * y.cs + y.coff + c);
+    const f32x4 o = ld4(at_ch(x, pix, c)) * ld4(at_ch(y, pix, c));
+    st4(at_ch_w(out, pix, c), o);
 }
 
 __global__ __launch_bounds__(256) void cp_gate_bwd_kernel(somi_slice dout, somi_slice x, somi_slice y, somi_slice dx, somi_slice dy, long n4, int C4) {
@@ -356,11 +356,11 @@ __global__ __launch_bounds__(256) void cp_gate_bwd_kernel(somi_slice dout, somi_
     if (i >= n4) return;
     const long pix = i / C4;
     const int c = 4 * (int)(i - pix * C4);
-    const f32x4 d = *reinterpret_cast<const f32x4 *>(dout.p + pix * dout.cs + dout.coff + c);
-    const f32x4 xv = *reinterpret_cast<const f32x4 *>(x.p + pix * x.cs + x.coff + c);
-    const f32x4 yv = *reinterpret_cast<const f32x4 *>(y.p + pix * y.cs + y.coff + c);
-    *reinterpret_cast<f32x4 *>(dx.p + pix * dx.cs + dx.coff + c) = d * yv;
-    *reinterpret_cast<f32x4 *>(dy.p + pix * dy.cs + dy.coff + c) = d * xv;
+    const f32x4 d = ld4(at_ch(dout, pix, c));
+    const f32x4 xv = ld4(at_ch(x, pix, c));
+    const f32x4 yv = ld4(at_ch(y, pix, c));
+    st4(at_ch_w(dx, pix, c), d * yv);
+    st4(at_ch_w(dy, pix, c), d * xv);
 }
 
 // g[b][c] = sigmoid(z[b][c]) + sigmoid(z[B + b][c]);  backward: dz[b] = dg s1 (1 - s1), dz[B + b] = dg s2 (1 - s2)

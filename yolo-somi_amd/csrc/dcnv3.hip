@@ -48,10 +48,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct DcnArgs {
     const float *input, *offset, *mask, *grad_output;
     float *output, *grad_input, *grad_offset, *grad_mask;

@@ -6,12 +6,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_grad(float v) {               // d/dv [0.5 v (1 + erf(v/sqrt2))]
-    return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
-}
-
 // z = gelu(LN(u)):  one wave per pixel row.  du = rstd * (g - mean(g) - xhat * mean(g * xhat)) with g = dz * gelu'(v) * gamma;
 // per-row-block partial sums of dgamma = sum g0 * xhat, dbeta = sum g0 (g0 = dz * gelu'(v)) go to part[blk][2][C].
 __global__ __launch_bounds__(256) void ln_gelu_bwd_kernel(const float *__restrict__ u, const float *__restrict__ gamma,

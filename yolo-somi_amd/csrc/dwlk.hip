@@ -28,8 +28,6 @@ constexpr int DL_G = 2;                                           // inputs load
 constexpr int DL_FWD_BLOCKS = 2048, DL_WGRAD_BLOCKS = 512;        // about this many workgroups in all
 constexpr int DL_MAX_ITERS = 64;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 struct DPlan {
     int nq, pp, iters, nblk, nchunk;
     unsigned nstrip, nitem;
@@ -51,36 +49,16 @@ static DPlan dplan(int B, int H, int W, int C, int want) {
     return p;
 }
 
-// sum of a float4 over the lanes of a workgroup that share a quad -> threads t < nq (others: garbage); red: 4 waves x 64 float4
-__device__ __forceinline__ f4 quad_sum(f4 v, int nq, f4 *red) {
-    for (int off = nq; off < 64; off <<= 1)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += __shfl_xor(v[e], off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < nq) red[wave * 64 + lane] = v;
-    __syncthreads();
-    f4 s = v;
-    if (threadIdx.x < nq) {
-        s = red[threadIdx.x];
-#pragma unroll
-        for (int wv = 1; wv < DL_THREADS / 64; ++wv) s += red[wv * 64 + threadIdx.x];
-    }
-    __syncthreads();
-    return s;
-}
-
-__device__ __forceinline__ f4 ld4(const float *p) { return *reinterpret_cast<const f4 *>(p); }
-
 // DL_G adjacent pixels of an image row, zero outside the row.  o: float index (relative to `base`, which is uniform over the workgroup; a
 // tensor is below 2^30 floats, check_size) of the first of them - it may lie outside the row -, advanced past the group; [lo, hi]: the
 // indices of the row's first and last pixel.  The index is clamped into the row and the value dropped where it was clamped: no branch, and
 // one running index in place of one address per pixel.
-__device__ __forceinline__ void load_group(f4 (&xv)[DL_G], const float *base, int &o, int lo, int hi, int cs) {
+__device__ __forceinline__ void load_group(f32x4 (&xv)[DL_G], const float *base, int &o, int lo, int hi, int cs) {
 #pragma unroll
     for (int i = 0; i < DL_G; ++i) {
         const int oc = min(max(o, lo), hi);
-        const f4 v = ld4(base + (unsigned)oc);
-        xv[i] = o == oc ? v : f4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 v = ld4(base + (unsigned)oc);
+        xv[i] = o == oc ? v : f32x4{0.f, 0.f, 0.f, 0.f};
         o += cs;
     }
 }
@@ -96,14 +74,14 @@ struct StencilArgs {
 // at four (128) the compiler spills 22 - 44 registers, some inside the tap loop, and the kernel is 1.2 - 1.8x slower.
 template <int K, int ACT, bool STATS>
 __global__ __launch_bounds__(DL_THREADS, 3) void dwlk_stencil_kernel(StencilArgs a) {
-    __shared__ f4 stage[DL_T][DL_THREADS];
+    __shared__ f32x4 stage[DL_T][DL_THREADS];
     constexpr int P = K / 2, NG = (DL_T + K - 1 + DL_G - 1) / DL_G;
-    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int ql = threadIdx.x % a.p.nq, psub = threadIdx.x / a.p.nq;
     const int c0 = (blockIdx.y * DL_MAXQ + ql) * 4;
     const bool active = c0 < a.C;
     constexpr bool stats = STATS;
-    f4 st1 = zero, st2 = zero;
+    f32x4 st1 = zero, st2 = zero;
     for (int it = 0; it < a.p.iters; ++it) {
         const unsigned item = (blockIdx.x * a.p.iters + it) * a.p.pp + psub;   // below 2^31 (check_size)
         if (!active || item >= a.p.nitem) continue;
@@ -111,7 +89,7 @@ __global__ __launch_bounds__(DL_THREADS, 3) void dwlk_stencil_kernel(StencilArgs
         const int h = (int)(row % a.H);
         const int w0 = (int)sw * DL_T;
         const float *xbase = a.x + a.x_coff;
-        f4 acc[DL_T];
+        f32x4 acc[DL_T];
 #pragma unroll
         for (int t = 0; t < DL_T; ++t) acc[t] = zero;
         const int r0 = h < P ? P - h : 0, r1 = a.H + P - h < K ? a.H + P - h : K;   // the tap rows inside the image
@@ -119,12 +97,12 @@ __global__ __launch_bounds__(DL_THREADS, 3) void dwlk_stencil_kernel(StencilArgs
         for (int r = r0; r < r1; ++r) {
             const int hi = h - P + r;
             const float *wr = a.w + (size_t)((a.flip ? K - 1 - r : r) * K) * a.w_cs + c0;
-            f4 wt[K];
+            f32x4 wt[K];
 #pragma unroll
             for (int q = 0; q < K; ++q) wt[q] = ld4(wr + (size_t)(a.flip ? K - 1 - q : q) * a.w_cs);
             const int lo = (int)((row - h + hi) * a.W) * a.x_cs + c0, up = lo + (a.W - 1) * a.x_cs;
             int o = lo + (w0 - P) * a.x_cs;
-            f4 xv[2][DL_G];
+            f32x4 xv[2][DL_G];
             load_group(xv[0], xbase, o, lo, up, a.x_cs);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {                        // the next group's loads fly while this group's products issue
@@ -145,38 +123,38 @@ __global__ __launch_bounds__(DL_THREADS, 3) void dwlk_stencil_kernel(StencilArgs
         for (int t = 0; t < DL_T; ++t) stage[t][threadIdx.x] = acc[t];
         const size_t pix0 = (size_t)row * a.W + w0;
         const int nt = a.W - w0 < DL_T ? a.W - w0 : DL_T;
-        f4 bias = zero, ps = {1.f, 1.f, 1.f, 1.f}, pt = zero, piv = zero;
+        f32x4 bias = zero, ps = {1.f, 1.f, 1.f, 1.f}, pt = zero, piv = zero;
         if (a.bias) bias = ld4(a.bias + c0);
         if (!stats && a.ps) ps = ld4(a.ps + c0);
         if (!stats && a.pt) pt = ld4(a.pt + c0);
         if (stats && a.pivot) piv = ld4(a.pivot + c0);
 #pragma unroll 1
         for (int t = 0; t < nt; ++t) {
-            f4 v = stage[t][threadIdx.x] + bias;
+            f32x4 v = stage[t][threadIdx.x] + bias;
             const size_t pix = pix0 + t;
             float *yp = a.y + pix * a.y_cs + a.y_coff + c0;
-            if constexpr (stats) *reinterpret_cast<f4 *>(yp) = v; // the pre-activation is what is stored; the sums are of act(.)
+            if constexpr (stats) st4(yp, v); // the pre-activation is what is stored; the sums are of act(.)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = apply_act<ACT>(v[e]);
             if constexpr (stats) {
-                const f4 d = v - piv;
+                const f32x4 d = v - piv;
                 st1 += d;
                 st2 += d * d;
             } else {
                 v = v * ps + pt;
                 if (a.r1) v += ld4(a.r1 + pix * a.r1_cs + a.r1_coff + c0);
                 if (a.r2) v += ld4(a.r2 + pix * a.r2_cs + a.r2_coff + c0);
-                *reinterpret_cast<f4 *>(yp) = v;
+                st4(yp, v);
             }
         }
     }
     if constexpr (!stats) return;
     __syncthreads();                                              // the reduction reuses the staging rows
-    const f4 s1 = quad_sum(st1, a.p.nq, stage[0]);
-    const f4 s2 = quad_sum(st2, a.p.nq, stage[1]);
+    const f32x4 s1 = block_quad_sum<DL_THREADS>(st1, a.p.nq, stage[0]);
+    const f32x4 s2 = block_quad_sum<DL_THREADS>(st2, a.p.nq, stage[1]);
     if (threadIdx.x < a.p.nq && active) {
-        *reinterpret_cast<f4 *>(a.ssum + (size_t)blockIdx.x * a.C + c0) = s1;
-        *reinterpret_cast<f4 *>(a.ssq + (size_t)blockIdx.x * a.C + c0) = s2;
+        st4(a.ssum + (size_t)blockIdx.x * a.C + c0, s1);
+        st4(a.ssq + (size_t)blockIdx.x * a.C + c0, s2);
     }
 }
 
@@ -190,16 +168,16 @@ struct WgradArgs {
 // stage 1: one row of partial sums per workgroup, part[row][(tap | K * K: the bias) * C + c]
 template <int K>
 __global__ __launch_bounds__(DL_THREADS, 4) void dwlk_wgrad_kernel(WgradArgs a) {
-    __shared__ f4 red[K + 1][DL_THREADS];
+    __shared__ f32x4 red[K + 1][DL_THREADS];
     constexpr int P = K / 2, NG = (DL_T + K - 1 + DL_G - 1) / DL_G;
-    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int ql = threadIdx.x % a.p.nq, psub = threadIdx.x / a.p.nq;
     const int c0 = (blockIdx.y * DL_MAXQ + ql) * 4;
     const bool active = c0 < a.C;
     float *prow = a.part + (size_t)blockIdx.x * (K * K + 1) * a.C;
 #pragma unroll 1
     for (int r = 0; r < K; ++r) {
-        f4 acc[K], bsum = zero;
+        f32x4 acc[K], bsum = zero;
 #pragma unroll
         for (int q = 0; q < K; ++q) acc[q] = zero;
         for (int it = 0; it < a.p.iters; ++it) {
@@ -211,7 +189,7 @@ __global__ __launch_bounds__(DL_THREADS, 4) void dwlk_wgrad_kernel(WgradArgs a) 
             const int hi = h - P + r;
             if (r != 0 && (hi < 0 || hi >= a.H)) continue;
             const float *dp = a.dy + ((size_t)row * a.W + w0) * a.dy_cs + a.dy_coff + c0;
-            f4 d[DL_T];
+            f32x4 d[DL_T];
 #pragma unroll
             for (int t = 0; t < DL_T; ++t) d[t] = w0 + t < a.W ? ld4(dp + (size_t)t * a.dy_cs) : zero;
             if (r == 0) {
@@ -222,7 +200,7 @@ __global__ __launch_bounds__(DL_THREADS, 4) void dwlk_wgrad_kernel(WgradArgs a) 
             const float *xbase = a.x + a.x_coff;
             const int lo = (int)((row - h + hi) * a.W) * a.x_cs + c0, up = lo + (a.W - 1) * a.x_cs;
             int o = lo + (w0 - P) * a.x_cs;
-            f4 xv[2][DL_G];
+            f32x4 xv[2][DL_G];
             load_group(xv[0], xbase, o, lo, up, a.x_cs);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
@@ -257,10 +235,10 @@ __global__ __launch_bounds__(DL_THREADS, 4) void dwlk_wgrad_kernel(WgradArgs a) 
 #pragma unroll
             for (int q = 0; q <= K; ++q) {
                 if (q == K && r != 0) break;
-                f4 s = red[q][threadIdx.x];
+                f32x4 s = red[q][threadIdx.x];
 #pragma unroll
                 for (int wv = 1; wv < DL_THREADS / 64; ++wv) s += red[q][wv * 64 + threadIdx.x];
-                *reinterpret_cast<f4 *>(prow + (size_t)(q == K ? K * K : r * K + q) * a.C + c0) = s;
+                st4(prow + (size_t)(q == K ? K * K : r * K + q) * a.C + c0, s);
             }
         }
         __syncthreads();

@@ -9,8 +9,8 @@
 //             place; and the row / column sums of dt * t, times (1 - sg): the gradient of conv1x1's output in sg's layout
 // x11 uses mean(x1) = beta (the mean of a normalised map is its shift); its gradient lands on beta alone, as autograd's does up to rounding.
 //
-// Geometry: coordatt.hip's.  A workgroup takes RH rows x NL columns of one image, lane (l, q) of its 256 = NL x QW owns column w0 + l and channel
-// quad q and walks the rows four at a time.  A group of cg channels is L = cg / 4 adjacent lanes: the reduction over a group goes through LDS,
+// Geometry: the map pass of common.h (map_plan, map_lane): a workgroup takes RH rows x NL columns of one image, lane (l, q) of its
+// 256 = NL x QW owns column w0 + l and channel quad q and walks the rows four at a time.  A group of cg channels is L = cg / 4 adjacent lanes: the reduction over a group goes through LDS,
 // every lane of the group adding the same L values in the same order, so all of them hold the same bits.  Reductions over the map: the lane
 // keeps its column's sum over the rows it walks, the workgroup adds its NL columns in order through LDS and writes one partial per (b, c); a
 // second launch folds the partials in order.  No float atomics: two launches are bit-identical.
@@ -23,33 +23,11 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int EM_RU = 4;          // rows in flight per lane
 constexpr int EM_MAX_CG = 64;     // channels of a group: at most 16 lanes
 
-struct EmPlan {
-    int QW, NL;                   // quads and columns of a workgroup: QW * NL <= 256
-    int nQc, nWc, nHc, RH;        // quad chunks (C / 4 > 256 only), column chunks, row chunks, rows per chunk
-};
-
-static EmPlan em_plan(int B, int H, int W, int C) {
-    EmPlan p;
-    const int C4 = C / 4;
-    p.QW = C4 < 256 ? C4 : 256;
-    p.NL = 256 / p.QW;
-    p.nQc = cdiv(C4, 256);
-    p.nWc = cdiv(W, p.NL);
-    p.RH = 32;
-    while (p.RH > EM_RU && (long)B * p.nQc * p.nWc * cdiv(H, p.RH) < 1024) p.RH /= 2;
-    p.nHc = cdiv(H, p.RH);
-    return p;
-}
-
-struct EmSl { float *p; int cs, coff; };
-
 struct EmArgs {
-    EmSl x, x2, sg, y, res, dx, dw, dsg;
+    somi_slice x, x2, sg, y, res, dx, dw, dsg;
     const float *gamma, *beta;
     float *stats, *vec, *sums, *bvec, *dgamma, *dbeta;
     float *part, *rowpart, *colpart;
@@ -58,29 +36,12 @@ struct EmArgs {
     int B, H, W, C4, L, QW, NL, nQc, nWc, nHc, RH, nP;
 };
 
-struct EmLane { int b, q, w, h0, h1; bool on; };
-
-__device__ __forceinline__ EmLane em_lane(const EmArgs &a) {
-    EmLane l;
-    const int t = threadIdx.x, lane = t / a.QW;
-    l.b = blockIdx.z / a.nQc;
-    l.q = (blockIdx.z - l.b * a.nQc) * 256 + (t - lane * a.QW);
-    l.w = blockIdx.x * a.NL + lane;
-    l.h0 = blockIdx.y * a.RH;
-    l.h1 = min(a.H, l.h0 + a.RH);
-    l.on = lane < a.NL && l.q < a.C4 && l.w < a.W;
-    return l;
-}
-
-__device__ __forceinline__ f32x4 em_ld(const EmSl &s, long pix, int q) { return *reinterpret_cast<const f32x4 *>(s.p + pix * s.cs + s.coff + 4 * q); }
-__device__ __forceinline__ void em_st(const EmSl &s, long pix, int q, f32x4 v) { *reinterpret_cast<f32x4 *>(s.p + pix * s.cs + s.coff + 4 * q) = v; }
-__device__ __forceinline__ f32x4 em_vec(const float *p, long row, int C4, int q) { return *reinterpret_cast<const f32x4 *>(p + (row * C4 + q) * 4); }
+__device__ __forceinline__ f32x4 em_vec(const float *p, long row, int C4, int q) { return ld4(p + (row * C4 + q) * 4); }
 __device__ __forceinline__ float em_sum4(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ f32x4 em_splat(float v) { return f32x4{v, v, v, v}; }
 
 // the workgroup's NL columns added in order, one partial per (b, partial, k, c): part[((b * nP + p) * K + k) * C + c]
 template <int K>
-__device__ __forceinline__ void em_fold_columns(const EmArgs &a, const EmLane &l, f32x4 (*sm)[256], const f32x4 (&s)[K]) {
+__device__ __forceinline__ void em_fold_columns(const EmArgs &a, const MapLane &l, f32x4 (*sm)[256], const f32x4 (&s)[K]) {
     const int t = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < K; ++k) sm[k][t] = s[k];
@@ -92,7 +53,7 @@ __device__ __forceinline__ void em_fold_columns(const EmArgs &a, const EmLane &l
         for (int k = 0; k < K; ++k) {
             f32x4 r = sm[k][t];
             for (int c = 1; c < a.NL; ++c) r += sm[k][c * a.QW + t];
-            *reinterpret_cast<f32x4 *>(a.part + ((p * K + k) * a.C4 + q) * 4) = r;
+            st4(a.part + ((p * K + k) * a.C4 + q) * 4, r);
         }
     }
 }
@@ -100,13 +61,13 @@ __device__ __forceinline__ void em_fold_columns(const EmArgs &a, const EmLane &l
 // ------------------------------------------------------------------------------------------------ statistics
 __global__ __launch_bounds__(256) void em_stats_kernel(EmArgs a) {
     __shared__ f32x4 sm[3][256];
-    const EmLane l = em_lane(a);
+    const MapLane l = map_lane(a);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 s[3] = {zero, zero, zero};
     if (l.on) {
         const long row0 = (long)l.b * (a.H + a.W);
-        const f32x4 piv = em_ld(a.x, (long)l.b * a.H * a.W, l.q) * em_ld(a.sg, row0, l.q) * em_ld(a.sg, row0 + a.H, l.q);
-        const f32x4 sw = em_ld(a.sg, row0 + a.H + l.w, l.q);
+        const f32x4 piv = ld4(at(a.x, (long)l.b * a.H * a.W, l.q)) * ld4(at(a.sg, row0, l.q)) * ld4(at(a.sg, row0 + a.H, l.q));
+        const f32x4 sw = ld4(at(a.sg, row0 + a.H + l.w, l.q));
         for (int g = l.h0; g < l.h1; g += EM_RU) {
             f32x4 v[EM_RU], sh[EM_RU], v2[EM_RU];
 #pragma unroll
@@ -114,9 +75,9 @@ __global__ __launch_bounds__(256) void em_stats_kernel(EmArgs a) {
                 v[r] = sh[r] = v2[r] = zero;
                 if (g + r < l.h1) {
                     const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                    v[r] = em_ld(a.x, pix, l.q);
-                    sh[r] = em_ld(a.sg, row0 + g + r, l.q);
-                    if (a.x2.p) v2[r] = em_ld(a.x2, pix, l.q);
+                    v[r] = ld4(at(a.x, pix, l.q));
+                    sh[r] = ld4(at(a.sg, row0 + g + r, l.q));
+                    if (a.x2.p) v2[r] = ld4(at(a.x2, pix, l.q));
                 }
             }
 #pragma unroll
@@ -143,14 +104,14 @@ __global__ __launch_bounds__(256) void em_stats_finish_kernel(EmArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] += em_vec(a.part, ((long)b * a.nP + p) * 3 + k, a.C4, q);
     const long row0 = (long)b * (a.H + a.W);
-    const f32x4 piv = em_ld(a.x, (long)b * a.H * a.W, q) * em_ld(a.sg, row0, q) * em_ld(a.sg, row0 + a.H, q);
+    const f32x4 piv = ld4(at(a.x, (long)b * a.H * a.W, q)) * ld4(at(a.sg, row0, q)) * ld4(at(a.sg, row0 + a.H, q));
     const float n = (float)a.H * (float)a.W;
     f32x4 m2 = s[1] - s[0] * s[0] / n;
     m2.x = fmaxf(m2.x, 0.f); m2.y = fmaxf(m2.y, 0.f); m2.z = fmaxf(m2.z, 0.f); m2.w = fmaxf(m2.w, 0.f);
     float *o = a.stats + (long)b * 3 * a.C4 * 4 + 4 * q;
-    *reinterpret_cast<f32x4 *>(o) = piv + s[0] / n;
-    *reinterpret_cast<f32x4 *>(o + a.C4 * 4) = m2;
-    *reinterpret_cast<f32x4 *>(o + 2 * a.C4 * 4) = s[2] / n;
+    st4(o, piv + s[0] / n);
+    st4(o + a.C4 * 4, m2);
+    st4(o + 2 * a.C4 * 4, s[2] / n);
 }
 
 // softmax over the cg values v[j0 .. j0 + cg) (stride 1), the maximum subtracted: the value at j
@@ -183,7 +144,7 @@ __global__ __launch_bounds__(256) void em_gate_kernel(EmArgs a) {
     __shared__ float sred[BWD ? 2 : 1][EM_RU][256];
     __shared__ f32x4 sm[BWD ? 3 : 1][256];
     const int t = threadIdx.x;
-    const EmLane l = em_lane(a);
+    const MapLane l = map_lane(a);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int gb = t - (l.q % a.L);                                // the first lane of this lane's group
     f32x4 mean = zero, rstd = zero, x21 = zero, x11 = zero, gam = zero, bet = zero, sw = zero;
@@ -194,9 +155,9 @@ __global__ __launch_bounds__(256) void em_gate_kernel(EmArgs a) {
         rstd = em_vec(a.vec, (long)l.b * 4 + 1, a.C4, l.q);
         x21 = em_vec(a.vec, (long)l.b * 4 + 2, a.C4, l.q);
         x11 = em_vec(a.vec, (long)l.b * 4 + 3, a.C4, l.q);
-        gam = *reinterpret_cast<const f32x4 *>(a.gamma + 4 * (l.q % a.L));
-        bet = *reinterpret_cast<const f32x4 *>(a.beta + 4 * (l.q % a.L));
-        sw = em_ld(a.sg, row0 + a.H + l.w, l.q);
+        gam = ld4(a.gamma + 4 * (l.q % a.L));
+        bet = ld4(a.beta + 4 * (l.q % a.L));
+        sw = ld4(at(a.sg, row0 + a.H + l.w, l.q));
     }
     const bool add = BWD ? a.accumulate != 0 : a.res.p != nullptr;
     for (int g = l.h0; g < l.h1; g += EM_RU) {
@@ -206,11 +167,11 @@ __global__ __launch_bounds__(256) void em_gate_kernel(EmArgs a) {
             v[r] = v2[r] = th[r] = d[r] = e[r] = zero;
             if (l.on && g + r < l.h1) {
                 const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                v[r] = em_ld(a.x, pix, l.q);
-                v2[r] = em_ld(a.x2, pix, l.q);
-                th[r] = em_ld(a.sg, row0 + g + r, l.q);
-                if (BWD) d[r] = em_ld(a.y, pix, l.q);
-                if (add) e[r] = BWD ? em_ld(a.dx, pix, l.q) : em_ld(a.res, pix, l.q);
+                v[r] = ld4(at(a.x, pix, l.q));
+                v2[r] = ld4(at(a.x2, pix, l.q));
+                th[r] = ld4(at(a.sg, row0 + g + r, l.q));
+                if (BWD) d[r] = ld4(at(a.y, pix, l.q));
+                if (add) e[r] = BWD ? ld4(at(a.dx, pix, l.q)) : ld4(at(a.res, pix, l.q));
             }
         }
 #pragma unroll
@@ -229,15 +190,17 @@ __global__ __launch_bounds__(256) void em_gate_kernel(EmArgs a) {
             for (int k = 1; k < a.L; ++k) wgt += sred[0][r][gb + k];
             const float sig = sigmoidf_(wgt);
             if (!BWD) {
-                em_st(a.y, pix, l.q, v[r] * sig + e[r]);
+                const f32x4 o = v[r] * sig + e[r];
+                st4(at_w(a.y, pix, l.q), o);
             } else {
                 float dd = sred[1][r][gb];
                 for (int k = 1; k < a.L; ++k) dd += sred[1][r][gb + k];
                 const float dwgt = dd * (sig * (1.0f - sig));
-                em_st(a.dx, pix, l.q, d[r] * sig + e[r]);
-                em_st(a.dw, pix, l.q, em_splat(dwgt));
+                const f32x4 o = d[r] * sig + e[r];
+                st4(at_w(a.dx, pix, l.q), o);
+                st4(at_w(a.dw, pix, l.q), splat4(dwgt));
                 s[0] += dwgt * th[r];
-                s[1] += em_splat(dwgt);
+                s[1] += splat4(dwgt);
                 s[2] += dwgt * v2[r];
             }
         }
@@ -257,7 +220,7 @@ __global__ __launch_bounds__(256) void em_sums_finish_kernel(EmArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) s[k] += em_vec(a.part, ((long)b * a.nP + p) * 3 + k, a.C4, q);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) *reinterpret_cast<f32x4 *>(a.sums + (((long)b * 3 + k) * a.C4 + q) * 4) = s[k];
+    for (int k = 0; k < 3; ++k) st4(a.sums + (((long)b * 3 + k) * a.C4 + q) * 4, s[k]);
 }
 
 // one lane per (b, c): bvec (B, 3, C) = c2 (what every pixel of dx2 gets from the softmax over mean x2), mean dx1, mean (dx1 * that)
@@ -315,7 +278,7 @@ __global__ __launch_bounds__(256) void em_param_grads_kernel(EmArgs a) {
 __global__ __launch_bounds__(256) void em_norm_bwd_kernel(EmArgs a) {
     __shared__ f32x4 srow[EM_RU][256];
     const int t = threadIdx.x;
-    const EmLane l = em_lane(a);
+    const MapLane l = map_lane(a);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 mean = zero, rstd = zero, x21 = zero, x11 = zero, gam = zero, c2 = zero, k1 = zero, k2 = zero, sw = zero, col = zero;
     const long row0 = (long)l.b * (a.H + a.W);
@@ -327,8 +290,8 @@ __global__ __launch_bounds__(256) void em_norm_bwd_kernel(EmArgs a) {
         c2 = em_vec(a.bvec, (long)l.b * 3, a.C4, l.q);
         k1 = em_vec(a.bvec, (long)l.b * 3 + 1, a.C4, l.q);
         k2 = em_vec(a.bvec, (long)l.b * 3 + 2, a.C4, l.q);
-        gam = *reinterpret_cast<const f32x4 *>(a.gamma + 4 * (l.q % a.L));
-        sw = em_ld(a.sg, row0 + a.H + l.w, l.q);
+        gam = ld4(a.gamma + 4 * (l.q % a.L));
+        sw = ld4(at(a.sg, row0 + a.H + l.w, l.q));
     }
     for (int g = l.h0; g < l.h1; g += EM_RU) {
         f32x4 v[EM_RU], dwg[EM_RU], sh[EM_RU];
@@ -337,9 +300,9 @@ __global__ __launch_bounds__(256) void em_norm_bwd_kernel(EmArgs a) {
             v[r] = dwg[r] = sh[r] = zero;
             if (l.on && g + r < l.h1) {
                 const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                v[r] = em_ld(a.x, pix, l.q);
-                dwg[r] = em_ld(a.dw, pix, l.q);
-                sh[r] = em_ld(a.sg, row0 + g + r, l.q);
+                v[r] = ld4(at(a.x, pix, l.q));
+                dwg[r] = ld4(at(a.dw, pix, l.q));
+                sh[r] = ld4(at(a.sg, row0 + g + r, l.q));
             }
         }
 #pragma unroll
@@ -352,8 +315,9 @@ __global__ __launch_bounds__(256) void em_norm_bwd_kernel(EmArgs a) {
             srow[r][t] = u;
             if (l.on && g + r < l.h1) {
                 const long pix = ((long)l.b * a.H + g + r) * a.W + l.w;
-                em_st(a.y, pix, l.q, dt);
-                em_st(a.dw, pix, l.q, dwg[r] * x11 + c2);
+                const f32x4 dx2 = dwg[r] * x11 + c2;
+                st4(at_w(a.y, pix, l.q), dt);
+                st4(at_w(a.dw, pix, l.q), dx2);
                 col += u;
             }
         }
@@ -364,12 +328,12 @@ __global__ __launch_bounds__(256) void em_norm_bwd_kernel(EmArgs a) {
             if (g + r < l.h1 && q < a.C4) {
                 f32x4 s = srow[r][qq];
                 for (int k = 1; k < a.NL; ++k) s += srow[r][k * a.QW + qq];
-                *reinterpret_cast<f32x4 *>(a.rowpart + (((long)l.b * a.H + g + r) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * q) = s;
+                st4(a.rowpart + (((long)l.b * a.H + g + r) * a.nWc + blockIdx.x) * (4 * a.C4) + 4 * q, s);
             }
         }
         __syncthreads();
     }
-    if (l.on) *reinterpret_cast<f32x4 *>(a.colpart + (((long)l.b * a.nHc + blockIdx.y) * a.W + l.w) * (4 * a.C4) + 4 * l.q) = col;
+    if (l.on) st4(a.colpart + (((long)l.b * a.nHc + blockIdx.y) * a.W + l.w) * (4 * a.C4) + 4 * l.q, col);
 }
 
 // one lane per (b, row of the (H + W)-row layout, quad): its partials in order, times (1 - sg): d t / d hw = t (1 - sigmoid(hw))
@@ -382,26 +346,25 @@ __global__ __launch_bounds__(256) void em_norm_bwd_finish_kernel(EmArgs a) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (r < a.H) {
         const float *p = a.rowpart + ((long)b * a.H + r) * a.nWc * (4 * a.C4) + 4 * q;
-        for (int k = 0; k < a.nWc; ++k) s += *reinterpret_cast<const f32x4 *>(p + (long)k * (4 * a.C4));
+        for (int k = 0; k < a.nWc; ++k) s += ld4(p + (long)k * (4 * a.C4));
     } else {
         const float *p = a.colpart + ((long)b * a.nHc * a.W + (r - a.H)) * (4 * a.C4) + 4 * q;
-        for (int k = 0; k < a.nHc; ++k) s += *reinterpret_cast<const f32x4 *>(p + (long)k * a.W * (4 * a.C4));
+        for (int k = 0; k < a.nHc; ++k) s += ld4(p + (long)k * a.W * (4 * a.C4));
     }
-    em_st(a.dsg, br, q, s * (1.0f - em_ld(a.sg, br, q)));
+    const f32x4 d = s * (1.0f - ld4(at(a.sg, br, q)));
+    st4(at_w(a.dsg, br, q), d);
 }
 
 enum EmOp { EM_STATS, EM_GATE, EM_BWD_GATE, EM_BWD_NORM };
 
-static EmSl em_sl(const somi_slice &s) { return EmSl{s.p, s.cs, s.coff}; }
-
 static size_t em_workspace_floats(int B, int H, int W, int C) {
-    const EmPlan p = em_plan(B, H, W, C);
+    const MapPlan p = map_plan(B, H, W, C, EM_RU);
     const size_t part = (size_t)B * p.nHc * p.nWc * 3 * C, rc = ((size_t)B * H * p.nWc + (size_t)B * p.nHc * W) * C;
     return part > rc ? part : rc;
 }
 
 // checks the descriptor for `op` and fills the kernel arguments; nothing is launched on an error
-static int em_unpack(const somi_ema_desc *d, EmOp op, EmArgs &a, EmPlan &p, const char *who) {
+static int em_unpack(const somi_ema_desc *d, EmOp op, EmArgs &a, MapPlan &p, const char *who) {
     SOMI_REQUIRE(d, SOMI_EINVAL, "%s: no descriptor", who);
     SOMI_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->C > 0 && d->factor > 0 && (long)d->B * d->H * d->W < (1L << 31) &&
                  (long)d->B * (d->H + d->W) * cdiv(d->C, 4) < (1L << 31) && (long)d->B * cdiv(cdiv(d->C, 4), 256) <= 65535 && d->H <= EM_RU * 65535,
@@ -439,10 +402,10 @@ static int em_unpack(const somi_ema_desc *d, EmOp op, EmArgs &a, EmPlan &p, cons
         SOMI_REQUIRE(d->workspace && aligned16(d->workspace), SOMI_EINVAL, "%s: a 16-byte aligned workspace is required", who);
         SOMI_REQUIRE(d->workspace_floats >= em_workspace_floats(d->B, d->H, d->W, C), SOMI_EWORKSPACE, "%s: workspace too small", who);
     }
-    p = em_plan(d->B, d->H, d->W, C);
+    p = map_plan(d->B, d->H, d->W, C, EM_RU);
     a = EmArgs{};
-    a.x = em_sl(d->x); a.x2 = em_sl(d->x2); a.sg = em_sl(d->sg); a.y = em_sl(d->y); a.res = em_sl(d->res);
-    a.dx = em_sl(d->dx); a.dw = em_sl(d->dw); a.dsg = em_sl(d->dsg);
+    a.x = d->x; a.x2 = d->x2; a.sg = d->sg; a.y = d->y; a.res = d->res;
+    a.dx = d->dx; a.dw = d->dw; a.dsg = d->dsg;
     a.gamma = d->gamma; a.beta = d->beta;
     a.stats = d->stats; a.vec = d->vec; a.sums = d->sums; a.bvec = d->bvec; a.dgamma = d->dgamma; a.dbeta = d->dbeta;
     a.part = a.rowpart = d->workspace;
@@ -454,7 +417,7 @@ static int em_unpack(const somi_ema_desc *d, EmOp op, EmArgs &a, EmPlan &p, cons
     return 0;
 }
 
-static dim3 em_grid(const somi_ema_desc *d, const EmPlan &p) { return dim3(p.nWc, p.nHc, d->B * p.nQc); }
+static dim3 em_grid(const somi_ema_desc *d, const MapPlan &p) { return dim3(p.nWc, p.nHc, d->B * p.nQc); }
 
 }  // namespace somi
 
@@ -468,13 +431,13 @@ extern "C" size_t somi_ema_workspace_floats(int B, int H, int W, int C) { return
 
 extern "C" int somi_ema_partials(int B, int H, int W, int C) {
     if (!em_sizes_ok(B, H, W, C)) return 0;
-    const EmPlan p = em_plan(B, H, W, C);
+    const MapPlan p = map_plan(B, H, W, C, EM_RU);
     return p.nHc * p.nWc;
 }
 
 extern "C" int somi_ema_stats_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream) {
     EmArgs a;
-    EmPlan p;
+    MapPlan p;
     if (int rc = em_unpack(d, EM_STATS, a, p, "ema stats")) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(em_stats_kernel, em_grid(d, p), dim3(256), 0, s, a);
@@ -485,7 +448,7 @@ extern "C" int somi_ema_stats_nhwc_f32(const somi_ema_desc *d, somi_stream_t str
 
 extern "C" int somi_ema_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream) {
     EmArgs a;
-    EmPlan p;
+    MapPlan p;
     if (int rc = em_unpack(d, EM_GATE, a, p, "ema gate")) return rc;
     hipLaunchKernelGGL(em_gate_kernel<false>, em_grid(d, p), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status("somi_ema_gate_nhwc_f32");
@@ -493,7 +456,7 @@ extern "C" int somi_ema_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stre
 
 extern "C" int somi_ema_bwd_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream) {
     EmArgs a;
-    EmPlan p;
+    MapPlan p;
     if (int rc = em_unpack(d, EM_BWD_GATE, a, p, "ema bwd gate")) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(em_gate_kernel<true>, em_grid(d, p), dim3(256), 0, s, a);
@@ -505,7 +468,7 @@ extern "C" int somi_ema_bwd_gate_nhwc_f32(const somi_ema_desc *d, somi_stream_t 
 
 extern "C" int somi_ema_bwd_norm_nhwc_f32(const somi_ema_desc *d, somi_stream_t stream) {
     EmArgs a;
-    EmPlan p;
+    MapPlan p;
     if (int rc = em_unpack(d, EM_BWD_NORM, a, p, "ema bwd norm")) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(em_norm_bwd_kernel, em_grid(d, p), dim3(256), 0, s, a);

@@ -18,8 +18,6 @@ constexpr int GC_THREADS = 256;
 constexpr int GC_MAXQ = 64;                                       // quads per channel chunk: 256 channels
 constexpr int GC_MAX_CIN_G = 16;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 struct GPlan {
     int nq, pp, iters, nblk, nchunk;
 };
@@ -54,42 +52,23 @@ struct FwdArgs {
     GPlan p;
 };
 
-// sum of a float4 over the lanes of a workgroup that share a quad: lanes (wave, ql + j*nq) -> lanes ql < nq of thread 0's wave
-// `red` holds 4 waves x 64 float4; returns the total in threads t < nq (others: garbage)
-__device__ __forceinline__ f4 block_quad_sum(f4 v, int nq, f4 *red) {
-    for (int off = nq; off < 64; off <<= 1)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += __shfl_xor(v[e], off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < nq) red[wave * 64 + lane] = v;
-    __syncthreads();
-    f4 s = v;
-    if (threadIdx.x < nq) {
-        s = red[threadIdx.x];
-#pragma unroll
-        for (int wv = 1; wv < GC_THREADS / 64; ++wv) s += red[wv * 64 + threadIdx.x];
-    }
-    __syncthreads();
-    return s;
-}
-
 template <int K, int S, bool DW>
 __global__ __launch_bounds__(GC_THREADS) void gconv_fwd_kernel(FwdArgs a) {
-    __shared__ f4 red[2][GC_THREADS];
+    __shared__ f32x4 red[2][GC_THREADS];
     constexpr int P = K / 2;
     const int ql = threadIdx.x % a.p.nq, psub = threadIdx.x / a.p.nq;
     const int co0 = (blockIdx.y * GC_MAXQ + ql) * 4;
     const bool active = co0 < a.Cw;
     const long npix = (long)a.B * a.Ho * a.Wo;
     const bool stats = a.ssum != nullptr;
-    f4 wreg[DW ? K * K : 1];
+    f32x4 wreg[DW ? K * K : 1];
     if constexpr (DW) {
 #pragma unroll
-        for (int t = 0; t < K * K; ++t) wreg[t] = active ? *reinterpret_cast<const f4 *>(a.w + (size_t)t * a.w_cs + co0) : f4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < K * K; ++t) wreg[t] = active ? ld4(a.w + (size_t)t * a.w_cs + co0) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    f4 bias = {0.f, 0.f, 0.f, 0.f}, piv = bias, st1 = bias, st2 = bias;
-    if (active && a.bias) bias = *reinterpret_cast<const f4 *>(a.bias + co0);
-    if (active && stats && a.pivot) piv = *reinterpret_cast<const f4 *>(a.pivot + co0);
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f}, piv = bias, st1 = bias, st2 = bias;
+    if (active && a.bias) bias = ld4(a.bias + co0);
+    if (active && stats && a.pivot) piv = ld4(a.pivot + co0);
     const bool load = active && co0 < a.C1;                      // quads of pad channels compute zeros (their weights are zero)
     for (int it = 0; it < a.p.iters; ++it) {
         const long pix = ((long)blockIdx.x * a.p.iters + it) * a.p.pp + psub;
@@ -97,7 +76,7 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_fwd_kernel(FwdArgs a) {
         const int wo = (int)(pix % a.Wo);
         const long t0 = pix / a.Wo;
         const int ho = (int)(t0 % a.Ho), b = (int)(t0 / a.Ho);
-        f4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         const float *xb = a.x + (size_t)b * a.H * a.W * a.x_cs + a.x_coff;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
@@ -109,7 +88,7 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_fwd_kernel(FwdArgs a) {
                 if (wi < 0 || wi >= a.W) continue;
                 const float *xp = xb + ((size_t)hi * a.W + wi) * a.x_cs;
                 if constexpr (DW) {
-                    if (load) acc += *reinterpret_cast<const f4 *>(xp + co0) * wreg[r * K + q];
+                    if (load) acc += ld4(xp + co0) * wreg[r * K + q];
                 } else {
                     const float *wt = a.w + (size_t)(r * K + q) * a.cin_g * a.w_cs;
 #pragma unroll
@@ -124,7 +103,7 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_fwd_kernel(FwdArgs a) {
                 }
             }
         }
-        f4 v = acc + bias;
+        f32x4 v = acc + bias;
         if (a.act == SOMI_ACT_SILU) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + __expf(-v[e]));
@@ -132,20 +111,20 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_fwd_kernel(FwdArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = apply_act_rt(v[e], a.act);
         }
-        if (a.res) v += *reinterpret_cast<const f4 *>(a.res + (size_t)pix * a.res_cs + a.res_coff + co0);
-        *reinterpret_cast<f4 *>(a.y + (size_t)pix * a.y_cs + a.y_coff + co0) = v;
+        if (a.res) v += ld4(a.res + (size_t)pix * a.res_cs + a.res_coff + co0);
+        st4(a.y + (size_t)pix * a.y_cs + a.y_coff + co0, v);
         if (stats) {
-            const f4 t = v - piv;
+            const f32x4 t = v - piv;
             st1 += t;
             st2 += t * t;
         }
     }
     if (!stats) return;                                           // uniform over the workgroup
-    const f4 s1 = block_quad_sum(st1, a.p.nq, red[0]);
-    const f4 s2 = block_quad_sum(st2, a.p.nq, red[1]);
+    const f32x4 s1 = block_quad_sum<GC_THREADS>(st1, a.p.nq, red[0]);
+    const f32x4 s2 = block_quad_sum<GC_THREADS>(st2, a.p.nq, red[1]);
     if (threadIdx.x < a.p.nq && active) {
-        *reinterpret_cast<f4 *>(a.ssum + (size_t)blockIdx.x * a.Cw + co0) = s1;
-        *reinterpret_cast<f4 *>(a.ssq + (size_t)blockIdx.x * a.Cw + co0) = s2;
+        st4(a.ssum + (size_t)blockIdx.x * a.Cw + co0, s1);
+        st4(a.ssq + (size_t)blockIdx.x * a.Cw + co0, s2);
     }
 }
 
@@ -171,7 +150,7 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_dgrad_kernel(DgradArgs a) {
         const int w = (int)(pix % a.W);
         const long t0 = pix / a.W;
         const int h = (int)(t0 % a.H), b = (int)(t0 / a.H);
-        f4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         const float *db = a.dy + (size_t)b * a.Ho * a.Wo * a.dy_cs + a.dy_coff;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
@@ -188,7 +167,7 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_dgrad_kernel(DgradArgs a) {
                 const float *dp = db + ((size_t)ho * a.Wo + wo) * a.dy_cs;
                 const float *wt = a.w + (size_t)(r * K + q) * a.cin_g * a.w_cs;
                 if constexpr (DW) {
-                    if (load) acc += *reinterpret_cast<const f4 *>(dp + ci0) * *reinterpret_cast<const f4 *>(wt + ci0);
+                    if (load) acc += ld4(dp + ci0) * ld4(wt + ci0);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -204,9 +183,9 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_dgrad_kernel(DgradArgs a) {
                 }
             }
         }
-        if (a.acc1) acc += *reinterpret_cast<const f4 *>(a.acc1 + (size_t)pix * a.acc1_cs + a.acc1_coff + ci0);
-        if (a.acc2) acc += *reinterpret_cast<const f4 *>(a.acc2 + (size_t)pix * a.acc2_cs + a.acc2_coff + ci0);
-        *reinterpret_cast<f4 *>(a.dx + (size_t)pix * a.dx_cs + a.dx_coff + ci0) = acc;
+        if (a.acc1) acc += ld4(a.acc1 + (size_t)pix * a.acc1_cs + a.acc1_coff + ci0);
+        if (a.acc2) acc += ld4(a.acc2 + (size_t)pix * a.acc2_cs + a.acc2_coff + ci0);
+        st4(a.dx + (size_t)pix * a.dx_cs + a.dx_coff + ci0, acc);
     }
 }
 
@@ -220,7 +199,7 @@ struct WgradArgs {
 // stage 1: one row of partial weight gradients per workgroup, part[row][(tap * cin_g + c) * C2r + co]
 template <int K, int S, bool DW>
 __global__ __launch_bounds__(GC_THREADS) void gconv_wgrad_kernel(WgradArgs a) {
-    __shared__ f4 red[GC_THREADS];
+    __shared__ f32x4 red[GC_THREADS];
     constexpr int P = K / 2, KK = K * K;
     const int ql = threadIdx.x % a.p.nq, psub = threadIdx.x / a.p.nq;
     const int co0 = (blockIdx.y * GC_MAXQ + ql) * 4;
@@ -229,16 +208,16 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_wgrad_kernel(WgradArgs a) {
     const long pix0 = (long)blockIdx.x * a.p.iters * a.p.pp + psub;
     float *row = a.part + (size_t)blockIdx.x * KK * a.cin_g * a.C2r;
     if constexpr (DW) {                                           // every tap at once: dy read once per pixel
-        f4 acc[KK];
+        f32x4 acc[KK];
 #pragma unroll
-        for (int t = 0; t < KK; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < KK; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int it = 0; it < a.p.iters; ++it) {
             const long pix = pix0 + (long)it * a.p.pp;
             if (!active || pix >= npix) break;
             const int wo = (int)(pix % a.Wo);
             const long t0 = pix / a.Wo;
             const int ho = (int)(t0 % a.Ho), b = (int)(t0 / a.Ho);
-            const f4 d = *reinterpret_cast<const f4 *>(a.dy + (size_t)pix * a.dy_cs + a.dy_coff + co0);
+            const f32x4 d = ld4(a.dy + (size_t)pix * a.dy_cs + a.dy_coff + co0);
             const float *xb = a.x + (size_t)b * a.H * a.W * a.x_cs + a.x_coff + co0;
 #pragma unroll
             for (int r = 0; r < K; ++r) {
@@ -248,20 +227,20 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_wgrad_kernel(WgradArgs a) {
                 for (int q = 0; q < K; ++q) {
                     const int wi = wo * S - P + q;
                     if (wi < 0 || wi >= a.W) continue;
-                    acc[r * K + q] += d * *reinterpret_cast<const f4 *>(xb + ((size_t)hi * a.W + wi) * a.x_cs);
+                    acc[r * K + q] += d * ld4(xb + ((size_t)hi * a.W + wi) * a.x_cs);
                 }
             }
         }
 #pragma unroll
         for (int t = 0; t < KK; ++t) {
-            const f4 s = block_quad_sum(acc[t], a.p.nq, red);
-            if (threadIdx.x < a.p.nq && active) *reinterpret_cast<f4 *>(row + (size_t)t * a.C2r + co0) = s;
+            const f32x4 s = block_quad_sum<GC_THREADS>(acc[t], a.p.nq, red);
+            if (threadIdx.x < a.p.nq && active) st4(row + (size_t)t * a.C2r + co0, s);
         }
     } else {
         for (int t = 0; t < KK; ++t) {
             const int r = t / K, q = t % K;
             for (int c = 0; c < a.cin_g; ++c) {
-                f4 acc = {0.f, 0.f, 0.f, 0.f};
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 for (int it = 0; it < a.p.iters; ++it) {
                     const long pix = pix0 + (long)it * a.p.pp;
                     if (!active || pix >= npix) break;
@@ -278,8 +257,8 @@ __global__ __launch_bounds__(GC_THREADS) void gconv_wgrad_kernel(WgradArgs a) {
                         if (co < a.C2) acc[e] += dp[co] * xp[(co / a.cout_g) * a.cin_g + c];
                     }
                 }
-                const f4 s = block_quad_sum(acc, a.p.nq, red);
-                if (threadIdx.x < a.p.nq && active) *reinterpret_cast<f4 *>(row + (size_t)(t * a.cin_g + c) * a.C2r + co0) = s;
+                const f32x4 s = block_quad_sum<GC_THREADS>(acc, a.p.nq, red);
+                if (threadIdx.x < a.p.nq && active) st4(row + (size_t)(t * a.cin_g + c) * a.C2r + co0, s);
             }
         }
     }

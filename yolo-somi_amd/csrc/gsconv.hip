@@ -23,9 +23,6 @@ constexpr int GS_BLOCKS = 2048;                                   // about this 
 // writes twice as long a run of every pixel's channel row
 constexpr int GS_TILE = 16, GS_TAILQ = 4, GS_WIDEQ = 8, GS_WIDE_TH = 8;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 struct GsPlan {
     int nq, pp, iters, nblk, nchunk;
 };
@@ -44,7 +41,7 @@ static GsPlan gs_plan(long npix, int Ch) {
     return p;
 }
 
-__device__ __forceinline__ f4 act4(f4 v, int act) {
+__device__ __forceinline__ f32x4 act4(f32x4 v, int act) {
     if (act == SOMI_ACT_SILU) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[e]));     // v_rcp_f32: 1 ulp, no division sequence
@@ -56,14 +53,14 @@ __device__ __forceinline__ f4 act4(f4 v, int act) {
 }
 
 // source quad J of one pixel -> its two places in the output row `o` (already at the pixel and the slice's offset), + the residual's
-__device__ __forceinline__ void store_shuffled(float *o, const float *r, int Ch, int J, f4 v) {
-    f2 ev = {v[0], v[2]}, od = {v[1], v[3]};
+__device__ __forceinline__ void store_shuffled(float *o, const float *r, int Ch, int J, f32x4 v) {
+    f32x2 ev = {v[0], v[2]}, od = {v[1], v[3]};
     if (r) {
-        ev += *reinterpret_cast<const f2 *>(r + 2 * J);
-        od += *reinterpret_cast<const f2 *>(r + Ch + 2 * J);
+        ev += *reinterpret_cast<const f32x2 *>(r + 2 * J);
+        od += *reinterpret_cast<const f32x2 *>(r + Ch + 2 * J);
     }
-    *reinterpret_cast<f2 *>(o + 2 * J) = ev;
-    *reinterpret_cast<f2 *>(o + Ch + 2 * J) = od;
+    *reinterpret_cast<f32x2 *>(o + 2 * J) = ev;
+    *reinterpret_cast<f32x2 *>(o + Ch + 2 * J) = od;
 }
 
 struct StreamArgs {
@@ -81,11 +78,11 @@ __global__ __launch_bounds__(GS_THREADS) void gs_stream_kernel(StreamArgs a) {
     if (J >= 2 * cq) return;
     const bool first = J < cq;
     const int c0 = (first ? J : J - cq) * 4;                      // the quad's first channel inside x1 / x_2
-    f4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
     const bool affine = !INVERSE && !first && a.scale;
     if (affine) {
-        sc = *reinterpret_cast<const f4 *>(a.scale + c0);
-        sh = *reinterpret_cast<const f4 *>(a.shift + c0);
+        sc = ld4(a.scale + c0);
+        sh = ld4(a.shift + c0);
     }
     const somi_slice half = first ? a.a : a.b;
     for (int it = 0; it < a.p.iters; ++it) {
@@ -94,10 +91,10 @@ __global__ __launch_bounds__(GS_THREADS) void gs_stream_kernel(StreamArgs a) {
         float *hp = half.p + (size_t)pix * half.cs + half.coff + c0;
         float *o = a.out.p + (size_t)pix * a.out.cs + a.out.coff;
         if constexpr (INVERSE) {
-            const f2 ev = *reinterpret_cast<const f2 *>(o + 2 * J), od = *reinterpret_cast<const f2 *>(o + a.Ch + 2 * J);
-            *reinterpret_cast<f4 *>(hp) = f4{ev[0], od[0], ev[1], od[1]};
+            const f32x2 ev = *reinterpret_cast<const f32x2 *>(o + 2 * J), od = *reinterpret_cast<const f32x2 *>(o + a.Ch + 2 * J);
+            st4(hp, f32x4{ev[0], od[0], ev[1], od[1]});
         } else {
-            f4 v = *reinterpret_cast<const f4 *>(hp);
+            f32x4 v = ld4(hp);
             if (!first) {
                 if (affine) v = v * sc + sh;
                 v = act4(v, a.act);
@@ -118,32 +115,32 @@ struct TailArgs {
 template <int QP, int TH, int TW>
 __global__ __launch_bounds__(GS_THREADS) void gs_tail_kernel(TailArgs a) {
     constexpr int XH = TH + 4, XW = TW + 4, UH = TH + 2, UW = TW + 2, NP = GS_THREADS / QP;
-    __shared__ f4 sx[XH * XW * QP];                               // x1, zero outside the image (dw1's padding)
-    __shared__ f4 st[UH * UW * QP];                               // t, zero outside the image (dw2's padding)
+    __shared__ f32x4 sx[XH * XW * QP];                            // x1, zero outside the image (dw1's padding)
+    __shared__ f32x4 st[UH * UW * QP];                            // t, zero outside the image (dw2's padding)
     const int ql = threadIdx.x % QP, lp = threadIdx.x / QP;
     const int cq = a.Ch / 4, q = (blockIdx.x % a.nchunk) * QP + ql;
     const bool active = q < cq;
     const int tile = blockIdx.x / a.nchunk;
     const int w0 = (tile % a.ntx) * TW, h0 = (tile / a.ntx % a.nty) * TH, b = tile / (a.ntx * a.nty);
-    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const size_t img = (size_t)b * a.H * a.W;
 
     for (int p = lp; p < XH * XW; p += NP) {
         const int h = h0 - 2 + p / XW, w = w0 - 2 + p % XW;
-        f4 v = zero;
+        f32x4 v = zero;
         if (active && h >= 0 && h < a.H && w >= 0 && w < a.W)
-            v = *reinterpret_cast<const f4 *>(a.x1.p + (img + (size_t)h * a.W + w) * a.x1.cs + a.x1.coff + q * 4);
+            v = ld4(a.x1.p + (img + (size_t)h * a.W + w) * a.x1.cs + a.x1.coff + q * 4);
         sx[p * QP + ql] = v;
     }
     __syncthreads();
 
-    f4 wr[9], bias = zero;
+    f32x4 wr[9], bias = zero;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wr[t] = active ? *reinterpret_cast<const f4 *>(a.w1 + (size_t)t * a.w_cs + q * 4) : zero;
-    if (active) bias = *reinterpret_cast<const f4 *>(a.b1 + q * 4);
+    for (int t = 0; t < 9; ++t) wr[t] = active ? ld4(a.w1 + (size_t)t * a.w_cs + q * 4) : zero;
+    if (active) bias = ld4(a.b1 + q * 4);
     for (int p = lp; p < UH * UW; p += NP) {
         const int r = p / UW, c = p % UW, h = h0 - 1 + r, w = w0 - 1 + c;
-        f4 v = zero;
+        f32x4 v = zero;
         if (active && h >= 0 && h < a.H && w >= 0 && w < a.W) {
             v = bias;
 #pragma unroll
@@ -157,12 +154,12 @@ __global__ __launch_bounds__(GS_THREADS) void gs_tail_kernel(TailArgs a) {
     __syncthreads();
 
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wr[t] = active ? *reinterpret_cast<const f4 *>(a.w2 + (size_t)t * a.w_cs + q * 4) : zero;
-    if (active) bias = *reinterpret_cast<const f4 *>(a.b2 + q * 4);
+    for (int t = 0; t < 9; ++t) wr[t] = active ? ld4(a.w2 + (size_t)t * a.w_cs + q * 4) : zero;
+    if (active) bias = ld4(a.b2 + q * 4);
     for (int p = lp; p < TH * TW; p += NP) {
         const int r = p / TW, c = p % TW, h = h0 + r, w = w0 + c;
         if (!active || h >= a.H || w >= a.W) continue;
-        f4 v = bias;
+        f32x4 v = bias;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll

@@ -6,8 +6,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 static inline int ew_grid(long items, int block = 256) {
     long g = (items + block - 1) / block;
     const long cap = 256L * 8;   // 8 workgroups per CU, grid-stride beyond that

@@ -5,8 +5,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void adam_ema_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
                                                        float *__restrict__ ema, long n, float lr, float b1, float b2, float eps, float wd,
                                                        float bc1, float bc2_sqrt, float ema_d) {

@@ -12,8 +12,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 static inline int pool_grid(long items) {
     long g = (items + 255) / 256;
     const long cap = 256L * 8;   // 8 workgroups per CU, grid-stride beyond that

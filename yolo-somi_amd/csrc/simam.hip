@@ -20,8 +20,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SA_K = 8;           // pixels a lane holds in registers: a chunk is SA_K * NL pixels
 constexpr int SA_COVER = 4;       // at most this many regions cover a pixel along one axis
 
@@ -35,9 +33,9 @@ struct SaPlan {
 };
 
 struct SaArgs {
-    const float *x; int x_cs, x_coff;
-    const float *y; int y_cs, y_coff;                  // dout of the two backward passes
-    float *out; int o_cs, o_coff;                      // apply: out;  bwd input: dx
+    somi_slice x;
+    somi_slice y;                                      // dout of the two backward passes
+    somi_slice out;                                    // apply: out;  bwd input: dx
     float *stats, *sums, *part;                        // part: per-chunk partials (nP > 1)
     int add_input, accumulate;
     SaGeom g;
@@ -48,10 +46,8 @@ static int sa_last_len(int size, int n, int step, int len, int stretch) { return
 
 static SaPlan sa_plan(int B, int H, int W, int C, int ny, int nx, int sy, int sx, int ly, int lx, int stretch) {
     SaPlan p;
-    const int C4 = C / 4;
-    p.QW = C4 < 256 ? C4 : 256;
-    p.NL = 256 / p.QW;
-    p.nQc = cdiv(C4, 256);
+    const MapShape s = map_shape(C);
+    p.QW = s.QW; p.NL = s.NL; p.nQc = s.nQc;
     p.R = ny * nx;
     const long nmax = (long)sa_last_len(H, ny, sy, ly, stretch) * sa_last_len(W, nx, sx, lx, stretch);
     p.nP = cdiv(nmax, (long)SA_K * p.NL);
@@ -93,8 +89,6 @@ __device__ __forceinline__ f32x4 sa_sigmoid(f32x4 u) {
     return s;
 }
 
-__device__ __forceinline__ f32x4 sa_ld(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-
 // (count, mean, M2) of two disjoint sets into the first; the counts depend on the lane or chunk only, never on the channel
 __device__ __forceinline__ void sa_merge(float &na, f32x4 &ma, f32x4 &qa, float nb, const f32x4 &mb, const f32x4 &qb) {
     if (nb == 0.f) return;
@@ -131,8 +125,8 @@ __global__ __launch_bounds__(256) void sa_reduce_kernel(SaArgs a) {
         float wgt[SA_K], cnt = 0.f;
         if (BWD && on) {
             const float *st = a.stats + ((long)b * R + r) * 2 * (4 * g.C4) + 4 * q;
-            mu = sa_ld(st);
-            dd = 4.0f * (sa_ld(st + 4 * g.C4) * g.inv_n + g.lambda);
+            mu = ld4(st);
+            dd = 4.0f * (ld4(st + 4 * g.C4) * g.inv_n + g.lambda);
         }
 #pragma unroll
         for (int k = 0; k < SA_K; ++k) {
@@ -142,9 +136,9 @@ __global__ __launch_bounds__(256) void sa_reduce_kernel(SaArgs a) {
             if (on && e < N) {
                 const int ey = e / rg.w, ex = e - ey * rg.w;
                 const long pix = ((long)b * g.H + rg.y0 + ey) * g.W + rg.x0 + ex;
-                v[k] = sa_ld(a.x + pix * a.x_cs + a.x_coff + 4 * q);
+                v[k] = ld4(at(a.x, pix, q));
                 if (BWD) {
-                    dv[k] = sa_ld(a.y + pix * a.y_cs + a.y_coff + 4 * q);
+                    dv[k] = ld4(at(a.y, pix, q));
                     wgt[k] = sa_weight(g, ri, rj, rg.y0 + ey, rg.x0 + ex);
                 }
                 cnt += 1.f;
@@ -191,8 +185,8 @@ __global__ __launch_bounds__(256) void sa_reduce_kernel(SaArgs a) {
         if (on && lane == 0) {
             float *dst = a.p.nP > 1 ? a.part + (((long)b * R + r) * a.p.nP + blockIdx.x) * 2 * (4 * g.C4)
                                     : (BWD ? a.sums : a.stats) + ((long)b * R + r) * 2 * (4 * g.C4);
-            *reinterpret_cast<f32x4 *>(dst + 4 * q) = m0;
-            *reinterpret_cast<f32x4 *>(dst + 4 * g.C4 + 4 * q) = m1;
+            st4(dst + 4 * q, m0);
+            st4(dst + 4 * g.C4 + 4 * q, m1);
         }
         __syncthreads();                                          // the next region reuses the LDS rows
     }
@@ -216,15 +210,15 @@ __global__ __launch_bounds__(256) void sa_reduce_finish_kernel(SaArgs a, int B) 
         const int have = min(chunk, N - k * chunk);
         if (have <= 0) break;                                     // a region smaller than the largest one has fewer chunks
         if (BWD) {
-            m0 += sa_ld(src);
-            m1 += sa_ld(src + 4 * g.C4);
+            m0 += ld4(src);
+            m1 += ld4(src + 4 * g.C4);
         } else {
-            sa_merge(cnt, m0, m1, (float)have, sa_ld(src), sa_ld(src + 4 * g.C4));
+            sa_merge(cnt, m0, m1, (float)have, ld4(src), ld4(src + 4 * g.C4));
         }
     }
     float *dst = (BWD ? a.sums : a.stats) + br * 2 * (4 * g.C4) + 4 * q;
-    *reinterpret_cast<f32x4 *>(dst) = m0;
-    *reinterpret_cast<f32x4 *>(dst + 4 * g.C4) = m1;
+    st4(dst, m0);
+    st4(dst + 4 * g.C4, m1);
 }
 
 // ------------------------------------------------------------------------------------------------ the two element-wise passes
@@ -240,9 +234,10 @@ __global__ __launch_bounds__(256) void sa_apply_kernel(SaArgs a, long total) {
     const long bh = pix / g.W;
     const int h = (int)(bh % g.H), b = (int)(bh / g.H);
     const int R = a.p.R;
-    const f32x4 x = sa_ld(a.x + pix * a.x_cs + a.x_coff + 4 * q);
+    // x and o spelled out: through at() the forward instance schedules differently
+    const f32x4 x = ld4(a.x.p + pix * a.x.cs + a.x.coff + 4 * q);
     f32x4 gr = {0.f, 0.f, 0.f, 0.f}, acc = gr;
-    if (BWD) gr = sa_ld(a.y + pix * a.y_cs + a.y_coff + 4 * q);
+    if (BWD) gr = ld4(at(a.y, pix, q));
     if (a.add_input) acc = BWD ? gr : x;
     const SaCover cy = sa_cover(h, g.sy, g.ly, g.ny, g.stretch), cx = sa_cover(w, g.sx, g.lx, g.nx, g.stretch);
     if (cy.n > 0 && cx.n > 0) {
@@ -252,8 +247,8 @@ __global__ __launch_bounds__(256) void sa_apply_kernel(SaArgs a, long total) {
                 const int r = i2 * g.nx + j2;
                 const float wgt = 1.0f / (float)(++k);
                 const float *st = a.stats + ((long)b * R + r) * 2 * (4 * g.C4) + 4 * q;
-                const f32x4 d = x - sa_ld(st), d2 = d * d;
-                const f32x4 dd = 4.0f * (sa_ld(st + 4 * g.C4) * g.inv_n + g.lambda);
+                const f32x4 d = x - ld4(st), d2 = d * d;
+                const f32x4 dd = 4.0f * (ld4(st + 4 * g.C4) * g.inv_n + g.lambda);
                 const f32x4 s = sa_sigmoid(d2 / dd + 0.5f);
                 if (!BWD) {
                     acc += wgt * x * s;
@@ -261,14 +256,14 @@ __global__ __launch_bounds__(256) void sa_apply_kernel(SaArgs a, long total) {
                     const SaRegion rg = sa_region(g, r);
                     const float *sm = a.sums + ((long)b * R + r) * 2 * (4 * g.C4) + 4 * q;
                     const f32x4 T = wgt * gr * x * s * (1.0f - s);
-                    acc += wgt * gr * s + 2.0f * T * d / dd - sa_ld(sm) * (2.0f / (float)(rg.h * rg.w)) / dd
-                           - (8.0f * g.inv_n) * d * sa_ld(sm + 4 * g.C4) / (dd * dd);
+                    acc += wgt * gr * s + 2.0f * T * d / dd - ld4(sm) * (2.0f / (float)(rg.h * rg.w)) / dd
+                           - (8.0f * g.inv_n) * d * ld4(sm + 4 * g.C4) / (dd * dd);
                 }
             }
     }
-    float *o = a.out + pix * a.o_cs + a.o_coff + 4 * q;
-    if (BWD && a.accumulate) acc += sa_ld(o);
-    *reinterpret_cast<f32x4 *>(o) = acc;
+    float *o = a.out.p + pix * a.out.cs + a.out.coff + 4 * q;
+    if (BWD && a.accumulate) acc += ld4(o);
+    st4(o, acc);
 }
 
 enum SaOp { SA_STATS, SA_APPLY, SA_SUMS_BWD, SA_INPUT_BWD };
@@ -307,10 +302,9 @@ static int sa_unpack(const somi_simam_desc *d, SaOp op, SaArgs &a, const char *w
         SOMI_REQUIRE(d->workspace && aligned16(d->workspace), SOMI_EINVAL, "%s: a 16-byte aligned workspace is required", who);
         SOMI_REQUIRE(d->workspace_floats >= somi_simam_workspace_floats(d), SOMI_EWORKSPACE, "%s: workspace too small", who);
     }
-    a.x = d->x.p; a.x_cs = d->x.cs; a.x_coff = d->x.coff;
-    a.y = d->y.p; a.y_cs = d->y.cs; a.y_coff = d->y.coff;
-    if (op == SA_APPLY) { a.out = d->y.p; a.o_cs = d->y.cs; a.o_coff = d->y.coff; }
-    if (op == SA_INPUT_BWD) { a.out = d->dx.p; a.o_cs = d->dx.cs; a.o_coff = d->dx.coff; }
+    a.x = d->x; a.y = d->y;
+    if (op == SA_APPLY) a.out = d->y;
+    if (op == SA_INPUT_BWD) a.out = d->dx;
     a.stats = d->stats; a.sums = d->sums; a.part = d->workspace;
     a.add_input = d->add_input; a.accumulate = d->accumulate;
     a.g = SaGeom{d->H, d->W, C / 4, d->ny, d->nx, d->step_y, d->step_x, d->len_y, d->len_x, d->stretch_last ? 1 : 0, 1.0f / d->n, d->lambda};

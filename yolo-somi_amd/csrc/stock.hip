@@ -11,8 +11,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 static inline int ew_grid(long items) {
     long g = (items + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));

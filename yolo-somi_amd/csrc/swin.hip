@@ -13,8 +13,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SW_N = 64;       // tokens per window
 constexpr int SW_HD = 32;      // head dim
 constexpr int SW_QS = 36;      // LDS row stride of q / k / v / dO: 16 rows 36 floats apart start in 16 different bank quads (ds_read_b128)
@@ -329,8 +327,7 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float *__restrict__
         const f32x4 v = reinterpret_cast<const f32x4 *>(u)[i], d = reinterpret_cast<const f32x4 *>(dy)[i];
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e)                                   // d/dv [0.5 v (1 + erf(v / sqrt 2))]
-            o[e] = d[e] * (0.5f * (1.f + erff(v[e] * 0.70710678118654752440f)) + v[e] * 0.39894228040143267794f * expf(-0.5f * v[e] * v[e]));
+        for (int e = 0; e < 4; ++e) o[e] = d[e] * gelu_grad(v[e]);
         reinterpret_cast<f32x4 *>(du)[i] = o;
     }
 }

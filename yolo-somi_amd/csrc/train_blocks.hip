@@ -14,7 +14,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int IMG_CHUNK = 256;       // pixels per workgroup in the per-image reductions
 
 static inline int ew_grid(long items) {

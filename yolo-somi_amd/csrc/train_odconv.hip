@@ -12,7 +12,6 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int ACT_SOFTMAX = 5;
 
 // y[b][y_off + o] = act(sum_i x[b][i] W[o][i] + bias[o]);  one workgroup per sample, one wave per output (strided)
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(64) void act_bwd_rows_kernel(const float *__restric
     float dot = 0.f;
     if (act == ACT_SOFTMAX) {
         for (int o = lane; o < ncol; o += 64) dot += dr[o] * yr[o];
-        for (int s = 32; s > 0; s >>= 1) dot += __shfl_xor(dot, s);
+        dot = wave_sum(dot);
     }
     for (int o = lane; o < ncol; o += 64) {
         const float v = yr[o], g = dr[o];
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(256) void linear_bwd_data_kernel(const float *__res
         const int b = (int)(e / nin), i = (int)(e % nin);
         float s = 0.f;
         for (int o = lane; o < nout; o += 64) s += dpre[(long)b * ldp + o] * W[(long)o * nin + i];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum(s);
         if (lane == 0) dx[(long)b * ldx + i] = (accumulate ? dx[(long)b * ldx + i] : 0.f) + s;
     }
 }

@@ -11,9 +11,6 @@
 #include "common.h"
 
 namespace somi {
-typedef int i32x4_ __attribute__((ext_vector_type(4)));
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // pixels per stage-1 workgroup: about 1024 chunks for large tensors (stage 2 walks the chunks), never fewer than 32 pixels (the 20x20 maps of
 // a batch of 32 are 12800 pixels: 128-pixel chunks left 156 of the 256 CUs without a workgroup)
@@ -424,7 +421,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_stage1_pooled(const float *__r
             // nullptr: no max-pool term
             const f32x4 kavg = *reinterpret_cast<const f32x4 *>(davg + (long)b * C + c) * inv_hw;
             const f32x4 kmax = dmax ? *reinterpret_cast<const f32x4 *>(dmax + (long)b * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const i32x4_ am = dmax ? *reinterpret_cast<const i32x4_ *>(amaxp + (long)b * C + c) : i32x4_{-1, -1, -1, -1};
+            const i32x4 am = dmax ? *reinterpret_cast<const i32x4 *>(amaxp + (long)b * C + c) : i32x4{-1, -1, -1, -1};
             const f32x4 mu = *reinterpret_cast<const f32x4 *>(mean + c), sc = *reinterpret_cast<const f32x4 *>(scale + c),
                         sh = *reinterpret_cast<const f32x4 *>(shift + c);
 #pragma unroll 4
@@ -479,7 +476,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_pooled(const float *dz, 
                 sc = *reinterpret_cast<const f32x4 *>(scale + c), sh = *reinterpret_cast<const f32x4 *>(shift + c);
     const f32x4 kavg = *reinterpret_cast<const f32x4 *>(davg + (long)b * C + c) * (1.f / (float)HW);
     const f32x4 kmax = dmax ? *reinterpret_cast<const f32x4 *>(dmax + (long)b * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const i32x4_ am = dmax ? *reinterpret_cast<const i32x4_ *>(amaxp + (long)b * C + c) : i32x4_{-1, -1, -1, -1};
+    const i32x4 am = dmax ? *reinterpret_cast<const i32x4 *>(amaxp + (long)b * C + c) : i32x4{-1, -1, -1, -1};
     const bool has_dz = dz != nullptr;
     if (has_dz) dz += (long)b * HW * dz_cs + dz_coff + c;
     x += (long)b * HW * x_cs + x_coff + c;
@@ -601,7 +598,7 @@ __global__ __launch_bounds__(256) void cbam_bn_bwd_reduce_kernel(CbamBnArgs a, f
                     a.sa[p], *reinterpret_cast<const float2 *>(a.dstats + p * 2), a.amaxc[p]);
             }
             if (rr == 0) {                                               // F: silu'(u) and silu'(u) (y - mean) at the arg-max pixel, by the chunk that holds it
-                const i32x4_ amp = *reinterpret_cast<const i32x4_ *>(a.amaxp + (long)b * C + c);
+                const i32x4 amp = *reinterpret_cast<const i32x4 *>(a.amaxp + (long)b * C + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (amp[e] >= q0 && amp[e] < q1) {
@@ -684,7 +681,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 cav = *reinterpret_cast<const f32x4 *>(a.ca + (long)b * C + c);
     const f32x4 kavg = *reinterpret_cast<const f32x4 *>(davg + (long)b * C + c) * (1.f / (float)HW);
     const f32x4 kmax = *reinterpret_cast<const f32x4 *>(dmax + (long)b * C + c);
-    const i32x4_ amp = *reinterpret_cast<const i32x4_ *>(a.amaxp + (long)b * C + c);
+    const i32x4 amp = *reinterpret_cast<const i32x4 *>(a.amaxp + (long)b * C + c);
     const float inv_c = 1.f / (float)C;
     const float *d = a.d + (long)b * HW * a.d_cs + a.d_coff + c, *y = a.y + (long)b * HW * a.y_cs + a.y_coff + c;
     const float *sa = a.sa + (long)b * HW, *dst = a.dstats + (long)b * HW * 2;

@@ -17,12 +17,9 @@
 
 namespace somi {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kUpTile = 8;      // source pixels per tile side
 constexpr int kUpChunk = 64;    // channels per LDS chunk: 16 quads
 
-__device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 
 // stages channels [c0, c0 + 64) of the (8+2R)^2 window around the tile into LDS as [wy][wx][64]; zero outside the map and beyond C
 template <int R>

@@ -79,6 +79,28 @@ def _f32c(t, name='tensor'):
     return t
 
 
+def _map(t, shape, what):
+    """t, once its leading (B, H, W) is known to be `shape`: a tuple, or a map whose sizes t must share."""
+    want = tuple(shape.shape[:3]) if torch.is_tensor(shape) else tuple(shape)
+    if tuple(t.shape[:3]) != want:
+        raise RuntimeError(f'{what} must be {want} + (channels,), got {tuple(t.shape)}')
+    return t
+
+
+def _check_impl(rc, what):
+    """check() for the entry points that refuse a configuration before any launch: that refusal is a NotImplementedError."""
+    if rc == -2:                                                  # SOMI_ENOTIMPL
+        raise NotImplementedError(f'{what}: {_lib.lib().somi_last_error().decode(errors="replace")}')
+    check(rc, what)
+
+
+def _scratch(d, floats, dev):
+    """A fresh float workspace of at least `floats` on descriptor d -> the tensor, which the caller keeps alive until the launch is enqueued."""
+    ws = torch.empty(max(floats, 4), device=dev, dtype=torch.float32)
+    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    return ws
+
+
 def conv_out_size(size, k, s, p, d=1):
     return (size + 2 * p - (d * (k - 1) + 1)) // s + 1
 
@@ -374,8 +396,7 @@ def maxpool3s2(x, c, x_coff=0, *, out=None, y_coff=0, codes=False):
     Ho, Wo = maxpool3s2_out_size(H), maxpool3s2_out_size(W)
     if out is None:
         out = torch.empty(B, Ho, Wo, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, Ho, Wo):
-        raise RuntimeError(f'maxpool3s2: output must be ({B}, {Ho}, {Wo}, .), got {tuple(out.shape)}')
+    _map(out, (B, Ho, Wo), 'maxpool3s2: output')
     arg = torch.empty(B * Ho * Wo * c, device=x.device, dtype=torch.uint8) if codes else None
     check(_lib.lib().somi_maxpool3s2_nhwc_f32(C.byref(_slice(x, x_coff)), C.byref(_slice(out, y_coff)), _ptr(arg), B, H, W, c, _stream()), 'maxpool3s2')
     return (out, arg) if codes else out
@@ -419,8 +440,7 @@ def asff_fuse(rs, vs, r_ups, v_ups, w, bias, c, *, out=None, o_coff=0, weights=F
     d, (B, H, W) = _asff_desc(rs, vs, r_ups, v_ups, w, bias, c, 'asff_fuse')
     if out is None:
         out = torch.empty(B, H, W, c, device=w.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'asff_fuse: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    _map(out, (B, H, W), 'asff_fuse: output')
     p = torch.empty(B, H, W, 3, device=w.device, dtype=torch.float32) if weights else None
     d.out, d.p = _slice(out, o_coff), _ptr(p)
     check(_lib.lib().somi_asff_fuse_nhwc_f32(C.byref(d), _stream()), 'asff_fuse')
@@ -467,23 +487,16 @@ def _coordatt_desc(B, H, W, c, a_h=None, a_w=None, what='coordatt'):
     return d
 
 
-def _coordatt_workspace(d, dev):
-    ws = torch.empty(max(_lib.lib().somi_coordatt_workspace_floats(d.B, d.H, d.W, d.C), 4), device=dev, dtype=torch.float32)
-    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
-    return ws
-
-
 def coordatt_means(x, c, x_coff=0, *, out=None, o_coff=0):
     """The two directional means of slice [x_coff, x_coff + c) of x (B,H,W,cs) -> out (B, H + W, 1, *) slice at o_coff: rows [0, H) the mean over W
     per (b, h, channel), rows [H, H + W) the mean over H per (b, w, channel) - the map coordinate attention's conv1 reads."""
     B, H, W, _ = x.shape
     if out is None:
         out = torch.empty(B, H + W, 1, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H + W, 1):
-        raise RuntimeError(f'coordatt_means: output must be ({B}, {H + W}, 1, .), got {tuple(out.shape)}')
+    _map(out, (B, H + W, 1), 'coordatt_means: output')
     d = _coordatt_desc(B, H, W, c)
     d.x, d.pool = _slice(x, x_coff), _slice(out, o_coff)
-    ws = _coordatt_workspace(d, x.device)                         # noqa: F841  (alive until the launch is enqueued)
+    ws = _scratch(d, _lib.lib().somi_coordatt_workspace_floats(d.B, d.H, d.W, d.C), x.device)    # noqa: F841  (alive until the launch is enqueued)
     check(_lib.lib().somi_coordatt_means_nhwc_f32(C.byref(d), _stream()), 'coordatt_means')
     return out
 
@@ -493,8 +506,9 @@ def coordatt_apply(x, a_h, a_w, c, x_coff=0, *, res=None, res_coff=0, out=None, 
     B, H, W, _ = x.shape
     if out is None:
         out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W) or (res is not None and tuple(res.shape[:3]) != (B, H, W)):
-        raise RuntimeError(f'coordatt_apply: output and shortcut must be ({B}, {H}, {W}, .)')
+    _map(out, (B, H, W), 'coordatt_apply: output')
+    if res is not None:
+        _map(res, (B, H, W), 'coordatt_apply: shortcut')
     d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_apply')
     d.x, d.y = _slice(x, x_coff), _slice(out, o_coff)
     if res is not None:
@@ -507,15 +521,14 @@ def coordatt_backward_gates(dout, x, a_h, a_w, c, do_coff=0, x_coff=0, *, da_h=N
     """da_h[b,h,:] = sum_w dout x a_w and da_w[b,w,:] = sum_h dout x a_h, written into the row tensors da_h / da_w ((B,H,c) and (B,W,c) tensors
     of their own when None).  -> (da_h tensor, da_w tensor)."""
     B, H, W, _ = x.shape
-    if tuple(dout.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'coordatt_backward_gates: dout must be ({B}, {H}, {W}, .), got {tuple(dout.shape)}')
+    _map(dout, (B, H, W), 'coordatt_backward_gates: dout')
     da_h = torch.empty(B, H, c, device=x.device, dtype=torch.float32) if da_h is None else da_h
     da_w = torch.empty(B, W, c, device=x.device, dtype=torch.float32) if da_w is None else da_w
     d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_backward_gates')
     d.x, d.y = _slice(x, x_coff), _slice(dout, do_coff)
     d.r_h, d.r_h_rows = _row_tensor(da_h, B, H, 'coordatt_backward_gates: da_h')
     d.r_w, d.r_w_rows = _row_tensor(da_w, B, W, 'coordatt_backward_gates: da_w')
-    ws = _coordatt_workspace(d, x.device)                         # noqa: F841
+    ws = _scratch(d, _lib.lib().somi_coordatt_workspace_floats(d.B, d.H, d.W, d.C), x.device)    # noqa: F841
     check(_lib.lib().somi_coordatt_bwd_gates_nhwc_f32(C.byref(d), _stream()), 'coordatt_backward_gates')
     first = lambda s: s[0] if isinstance(s, (tuple, list)) else s    # noqa: E731
     return first(da_h), first(da_w)
@@ -529,8 +542,7 @@ def coordatt_backward_input(dout, a_h, a_w, gh, gw, c, do_coff=0, *, out=None, d
         if accumulate:
             raise RuntimeError('coordatt_backward_input: accumulate needs the tensor to add to')
         out = torch.empty(B, H, W, c, device=dout.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'coordatt_backward_input: dx must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    _map(out, (B, H, W), 'coordatt_backward_input: dx')
     d = _coordatt_desc(B, H, W, c, a_h, a_w, 'coordatt_backward_input')
     d.y, d.dx, d.accumulate = _slice(dout, do_coff), _slice(out, dx_coff), int(accumulate)
     d.r_h, d.r_h_rows = _row_tensor(gh, B, H, 'coordatt_backward_input: gh')
@@ -563,21 +575,8 @@ def _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, what, workspa
     d.gamma, d.beta, d.vec = _ptr(_f32c(gamma)), _ptr(_f32c(beta)), _ptr(_f32c(vec))
     ws = None
     if workspace:
-        ws = torch.empty(max(_lib.lib().somi_ema_workspace_floats(B, H, W, c), 4), device=x.device, dtype=torch.float32)
-        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+        ws = _scratch(d, _lib.lib().somi_ema_workspace_floats(B, H, W, c), x.device)
     return d, ws
-
-
-def _ema_check(rc, what):
-    if rc == -2:                                                  # SOMI_ENOTIMPL: a configuration the kernels refuse before any launch
-        raise NotImplementedError(f'{what}: {_lib.lib().somi_last_error().decode(errors="replace")}')
-    check(rc, what)
-
-
-def _ema_map(t, like, what):
-    if tuple(t.shape[:3]) != tuple(like.shape[:3]):
-        raise RuntimeError(f'{what}: every map must be {tuple(like.shape[:3])} + (.,), got {tuple(t.shape)}')
-    return t
 
 
 def ema_stats(x, sg, c, factor, gamma, beta, eps, x_coff=0, *, sg_coff=0, x2=None, x2_coff=0):
@@ -590,8 +589,8 @@ def ema_stats(x, sg, c, factor, gamma, beta, eps, x_coff=0, *, sg_coff=0, x2=Non
     d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_stats')     # noqa: F841  (ws alive until the launch is enqueued)
     d.stats, d.eps = _ptr(stats), float(eps)
     if x2 is not None:
-        d.x2 = _slice(_ema_map(x2, x, 'ema_stats'), x2_coff)
-    _ema_check(_lib.lib().somi_ema_stats_nhwc_f32(C.byref(d), _stream()), 'ema_stats')
+        d.x2 = _slice(_map(x2, x, 'ema_stats: a map'), x2_coff)
+    _check_impl(_lib.lib().somi_ema_stats_nhwc_f32(C.byref(d), _stream()), 'ema_stats')
     return stats, vec
 
 
@@ -602,10 +601,10 @@ def ema_gate(x, x2, sg, vec, c, factor, gamma, beta, x_coff=0, *, x2_coff=0, sg_
     if out is None:
         out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
     d, _ = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_gate', workspace=False)
-    d.x2, d.y = _slice(_ema_map(x2, x, 'ema_gate'), x2_coff), _slice(_ema_map(out, x, 'ema_gate'), o_coff)
+    d.x2, d.y = _slice(_map(x2, x, 'ema_gate: a map'), x2_coff), _slice(_map(out, x, 'ema_gate: a map'), o_coff)
     if res is not None:
-        d.res = _slice(_ema_map(res, x, 'ema_gate'), res_coff)
-    _ema_check(_lib.lib().somi_ema_gate_nhwc_f32(C.byref(d), _stream()), 'ema_gate')
+        d.res = _slice(_map(res, x, 'ema_gate: a map'), res_coff)
+    _check_impl(_lib.lib().somi_ema_gate_nhwc_f32(C.byref(d), _stream()), 'ema_gate')
     return out
 
 
@@ -623,12 +622,12 @@ def ema_backward_gate(dout, x, x2, sg, vec, c, factor, gamma, beta, dgamma, dbet
     sums = torch.empty(B, 3, c, device=x.device, dtype=torch.float32)
     bvec = torch.empty(B, 3, c, device=x.device, dtype=torch.float32)
     d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_backward_gate')     # noqa: F841
-    d.x2, d.y = _slice(_ema_map(x2, x, 'ema_backward_gate'), x2_coff), _slice(_ema_map(dout, x, 'ema_backward_gate'), do_coff)
-    d.dx, d.dw = _slice(_ema_map(dx, x, 'ema_backward_gate'), dx_coff), _slice(_ema_map(dw, x, 'ema_backward_gate'), dw_coff)
+    d.x2, d.y = _slice(_map(x2, x, 'ema_backward_gate: a map'), x2_coff), _slice(_map(dout, x, 'ema_backward_gate: a map'), do_coff)
+    d.dx, d.dw = _slice(_map(dx, x, 'ema_backward_gate: a map'), dx_coff), _slice(_map(dw, x, 'ema_backward_gate: a map'), dw_coff)
     d.sums, d.bvec, d.dgamma, d.dbeta, d.accumulate = _ptr(sums), _ptr(bvec), _ptr(_f32c(dgamma)), _ptr(_f32c(dbeta)), int(accumulate)
     if dgamma.numel() != gamma.numel() or dbeta.numel() != beta.numel():
         raise RuntimeError('ema_backward_gate: dgamma / dbeta must have gamma\'s / beta\'s size')
-    _ema_check(_lib.lib().somi_ema_bwd_gate_nhwc_f32(C.byref(d), _stream()), 'ema_backward_gate')
+    _check_impl(_lib.lib().somi_ema_bwd_gate_nhwc_f32(C.byref(d), _stream()), 'ema_backward_gate')
     return dx, dw, sums, bvec
 
 
@@ -639,9 +638,9 @@ def ema_backward_norm(x, sg, dw, vec, bvec, c, factor, gamma, beta, x_coff=0, *,
     dt = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dt is None else dt
     dsg = torch.empty(B, H + W, c, device=x.device, dtype=torch.float32) if dsg is None else dsg
     d, ws = _ema_desc(x, c, factor, x_coff, sg, sg_coff, gamma, beta, vec, 'ema_backward_norm')     # noqa: F841
-    d.dw, d.y = _slice(_ema_map(dw, x, 'ema_backward_norm'), dw_coff), _slice(_ema_map(dt, x, 'ema_backward_norm'), dt_coff)
+    d.dw, d.y = _slice(_map(dw, x, 'ema_backward_norm: a map'), dw_coff), _slice(_map(dt, x, 'ema_backward_norm: a map'), dt_coff)
     d.dsg, d.bvec = _ema_rows(dsg, B, H + W, dsg_coff, 'ema_backward_norm: dsg'), _ptr(_f32c(bvec))
-    _ema_check(_lib.lib().somi_ema_bwd_norm_nhwc_f32(C.byref(d), _stream()), 'ema_backward_norm')
+    _check_impl(_lib.lib().somi_ema_bwd_norm_nhwc_f32(C.byref(d), _stream()), 'ema_backward_norm')
     return dt, dw, dsg
 
 
@@ -666,8 +665,7 @@ def _acmix_desc(qkv, c, what, workspace=False):
         d.q, d.k, d.v = _slice(t, qkv[1]), _slice(t, qkv[2]), _slice(t, qkv[3])
     ws = None
     if workspace:
-        ws = torch.empty(max(_lib.lib().somi_acmix_workspace_floats(B, H, W, c), 4), device=t.device, dtype=torch.float32)
-        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+        ws = _scratch(d, _lib.lib().somi_acmix_workspace_floats(B, H, W, c), t.device)
     return d, ws
 
 
@@ -689,7 +687,7 @@ def _acmix_small(t, n, what):
 def acmix_fold_weff(fc_w, dep_w, c):
     """fc.weight (9, 12[, 1, 1]) and dep_conv.weight (c, 9, 3, 3) -> weff (12, 9, c / 4, 4): dep_conv(fc(.)) as one grouped 3x3 conv."""
     weff = torch.empty(12, 9, c // 4, 4, device=fc_w.device, dtype=torch.float32)
-    _ema_check(_lib.lib().somi_acmix_fold_weff_f32(_acmix_small(fc_w, 108, 'fc.weight'), _acmix_small(dep_w, c * 81, 'dep_conv.weight'), _ptr(weff),
+    _check_impl(_lib.lib().somi_acmix_fold_weff_f32(_acmix_small(fc_w, 108, 'fc.weight'), _acmix_small(dep_w, c * 81, 'dep_conv.weight'), _ptr(weff),
                                                    int(c), _stream()), 'acmix_fold_weff')
     return weff
 
@@ -698,7 +696,7 @@ def acmix_split_dweff(dweff, fc_w, dep_w, c):
     """The gradient of weff -> (dfc (9, 12), ddep (c, 9, 3, 3))."""
     dfc = torch.empty(9, 12, device=dweff.device, dtype=torch.float32)
     ddep = torch.empty(c, 9, 3, 3, device=dweff.device, dtype=torch.float32)
-    _ema_check(_lib.lib().somi_acmix_split_dweff_f32(_acmix_small(dweff, 108 * c, 'dweff'), _acmix_small(fc_w, 108, 'fc.weight'),
+    _check_impl(_lib.lib().somi_acmix_split_dweff_f32(_acmix_small(dweff, 108 * c, 'dweff'), _acmix_small(fc_w, 108, 'fc.weight'),
                                                      _acmix_small(dep_w, c * 81, 'dep_conv.weight'), _ptr(dfc), _ptr(ddep), int(c), _stream()),
                'acmix_split_dweff')
     return dfc, ddep
@@ -711,9 +709,9 @@ def acmix_conv(qkv, c, weff, bias, *, out=None, o_coff=0):
     if out is None:
         out = torch.empty(B, H, W, c, device=qkv[0].device, dtype=torch.float32)
     d, _ = _acmix_desc(qkv, c, 'acmix_conv')
-    d.mix = _slice(_ema_map(out, qkv[0], 'acmix_conv'), o_coff)
+    d.mix = _slice(_map(out, qkv[0], 'acmix_conv: a map'), o_coff)
     d.weff, d.bias = _acmix_small(weff, 108 * c, 'weff'), _acmix_small(bias, c, 'bias')
-    _ema_check(_lib.lib().somi_acmix_conv_nhwc_f32(C.byref(d), _stream()), 'acmix_conv')
+    _check_impl(_lib.lib().somi_acmix_conv_nhwc_f32(C.byref(d), _stream()), 'acmix_conv')
     return out
 
 
@@ -728,13 +726,13 @@ def acmix_attn(qkv, c, wp, rate1, rate2, *, mix=None, mix_coff=0, out=None, o_co
     if lse is None and want_lse:
         lse = torch.empty(B, H, W, 4, device=x.device, dtype=torch.float32)
     d, _ = _acmix_desc(qkv, c, 'acmix_attn')
-    d.out = _slice(_ema_map(out, x, 'acmix_attn'), o_coff)
+    d.out = _slice(_map(out, x, 'acmix_attn: a map'), o_coff)
     if mix is not None:
-        d.mix = _slice(_ema_map(mix, x, 'acmix_attn'), mix_coff)
+        d.mix = _slice(_map(mix, x, 'acmix_attn: a map'), mix_coff)
     if lse is not None:
-        d.lse = _slice(_ema_map(lse, x, 'acmix_attn'), lse_coff)
+        d.lse = _slice(_map(lse, x, 'acmix_attn: a map'), lse_coff)
     d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
-    _ema_check(_lib.lib().somi_acmix_attn_nhwc_f32(C.byref(d), _stream()), 'acmix_attn')
+    _check_impl(_lib.lib().somi_acmix_attn_nhwc_f32(C.byref(d), _stream()), 'acmix_attn')
     return out, lse
 
 
@@ -753,13 +751,13 @@ def acmix_attn_backward_q(dout, qkv, c, wp, rate1, rate2, lse, *, do_coff=0, lse
     dwp = torch.empty(c // 4, 2, device=x.device, dtype=torch.float32)
     drates = torch.empty(2, device=x.device, dtype=torch.float32)
     d, ws = _acmix_desc(qkv, c, 'acmix_attn_backward_q', workspace=True)     # noqa: F841  (ws alive until the launch is enqueued)
-    d.out, d.lse = _slice(_ema_map(dout, x, 'acmix_attn_backward_q'), do_coff), _slice(_ema_map(lse, x, 'acmix_attn_backward_q'), lse_coff)
-    d.aux, d.dq = _slice(_ema_map(aux, x, 'acmix_attn_backward_q'), aux_coff), _slice(_ema_map(dq, x, 'acmix_attn_backward_q'), dq_coff)
+    d.out, d.lse = _slice(_map(dout, x, 'acmix_attn_backward_q: a map'), do_coff), _slice(_map(lse, x, 'acmix_attn_backward_q: a map'), lse_coff)
+    d.aux, d.dq = _slice(_map(aux, x, 'acmix_attn_backward_q: a map'), aux_coff), _slice(_map(dq, x, 'acmix_attn_backward_q: a map'), dq_coff)
     if mix is not None:
-        d.mix = _slice(_ema_map(mix, x, 'acmix_attn_backward_q'), mix_coff)
+        d.mix = _slice(_map(mix, x, 'acmix_attn_backward_q: a map'), mix_coff)
     d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
     d.dwp, d.drates, d.accumulate = _ptr(dwp), _ptr(drates), int(accumulate)
-    _ema_check(_lib.lib().somi_acmix_attn_bwd_q_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_q')
+    _check_impl(_lib.lib().somi_acmix_attn_bwd_q_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_q')
     return dq, aux, dwp, drates
 
 
@@ -774,12 +772,12 @@ def acmix_attn_backward_kv(dout, qkv, c, wp, rate1, rate2, lse, aux, *, do_coff=
     dk = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dk is None else dk
     dv = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32) if dv is None else dv
     d, _ = _acmix_desc(qkv, c, 'acmix_attn_backward_kv')
-    d.out, d.lse = _slice(_ema_map(dout, x, 'acmix_attn_backward_kv'), do_coff), _slice(_ema_map(lse, x, 'acmix_attn_backward_kv'), lse_coff)
-    d.aux = _slice(_ema_map(aux, x, 'acmix_attn_backward_kv'), aux_coff)
-    d.dk, d.dv = _slice(_ema_map(dk, x, 'acmix_attn_backward_kv'), dk_coff), _slice(_ema_map(dv, x, 'acmix_attn_backward_kv'), dv_coff)
+    d.out, d.lse = _slice(_map(dout, x, 'acmix_attn_backward_kv: a map'), do_coff), _slice(_map(lse, x, 'acmix_attn_backward_kv: a map'), lse_coff)
+    d.aux = _slice(_map(aux, x, 'acmix_attn_backward_kv: a map'), aux_coff)
+    d.dk, d.dv = _slice(_map(dk, x, 'acmix_attn_backward_kv: a map'), dk_coff), _slice(_map(dv, x, 'acmix_attn_backward_kv: a map'), dv_coff)
     d.wp, d.rate1, d.rate2 = _acmix_small(wp, c // 2, 'wp'), _acmix_small(rate1, 1, 'rate1'), _acmix_small(rate2, 1, 'rate2')
     d.accumulate = int(accumulate)
-    _ema_check(_lib.lib().somi_acmix_attn_bwd_kv_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_kv')
+    _check_impl(_lib.lib().somi_acmix_attn_bwd_kv_nhwc_f32(C.byref(d), _stream()), 'acmix_attn_backward_kv')
     return dk, dv
 
 
@@ -788,10 +786,10 @@ def acmix_conv_backward_data(dout, c, weff, rate2, dqkv, *, do_coff=0, accumulat
     side), added to with `accumulate`."""
     dqkv = _acmix_qkv(dqkv, c)
     d, _ = _acmix_desc((dqkv[0],), c, 'acmix_conv_backward_data')
-    d.out = _slice(_ema_map(dout, dqkv[0], 'acmix_conv_backward_data'), do_coff)
+    d.out = _slice(_map(dout, dqkv[0], 'acmix_conv_backward_data: a map'), do_coff)
     d.dq, d.dk, d.dv = _slice(dqkv[0], dqkv[1]), _slice(dqkv[0], dqkv[2]), _slice(dqkv[0], dqkv[3])
     d.weff, d.rate2, d.accumulate = _acmix_small(weff, 108 * c, 'weff'), _acmix_small(rate2, 1, 'rate2'), int(accumulate)
-    _ema_check(_lib.lib().somi_acmix_conv_bwd_data_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_data')
+    _check_impl(_lib.lib().somi_acmix_conv_bwd_data_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_data')
     return dqkv[0]
 
 
@@ -802,9 +800,9 @@ def acmix_conv_backward_weight(dout, qkv, c, rate2, *, do_coff=0):
     dweff = torch.empty(12, 9, c // 4, 4, device=x.device, dtype=torch.float32)
     dbias = torch.empty(c, device=x.device, dtype=torch.float32)
     d, ws = _acmix_desc(qkv, c, 'acmix_conv_backward_weight', workspace=True)     # noqa: F841
-    d.out = _slice(_ema_map(dout, x, 'acmix_conv_backward_weight'), do_coff)
+    d.out = _slice(_map(dout, x, 'acmix_conv_backward_weight: a map'), do_coff)
     d.rate2, d.dweff, d.dbias = _acmix_small(rate2, 1, 'rate2'), _ptr(dweff), _ptr(dbias)
-    _ema_check(_lib.lib().somi_acmix_conv_bwd_weight_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_weight')
+    _check_impl(_lib.lib().somi_acmix_conv_bwd_weight_nhwc_f32(C.byref(d), _stream()), 'acmix_conv_backward_weight')
     return dweff, dbias
 
 
@@ -848,19 +846,13 @@ def _simam_desc(x, c, grid, x_coff, stats, what):
     return d
 
 
-def _simam_workspace(d, dev):
-    ws = torch.empty(max(_lib.lib().somi_simam_workspace_floats(C.byref(d)), 4), device=dev, dtype=torch.float32)
-    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
-    return ws
-
-
 def simam_stats(x, c, grid, x_coff=0):
     """Per (image, region, channel) of slice [x_coff, x_coff + c) of x (B,H,W,cs): the mean over the region and the sum of squared deviations
     about it -> stats (B, ny * nx, 2, c).  grid: simam_grid(...)."""
     B = x.shape[0]
     stats = torch.empty(B, grid[0] * grid[1], 2, c, device=x.device, dtype=torch.float32)
     d = _simam_desc(x, c, grid, x_coff, stats, 'simam_stats')
-    ws = _simam_workspace(d, x.device)                            # noqa: F841  (alive until the launch is enqueued)
+    ws = _scratch(d, _lib.lib().somi_simam_workspace_floats(C.byref(d)), x.device)    # noqa: F841  (alive until the launch is enqueued)
     check(_lib.lib().somi_simam_stats_nhwc_f32(C.byref(d), _stream()), 'simam_stats')
     return stats
 
@@ -870,8 +862,7 @@ def simam_apply(x, stats, c, grid, x_coff=0, *, out=None, o_coff=0, add_input=Fa
     B, H, W, _ = x.shape
     if out is None:
         out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'simam_apply: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    _map(out, (B, H, W), 'simam_apply: output')
     d = _simam_desc(x, c, grid, x_coff, stats, 'simam_apply: stats')
     d.y, d.add_input = _slice(out, o_coff), int(add_input)
     check(_lib.lib().somi_simam_apply_nhwc_f32(C.byref(d), _stream()), 'simam_apply')
@@ -881,12 +872,11 @@ def simam_apply(x, stats, c, grid, x_coff=0, *, out=None, o_coff=0, add_input=Fa
 def simam_backward_sums(dout, x, stats, c, grid, do_coff=0, x_coff=0):
     """The two per (image, region, channel) sums of the backward, A = sum T d and B = sum T d^2 with T = w g x s (1 - s) -> sums (B, ny * nx, 2, c)."""
     B, H, W, _ = x.shape
-    if tuple(dout.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'simam_backward_sums: dout must be ({B}, {H}, {W}, .), got {tuple(dout.shape)}')
+    _map(dout, (B, H, W), 'simam_backward_sums: dout')
     sums = torch.empty_like(stats)
     d = _simam_desc(x, c, grid, x_coff, stats, 'simam_backward_sums: stats')
     d.y, d.sums = _slice(dout, do_coff), _ptr(sums)
-    ws = _simam_workspace(d, x.device)                            # noqa: F841
+    ws = _scratch(d, _lib.lib().somi_simam_workspace_floats(C.byref(d)), x.device)    # noqa: F841
     check(_lib.lib().somi_simam_bwd_sums_nhwc_f32(C.byref(d), _stream()), 'simam_backward_sums')
     return sums
 
@@ -899,8 +889,8 @@ def simam_backward_input(dout, x, stats, sums, c, grid, do_coff=0, x_coff=0, *, 
         if accumulate:
             raise RuntimeError('simam_backward_input: accumulate needs the tensor to add to')
         out = torch.empty(B, H, W, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W) or tuple(dout.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'simam_backward_input: dout and dx must be ({B}, {H}, {W}, .), got {tuple(dout.shape)} and {tuple(out.shape)}')
+    _map(dout, (B, H, W), 'simam_backward_input: dout')
+    _map(out, (B, H, W), 'simam_backward_input: dx')
     d = _simam_desc(x, c, grid, x_coff, stats, 'simam_backward_input: stats')
     if tuple(sums.shape) != tuple(stats.shape) or not sums.is_contiguous() or sums.dtype != torch.float32:
         raise RuntimeError(f'simam_backward_input: sums must be like stats, got {tuple(sums.shape)}')
@@ -911,11 +901,6 @@ def simam_backward_input(dout, x, stats, sums, c, grid, do_coff=0, x_coff=0, *, 
 
 
 # ---------------------------------------------------------------------------------------------- ASF-YOLO neck (asf.hip)
-def _map_check(t, shape, what):
-    if tuple(t.shape[:3]) != tuple(shape):
-        raise RuntimeError(f'{what} must be {tuple(shape)} + (channels,), got {tuple(t.shape)}')
-
-
 def zoomcat_small_size(size):
     """The size of Zoom_cat's small map along an axis of the middle map's `size`: read at (h >> 1, w >> 1)."""
     return (size + 1) // 2
@@ -932,11 +917,11 @@ def zoomcat(l, m, s, cl, cm, cs, l_coff=0, m_coff=0, s_coff=0, *, out=None, o_co
     if m is None and out is None:
         raise RuntimeError('zoomcat: m in place needs the output tensor that holds it')
     if m is not None:
-        _map_check(m, (B, H, W), 'zoomcat: m')
-    _map_check(s, (B, zoomcat_small_size(H), zoomcat_small_size(W)), 'zoomcat: s')
+        _map(m, (B, H, W), 'zoomcat: m')
+    _map(s, (B, zoomcat_small_size(H), zoomcat_small_size(W)), 'zoomcat: s')
     if out is None:
         out = torch.empty(B, H, W, cl + cm + cs, device=l.device, dtype=torch.float32)
-    _map_check(out, (B, H, W), 'zoomcat: out')
+    _map(out, (B, H, W), 'zoomcat: out')
     d = _lib.ZoomcatDesc()
     d.B, d.H, d.W, d.Cl, d.Cm, d.Cs = B, H, W, cl, cm, cs
     d.l, d.s, d.out = _slice(l, l_coff), _slice(s, s_coff), _slice(out, o_coff)
@@ -966,7 +951,7 @@ def zoomcat_backward(dout, codes, cl, cm, cs, do_coff=0, *, dl=True, dm=None, ds
             if accumulate[k]:
                 raise RuntimeError('zoomcat_backward: accumulate needs the tensor to add to')
             tgt = (torch.empty(*shapes[k], device=dout.device, dtype=torch.float32), 0)
-        _map_check(tgt[0], shapes[k][:3], f'zoomcat_backward: d{name}')
+        _map(tgt[0], shapes[k][:3], f'zoomcat_backward: d{name}')
         setattr(d, name, _slice(*tgt))
         d.accumulate[k] = int(accumulate[k])
         outs.append(tgt[0])
@@ -981,18 +966,12 @@ def _scalseq_desc(us, c, coffs, what):
     B, H, W, _ = u3.shape
     if H % 4 or W % 4:
         raise RuntimeError(f'{what}: the P3 map must have sizes that are multiples of 4, got {H}x{W}')
-    _map_check(u4, (B, H // 2, W // 2), f'{what}: u4')
-    _map_check(u5, (B, H // 4, W // 4), f'{what}: u5')
+    _map(u4, (B, H // 2, W // 2), f'{what}: u4')
+    _map(u5, (B, H // 4, W // 4), f'{what}: u5')
     d = _lib.ScalseqDesc()
     d.B, d.H, d.W, d.C = B, H, W, c
     d.u3, d.u4, d.u5 = _slice(u3, coffs[0]), _slice(u4, coffs[1]), _slice(u5, coffs[2])
     return d
-
-
-def _scalseq_workspace(d, dev):
-    ws = torch.empty(max(_lib.lib().somi_scalseq_workspace_floats(d.B, d.H, d.W, d.C), 4), device=dev, dtype=torch.float32)
-    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
-    return ws
 
 
 def _scalseq_stats_args(d, st):
@@ -1011,7 +990,7 @@ def scalseq_stats(us, c, gamma, beta, eps, momentum, running_mean=None, running_
     _scalseq_stats_args(d, st)
     d.gamma, d.beta, d.eps, d.momentum = _ptr(_f32c(gamma)), _ptr(_f32c(beta)), float(eps), float(momentum)
     d.running_mean, d.running_var = _ptr(running_mean), _ptr(running_var)
-    ws = _scalseq_workspace(d, dev)                               # noqa: F841  (alive until the launch is enqueued)
+    ws = _scratch(d, _lib.lib().somi_scalseq_workspace_floats(d.B, d.H, d.W, d.C), dev)    # noqa: F841  (alive until the launch is enqueued)
     check(_lib.lib().somi_scalseq_stats_f32(C.byref(d), _stream()), 'scalseq_stats')
     return st
 
@@ -1023,7 +1002,7 @@ def scalseq_fuse(us, c, scale=None, shift=None, coffs=(0, 0, 0), *, out=None, o_
     B, H, W, _ = us[0].shape
     if out is None:
         out = torch.empty(B, H, W, c, device=us[0].device, dtype=torch.float32)
-    _map_check(out, (B, H, W), 'scalseq_fuse: out')
+    _map(out, (B, H, W), 'scalseq_fuse: out')
     d.out = _slice(out, o_coff)
     if scale is not None:
         d.scale, d.shift = _ptr(_f32c(scale)), _ptr(_f32c(shift))
@@ -1038,7 +1017,7 @@ def scalseq_route_backward(dout, codes, us, c, st, coffs=(0, 0, 0), *, do_coff=0
     slope, children summed, at the maps' own resolutions) and sums (2, c) = (sum g, sum g xhat); dgamma / dbeta, when given, are ADDED to."""
     d = _scalseq_desc(us, c, coffs, 'scalseq_route_backward')
     B, H, W, _ = us[0].shape
-    _map_check(dout, (B, H, W), 'scalseq_route_backward: dout')
+    _map(dout, (B, H, W), 'scalseq_route_backward: dout')
     if codes.dtype != torch.uint8 or codes.numel() != B * H * W * (c // 4):
         raise RuntimeError(f'scalseq_route_backward: codes must hold {B * H * W * (c // 4)} bytes')
     dev = dout.device
@@ -1048,7 +1027,7 @@ def scalseq_route_backward(dout, codes, us, c, st, coffs=(0, 0, 0), *, do_coff=0
     d.g3, d.g4, d.g5 = (_slice(g, 0) for g in gs)
     _scalseq_stats_args(d, st)
     d.dgamma, d.dbeta = _ptr(dgamma), _ptr(dbeta)
-    ws = _scalseq_workspace(d, dev)                               # noqa: F841
+    ws = _scratch(d, _lib.lib().somi_scalseq_workspace_floats(d.B, d.H, d.W, d.C), dev)    # noqa: F841
     check(_lib.lib().somi_scalseq_route_bwd_nhwc_f32(C.byref(d), _stream()), 'scalseq_route_backward')
     return gs, sums
 
@@ -1057,7 +1036,7 @@ def scalseq_apply_backward(gs, us, c, st, sums, coffs=(0, 0, 0), g_coffs=(0, 0, 
     """Pass 2, in place on gs: du_i = scale (g_i - w_i (m1 + xhat_i m2)), w = 1, 4, 16, m1 = sum g / N, m2 = sum g xhat / N.  -> gs."""
     d = _scalseq_desc(us, c, coffs, 'scalseq_apply_backward')
     for g, u in zip(gs, us):
-        _map_check(g, u.shape[:3], 'scalseq_apply_backward: a gradient map')
+        _map(g, u.shape[:3], 'scalseq_apply_backward: a gradient map')
     d.g3, d.g4, d.g5 = (_slice(g, o) for g, o in zip(gs, g_coffs))
     _scalseq_stats_args(d, st)
     d.sums = _ptr(_f32c(sums))
@@ -1096,8 +1075,7 @@ def _asfatt_desc(B, H, W, c, workspace_on=None):
     d.B, d.H, d.W, d.C = B, H, W, c
     ws = None
     if workspace_on is not None:
-        ws = torch.empty(max(_lib.lib().somi_asfatt_workspace_floats(B, H, W, c), 4), device=workspace_on, dtype=torch.float32)
-        d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+        ws = _scratch(d, _lib.lib().somi_asfatt_workspace_floats(B, H, W, c), workspace_on)
     return d, ws
 
 
@@ -1110,13 +1088,13 @@ def _gate_check(g, B, c, what):
 def asf_mix_means(x1, x2, gate, c, x1_coff=0, x2_coff=0, *, t=None, t_coff=0, pool=None, p_coff=0):
     """t = x1 * gate[b,c] + x2 written, and pool (B, H + W, 1, .) = the row means and column means of t from the same pass.  -> (t, pool)."""
     B, H, W, _ = x1.shape
-    _map_check(x2, (B, H, W), 'asf_mix_means: x2')
+    _map(x2, (B, H, W), 'asf_mix_means: x2')
     if t is None:
         t = torch.empty(B, H, W, c, device=x1.device, dtype=torch.float32)
     if pool is None:
         pool = torch.empty(B, H + W, 1, c, device=x1.device, dtype=torch.float32)
-    _map_check(t, (B, H, W), 'asf_mix_means: t')
-    _map_check(pool, (B, H + W, 1), 'asf_mix_means: pool')
+    _map(t, (B, H, W), 'asf_mix_means: t')
+    _map(pool, (B, H + W, 1), 'asf_mix_means: pool')
     d, ws = _asfatt_desc(B, H, W, c, x1.device)                   # noqa: F841  (alive until the launch is enqueued)
     d.x1, d.x2, d.t, d.pool, d.gate = _slice(x1, x1_coff), _slice(x2, x2_coff), _slice(t, t_coff), _slice(pool, p_coff), _gate_check(gate, B, c, 'gate')
     check(_lib.lib().somi_asf_mix_means_nhwc_f32(C.byref(d), _stream()), 'asf_mix_means')
@@ -1126,7 +1104,7 @@ def asf_mix_means(x1, x2, gate, c, x1_coff=0, x2_coff=0, *, t=None, t_coff=0, po
 def asf_mix_backward_sums(dt, x1, c, dt_coff=0, x1_coff=0):
     """ds[b,c] = sum over the pixels of dt * x1: the gradient of the gate."""
     B, H, W, _ = x1.shape
-    _map_check(dt, (B, H, W), 'asf_mix_backward_sums: dt')
+    _map(dt, (B, H, W), 'asf_mix_backward_sums: dt')
     ds = torch.empty(B, c, device=x1.device, dtype=torch.float32)
     d, ws = _asfatt_desc(B, H, W, c, x1.device)                   # noqa: F841
     d.x1, d.t, d.ds = _slice(x1, x1_coff), _slice(dt, dt_coff), _ptr(ds)
@@ -1141,7 +1119,7 @@ def asf_mix_backward_input(dt, gate, davg, c, dt_coff=0, *, out=None, dx_coff=0,
         if accumulate:
             raise RuntimeError('asf_mix_backward_input: accumulate needs the tensor to add to')
         out = torch.empty(B, H, W, c, device=dt.device, dtype=torch.float32)
-    _map_check(out, (B, H, W), 'asf_mix_backward_input: dx1')
+    _map(out, (B, H, W), 'asf_mix_backward_input: dx1')
     d, _ = _asfatt_desc(B, H, W, c)
     d.t, d.dx1, d.accumulate = _slice(dt, dt_coff), _slice(out, dx_coff), int(accumulate)
     d.gate, d.davg = _gate_check(gate, B, c, 'gate'), _gate_check(davg, B, c, 'davg')
@@ -1227,8 +1205,7 @@ def cpca_wgrad(u, ts, ds, dts, c, dw_h, dw_v, db_h, db_v, *, accumulate=False, t
         d.t[k], d.dt[k] = _cpca_slice(ts[k]), _cpca_slice(dts[k])
         d.dw_h[k], d.dw_v[k] = _cpca_vec(dw_h[k], c * taps[k], 'cpca_wgrad: dw_h'), _cpca_vec(dw_v[k], c * taps[k], 'cpca_wgrad: dw_v')
         d.db_h[k], d.db_v[k] = _cpca_vec(db_h[k], c, 'cpca_wgrad: db_h'), _cpca_vec(db_v[k], c, 'cpca_wgrad: db_v')
-    ws = torch.empty(max(_lib.lib().somi_cpca_wgrad_workspace_floats(B, H, W, c), 4), device=first.device, dtype=torch.float32)
-    d.workspace, d.workspace_floats = _ptr(ws), ws.numel()
+    ws = _scratch(d, _lib.lib().somi_cpca_wgrad_workspace_floats(B, H, W, c), first.device)
     check(_lib.lib().somi_cpca_wgrad_nhwc_f32(C.byref(d), _stream()), 'cpca_wgrad')
 
 
@@ -1300,8 +1277,7 @@ def _up_out(x, c, out, what):
     B, H, W, _ = x.shape
     if out is None:
         out = torch.empty(B, 2 * H, 2 * W, c, device=x.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, 2 * H, 2 * W):
-        raise RuntimeError(f'{what}: output must be ({B}, {2 * H}, {2 * W}, .), got {tuple(out.shape)}')
+    _map(out, (B, 2 * H, 2 * W), f'{what}: output')
     return out
 
 
@@ -1310,8 +1286,7 @@ def carafe(x, logits, c, k_up, x_coff=0, l_coff=0, *, out=None, y_coff=0, weight
     [l_coff, ...) of `logits` (B,H,W,*) -> out (B,2H,2W,*) slice at y_coff.  weights=True (training): -> (out, weights), the softmax weights
     (B,2H,2W,k_up^2) carafe_backward needs - nothing else is kept."""
     B, H, W, _ = x.shape
-    if tuple(logits.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'carafe: logits must be ({B}, {H}, {W}, .), got {tuple(logits.shape)}')
+    _map(logits, (B, H, W), 'carafe: logits')
     out = _up_out(x, c, out, 'carafe')
     wts = torch.empty(B, 2 * H, 2 * W, k_up * k_up, device=x.device, dtype=torch.float32) if weights else None
     check(_lib.lib().somi_carafe_nhwc_f32(_ptr(_f32c(x)), _ptr(_f32c(logits)), _ptr(_f32c(out)), _ptr(wts), B, H, W, c, int(k_up), x.shape[3], x_coff,
@@ -1357,8 +1332,7 @@ def reset_dysample_far_taps():
 
 def _dysample_args(x, offset, init_pos, c, groups, what):
     B, H, W, _ = x.shape
-    if tuple(offset.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'{what}: offset must be ({B}, {H}, {W}, .), got {tuple(offset.shape)}')
+    _map(offset, (B, H, W), f'{what}: offset')
     if init_pos.numel() != 8 * groups or init_pos.dtype != torch.float32 or not init_pos.is_contiguous():
         raise RuntimeError(f'{what}: init_pos must hold {8 * groups} contiguous float32 values')
     if c % groups or (c // groups) % 4:
@@ -1919,8 +1893,7 @@ def psa_attention(qkv, heads, *, qkv_coff=0, out=None, o_coff=0, lse=False, v_ou
     N = H * W
     if out is None:
         out = torch.empty(B, H, W, 64 * heads, device=qkv.device, dtype=torch.float32)
-    if tuple(out.shape[:3]) != (B, H, W):
-        raise RuntimeError(f'psa attention: output must be ({B}, {H}, {W}, .), got {tuple(out.shape)}')
+    _map(out, (B, H, W), 'psa attention: output')
     lt = torch.empty(B, heads, N, device=qkv.device, dtype=torch.float32) if lse else None
     vt = torch.empty(B, H, W, 64 * heads, device=qkv.device, dtype=torch.float32) if v_out else None
     check(_lib.lib().somi_psa_attention_f32(_ptr(_f32c(qkv, 'qkv')), cs, qkv_coff, B, N, heads, _ptr(_f32c(out, 'output')), out.shape[3],
