@@ -559,6 +559,56 @@ int somi_cpca_sigmoid2_bwd_f32(const float *z, const float *dg, float *dz, int B
  * somi_pool_bwd_add_nhwc_f32 needs.  An integer minimum over the matching pixels, independent of the order. */
 int somi_cpca_argmax_pixel_nhwc_f32(somi_slice x, const float *mx, int32_t *amaxp, int B, int HW, int C, somi_stream_t stream);
 
+/* Tail attention of the CBAM C3 family (SCBAMBottleneck, models/common.py:975-995; the bare C3CBAM row, :494-504; cbam_c3.hip): a map t
+ * (B,H,W,.) combined with its channel gate ca (B, C) and its spatial gate sa (B, H, W) into a channel slice, plus an optional shortcut:
+ *   SOMI_GATE_PRODUCT      out = t * ca * sa [+ residual]
+ *   SOMI_GATE_SIGMOID_SUM  out = sigmoid(t * (ca + sa)) [+ residual]
+ * residual.p NULL: none.  out may be t or residual themselves.  B <= 65535, B * HW < 2^31, C % 4 == 0; ca 16-byte aligned.
+ * Backward in two passes with the spatial gate's own backward between them:
+ *  pixel: dsa[p] = sum_c g * t * ca (product, g = dout) or sum_c g * t (sigmoid-sum, g = dout * o * (1 - o), o the forward's sigmoid), written
+ *         raw (logit = 0) or times sa * (1 - sa) (logit = 1: what somi_spatial_attn_bwd_f32 takes); amaxc[p] = the first channel of the
+ *         pixel's maximum of t * ca; with t_max (B, C) = the spatial maxima of t the forward pooled, amaxp[b][c] = the first pixel that
+ *         holds it (an integer minimum, order-independent).  t_max and amaxp are given together or not at all.  A channel none of whose
+ *         values equals its t_max (a NaN in t, or a t_max from elsewhere) keeps 0x7f7f7f7f, which is no pixel: somi_pool_bwd_add_nhwc_f32
+ *         compares against amaxp and never indexes with it, so the maximum's gradient then goes nowhere.  B * C < 2^31.
+ *  chan:  with dstats (B,H,W,2) the gradient of [mean_c, max_c] of t * ca,  dt1 = dstats0 / C + [c == amaxc] * dstats1 (+ dout * sa, product);
+ *         product: dca = sum_p dt1 * t, dt = dt1 * ca;  sigmoid-sum: dca = sum_p (g + dt1) * t, dt = g * (ca + sa) + dt1 * ca.
+ *         dt is written, or added to with `accumulate`; it may be dout itself.  dca (B, C) is written.  workspace:
+ *         somi_gate_combine_bwd_workspace_floats floats, 16-byte aligned: per-workgroup partials, finished in ascending order in fp64.
+ * No float atomics: two launches are bit-identical. */
+#define SOMI_GATE_PRODUCT 0
+#define SOMI_GATE_SIGMOID_SUM 1
+int somi_gate_combine_nhwc_f32(somi_slice t, const float *ca, const float *sa, somi_slice residual, somi_slice out, int B, int HW, int C, int mode,
+                               somi_stream_t stream);
+int somi_gate_combine_bwd_pixel_f32(somi_slice dout, somi_slice t, const float *ca, const float *sa, const float *t_max, float *dsa,
+                                    int32_t *amaxc, int32_t *amaxp, int B, int HW, int C, int mode, int logit, somi_stream_t stream);
+/* How many trips of its grid-stride loop the busiest wave of the per-pixel pass makes at this shape - host arithmetic: at most 2048 workgroups
+ * of four waves, a wave taking 64 / lanes pixels a trip, lanes = the smallest power of two covering C / 4.  0 for sizes the pass refuses. */
+int somi_gate_combine_pixel_trips(int B, int HW, int C);
+size_t somi_gate_combine_bwd_workspace_floats(int B, int HW, int C);
+/* The depthwise-separable spatial gate of CBAMBottleneckDWC (SpatialAttentionModuleDWC, models/common.py:361-389, 425-438) on stats (B,H,W,2):
+ *   u = depthwise k x k conv (bias, pad k / 2);  v = relu(BN(u));  p = 1x1 conv 2 -> 1 (bias);  q = relu(BN1(p));  sa = sigmoid(q);  k = 3 or 7.
+ * params, 2 k k + 11 floats: depth_conv.weight (2,1,k,k), depth_conv.bias (2), bn.weight (2), bn.bias (2), point_conv.weight (2),
+ * point_conv.bias, bn1.weight, bn1.bias.  run, 6 floats: bn.running_mean (2), bn.running_var (2), bn1.running_mean, bn1.running_var.
+ * eval: running statistics, one launch.  train: batch statistics over the B H W > 1 values of a channel (biased variance), run (if given)
+ * moved by `momentum` with the unbiased variance; keeps u (B,H,W,2), p (B,H,W) and st (8 floats: mean (2) and rstd (2) of u, mean and
+ * rstd of p); three launches - the two BatchNorms are grid-wide reductions that follow one another.  bwd: from the RAW gradient of sa
+ * (somi_gate_combine_bwd_pixel_f32 with logit = 0) dstats (B,H,W,2), and every parameter gradient ADDED to dparams_accumulate in the layout
+ * of params.  workspace: somi_dwc_gate_workspace_floats floats, 16-byte aligned (fp64 partial rows, finished in a fixed order: bit-identical
+ * launches).  somi_dwc_gate_trips: the trips of the kernels' grid-stride loops at this size (host arithmetic; at most 128 workgroups). */
+size_t somi_dwc_gate_workspace_floats(int B, int H, int W, int k);
+int somi_dwc_gate_trips(int B, int H, int W);
+int somi_dwc_gate_eval_f32(const float *stats, const float *params, const float *run, float *sa, int B, int H, int W, int k, float eps,
+                           somi_stream_t stream);
+int somi_dwc_gate_train_f32(const float *stats, const float *params, float *u, float *p, float *st, float *run, float momentum, float eps,
+                            float *sa, float *workspace, size_t workspace_floats, int B, int H, int W, int k, somi_stream_t stream);
+int somi_dwc_gate_bwd_f32(const float *dsa, const float *stats, const float *u, const float *p, const float *st, const float *params,
+                          float *dstats, float *dparams_accumulate, float *workspace, size_t workspace_floats, int B, int H, int W, int k,
+                          somi_stream_t stream);
+int somi_gate_combine_bwd_chan_f32(somi_slice dout, somi_slice t, const float *ca, const float *sa, const float *dstats, const int32_t *amaxc,
+                                   somi_slice dt, float *dca, float *workspace, size_t workspace_floats, int B, int HW, int C, int mode,
+                                   int accumulate, somi_stream_t stream);
+
 /* SimAM attention (SimAM, models/common.py:2915-2939; SimAMWithSlicing, :9374-9408; SimAMWithFlexibleSlicing, :9411-9480; simam.hip): the
  * parameter-free energy gate as ONE operator over a grid of ny x nx regions of the map x (B,H,W,.).  Region (i, j) spans rows
  * [i * step_y, i * step_y + len_y) and columns [j * step_x, j * step_x + len_x); with stretch_last the last region of an axis runs to the map

@@ -322,6 +322,16 @@ SIGNATURES = {
     'somi_cpca_sigmoid2_f32': (I, [P, P, I, I, S]),
     'somi_cpca_sigmoid2_bwd_f32': (I, [P, P, P, I, I, S]),
     'somi_cpca_argmax_pixel_nhwc_f32': (I, [Slice, P, P, I, I, I, S]),
+    'somi_gate_combine_nhwc_f32': (I, [Slice, P, P, Slice, Slice, I, I, I, I, S]),
+    'somi_gate_combine_bwd_pixel_f32': (I, [Slice, Slice, P, P, P, P, P, P, I, I, I, I, I, S]),
+    'somi_gate_combine_bwd_workspace_floats': (Z, [I, I, I]),
+    'somi_gate_combine_pixel_trips': (I, [I, I, I]),
+    'somi_dwc_gate_workspace_floats': (Z, [I, I, I, I]),
+    'somi_dwc_gate_trips': (I, [I, I, I]),
+    'somi_dwc_gate_eval_f32': (I, [P, P, P, P, I, I, I, I, F, S]),
+    'somi_dwc_gate_train_f32': (I, [P, P, P, P, P, P, F, F, P, P, Z, I, I, I, I, S]),
+    'somi_dwc_gate_bwd_f32': (I, [P, P, P, P, P, P, P, P, P, Z, I, I, I, I, S]),
+    'somi_gate_combine_bwd_chan_f32': (I, [Slice, Slice, P, P, P, P, Slice, P, P, Z, I, I, I, I, I, S]),
     'somi_simam_desc_bytes': (Z, []),
     'somi_simam_workspace_floats': (Z, [C.POINTER(SimamDesc)]),
     'somi_simam_stats_nhwc_f32': (I, [C.POINTER(SimamDesc), S]),

@@ -626,9 +626,11 @@ class CBAMBottleneck(nn.Module):
 
     def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
         """dout: gradient w.r.t. the block output (Act); the input gradient is ADDED into dx_out (Act, e.g. a slice of the
-        C2f gradient buffer that already holds the gradient of the input's other consumers) - the only form this block has."""
-        if dx_out is None or not accumulate or not need_dx:
-            raise NotImplementedError('CBAMBottleneck adds its input gradient into dx_out')
+        C2f gradient buffer that already holds the gradient of the input's other consumers); or, with none of the three given, it is RETURNED
+        as a tensor of its own (the form C3.backward takes: C3_CBAM, C3_CBAMS) - the same launches, cv1's data gradient written, not added."""
+        returning = dx_out is None and not accumulate and need_dx
+        if not returning and (dx_out is None or not accumulate or not need_dx):
+            raise NotImplementedError('CBAMBottleneck adds its input gradient into dx_out, or returns it (dx_out=None, accumulate=False)')
         x, t = self.__dict__.pop('_ctx')
         d = self.cv2.backward(dout)                               # d(t*ca*sa)
         bn = None
@@ -640,7 +642,8 @@ class CBAMBottleneck(nn.Module):
         pooled = self.channel_attention.backward(dca, d, amaxp, defer=True)   # the pooled paths join d inside cv1's BatchNorm backward
         c1 = self.cv1.conv.in_channels
         fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0  # the shortcut's gradient rides the dgrad epilogue
-        self.cv1.backward(d, dx_out=dx_out, accumulate=True, also_add=dout if fuse else None, pooled=pooled, cbam=state[0] if state else None)
+        dx_out = self.cv1.backward(d, dx_out=dx_out, accumulate=not returning, also_add=dout if fuse else None, pooled=pooled,
+                                   cbam=state[0] if state else None)
         if self.add and not fuse:
             ops.add_(dx_out.t, dx_out.coff, dout.t, dout.coff, x.c)
         return dx_out
@@ -3513,6 +3516,350 @@ class C3CPCA(C3):
         self.m = nn.Sequential(*(CPCABottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
 
     accumulates = folds_pooled = False                           # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
+    reduction = 1
+
+
+# ------------------------------------------------------------------------------------------------ the CBAM C3 family
+def _cbam_limits(who, c, ratio, train_whole=False, unpadded=False):
+    """The widths the CBAM kernels take, checked before any launch: channel quads, a shared MLP of 1..64 hidden neurons over at most 1024
+    channels (somi_attn_mlp_f32), and - train_whole: the block's training path scales a whole tensor; unpadded: the block hands tensors of
+    exactly c channels on - a width stored unpadded."""
+    if c % 4:
+        raise NotImplementedError(f'{who}: hidden width {c} is not a multiple of 4 (a lane owns a channel quad)')
+    if c // ratio == 0:
+        raise NotImplementedError(f'{who}: {c} channels at ratio {ratio} leave the channel attention\'s MLP no hidden neuron '
+                                  f'(at least {ratio} channels)')
+    if c > 1024 or c // ratio > 64:
+        raise NotImplementedError(f'{who}: the channel attention\'s MLP runs on at most 1024 channels and 64 hidden neurons, got {c} and {c // ratio}')
+    if unpadded and pad4(c) != c:
+        raise NotImplementedError(f'{who}: the gated tensors are exactly {c} channels wide, and {c} channels are stored as a slice of {pad4(c)} '
+                                  f'(a multiple of 32 from 64 up)')
+    if train_whole and pad4(c) != c:
+        raise NotImplementedError(f'{who}: the CBAM training path works on whole tensors, and {c} channels are stored as a slice of {pad4(c)}')
+
+
+def _gate_kernel_size(who, kernel_size):
+    if kernel_size not in (3, 5, 7):
+        raise NotImplementedError(f'{who}: kernel_size {kernel_size} of the spatial gate is not built, only 3, 5 and 7')
+    return kernel_size
+
+
+class DepthWiseConv(nn.Module):
+    """depthwise k x k conv -> BatchNorm -> ReLU -> 1x1 conv -> BatchNorm -> ReLU (models/common.py:361-389): the parameter holder of the
+    depthwise-separable spatial gate; SpatialAttentionModuleDWC runs it."""
+
+    def __init__(self, in_channel, out_channel, kernel_size=3, stride=1, padding=1):
+        super().__init__()
+        self.depth_conv = nn.Conv2d(in_channel, in_channel, kernel_size, stride, padding, groups=in_channel)
+        self.bn = nn.BatchNorm2d(in_channel)
+        self.point_conv = nn.Conv2d(in_channel, out_channel, 1, 1, 0)
+        self.relu = nn.ReLU(inplace=True)
+        self.bn1 = nn.BatchNorm2d(out_channel)
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def ordered(self):
+        """The parameters in the order of the kernels' flat vector (ops.dwc_gate_*)."""
+        return (self.depth_conv.weight, self.depth_conv.bias, self.bn.weight, self.bn.bias, self.point_conv.weight, self.point_conv.bias,
+                self.bn1.weight, self.bn1.bias)
+
+
+class SpatialAttentionModuleDWC(nn.Module):
+    """sigmoid(relu(BN1(conv1x1(relu(BN(dwconv_kxk([mean_c, max_c]))))))) (models/common.py:425-438): the ReLU comes before the sigmoid, so the
+    gate lies in [0.5, 1).  k is 3 or 7.  Inference: one launch on the running statistics.  Training: three launches (the two BatchNorms take
+    batch statistics over (B, H, W), two grid-wide reductions that follow one another), the running statistics and num_batches_tracked move
+    as in nn.BatchNorm2d; backward starts at the raw gradient of the gate: six launches for dstats and the eight parameter gradients."""
+
+    def __init__(self, kernel_size=7):
+        super().__init__()
+        if kernel_size not in (3, 7):
+            raise NotImplementedError(f'SpatialAttentionModuleDWC: kernel_size {kernel_size} is not built, only 3 and 7 (the reference asserts the same)')
+        self.cv1 = DepthWiseConv(2, 1, kernel_size, padding=3 if kernel_size == 7 else 1)
+        self.sigmoid = nn.Sigmoid()
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def _vectors(self, dev):
+        g = self.cv1
+        params = torch.cat([p_.detach().float().reshape(-1) for p_ in g.ordered()]).to(dev)
+        run = torch.cat([g.bn.running_mean, g.bn.running_var, g.bn1.running_mean, g.bn1.running_var]).detach().float().to(dev)
+        return params, run
+
+    def gate(self, stats):
+        """stats (B,H,W,2) -> sa (B,H,W)."""
+        g = self.cv1
+        k = g.depth_conv.kernel_size[0]
+        if g.bn.eps != g.bn1.eps or g.bn.momentum != g.bn1.momentum:
+            raise NotImplementedError('SpatialAttentionModuleDWC: the two BatchNorms share eps and momentum on the SOMI path')
+        params, run = self._vectors(stats.device)
+        if not self.training:
+            return ops.dwc_gate_eval(stats, params, run, k, g.bn.eps)
+        if ops.SYNC_BN is not None:
+            raise NotImplementedError('SpatialAttentionModuleDWC: the gate\'s two BatchNorms take local batch statistics; not under ops.SYNC_BN')
+        sa, u, p, st = ops.dwc_gate_train(stats, params, run, k, g.bn.eps, g.bn.momentum)
+        with torch.no_grad():
+            g.bn.running_mean.copy_(run[0:2]), g.bn.running_var.copy_(run[2:4])
+            g.bn1.running_mean.copy_(run[4:5]), g.bn1.running_var.copy_(run[5:6])
+        _bump_batches_tracked(g.bn)
+        _bump_batches_tracked(g.bn1)
+        self.__dict__['_ctx'] = (stats, u, p, st, params)
+        return sa
+
+    def gate_backward(self, dsa):
+        """dsa: the raw gradient of the gate -> dstats; the eight parameter gradients into .grad."""
+        stats, u, p, st, params = self.__dict__.pop('_ctx')
+        k = self.cv1.depth_conv.kernel_size[0]
+        dparams = torch.zeros_like(params)
+        dstats = ops.dwc_gate_backward(dsa, stats, u, p, st, params, k, dparams)
+        off = 0
+        for p_ in self.cv1.ordered():
+            _acc_grad(p_, dparams[off:off + p_.numel()].view_as(p_))
+            off += p_.numel()
+        return dstats
+
+
+class _TailGate(nn.Module):
+    """What SCBAMBottleneck and C3CBAM share: on the children `channel_attention` (ChannelAttentionModule) and `spatial_attention`
+    (SpatialAttentionModule), ca = channel_attention(t), sa = the k x k gate of [mean_c, max_c] of t * ca, and ONE pass that combines t, ca and sa
+    into the output's channel slice (+ a shortcut): ops.gate_combine, as a product (CBAM) or as sigmoid(t * (ca + sa)) (SCBAM).  Forward:
+    global_pool (none when the producing Conv took the pools), attn_mlp, chan_stats, spatial_attn, gate_combine.  Backward: the per-pixel pass
+    (d logit, both arg-maxima), step B of train_blocks.hip (three launches), the per-element pass (dt + dca, two launches), the MLP backward (two)."""
+
+    def _gate_forward(self, t, mode, residual=None, out=None, pooled=None):
+        c = t.c
+        if t.up:
+            raise NotImplementedError(f'{type(self).__name__}: an upsampled view is not a map the gates can pool')
+        if not t.t.is_cuda:
+            raise RuntimeError(f'somi_amd {type(self).__name__} runs on the MI355X only (no CPU fallback)')
+        ca = self.channel_attention(t, pooled=pooled)
+        sam = self.spatial_attention
+        stats = ops.chan_stats(t.t, ca, c=c, x_coff=t.coff)
+        w = None
+        if isinstance(sam, SpatialAttentionModuleDWC):
+            sa = sam.gate(stats)
+        else:
+            if self.training:
+                sam.invalidate()
+            w, b = sam._packed(t.t.device)
+            sa = ops.spatial_attn(stats, w, b, sam.cv1.kernel_size[0])
+        B, H, W, _ = t.shape
+        if out is None:
+            out = concat_act(t.t, H, W, c)                        # pad channels (if any) zero
+        ops.gate_combine(t.t, ca, sa, c, mode, t.coff, residual=None if residual is None else residual.t,
+                         res_coff=0 if residual is None else residual.coff, out=out.t, o_coff=out.coff)
+        if self.training:
+            self.__dict__['_gctx'] = (t, ca, stats, sa, w, mode)
+        return Act(out.t, out.coff, c)
+
+    def _gate_backward(self, dout, dt=None, accumulate=False, defer=False):
+        """dout: the gradient of the combined output (Act).  -> (the gradient of t as an Act: a tensor of its own, or dt's slice, added to it
+        with `accumulate`; the channel attention's pooled part (davg, dmax, amaxp) with `defer`, else None: it is added to that Act in place)."""
+        t, ca, stats, sa, w, mode = self.__dict__.pop('_gctx')
+        sam, c = self.spatial_attention, t.c
+        dwc = isinstance(sam, SpatialAttentionModuleDWC)          # its backward starts at the sigmoid: the raw gradient of the gate
+        t_max = self.channel_attention.__dict__['_ctx'][2]        # the pooled maxima: the per-pixel pass finds their first pixels by value
+        dlogit, amaxc, amaxp = ops.gate_combine_backward_pixel(dout.t, t.t, ca, sa, c, mode, dout.coff, t.coff, t_max=t_max, logit=not dwc)
+        if dwc:
+            dstats = sam.gate_backward(dlogit)
+        else:
+            (dw, db), fin = _grad_targets(sam.cv1.weight, sam.cv1.bias)     # accumulated in nn.Conv2d's (1,2,k,k) layout
+            dstats = ops.spatial_attn_backward(dlogit, stats, w, sam.cv1.kernel_size[0], dw, db)
+            fin()
+        d, dca = ops.gate_combine_backward_chan(dout.t, t.t, ca, sa, dstats, amaxc, c, mode, dout.coff, t.coff, dt=None if dt is None else dt.t,
+                                                dt_coff=0 if dt is None else dt.coff, accumulate=accumulate)
+        d = Act(d, 0 if dt is None else dt.coff, c)
+        return d, self.channel_attention.backward(dca, d, amaxp, defer=defer)
+
+
+class SCBAMBottleneck(_TailGate):
+    """x2 = cv2(cv1(x)) (1x1, 3x3);  yc = ca(x2) * x2;  ys = sa(yc) * x2 - the gate is computed from yc but multiplies x2 -;
+    out = sigmoid(yc + ys) (+ x) (models/common.py:975-995).  Ratio 16, plain 7x7 gate.  The gated tensor is the block's output: the combine
+    pass writes `out`'s channel slice, shortcut included; backward hands the pooled part of the channel attention's gradient to cv2's BatchNorm
+    backward and the shortcut's gradient to cv1's data-gradient epilogue."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5, ratio=16, kernel_size=7):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_, c2, 3, 1, g=g)
+        self.add = shortcut and c1 == c2
+        self.channel_attention = ChannelAttentionModule(c2, ratio)
+        self.spatial_attention = SpatialAttentionModule(_gate_kernel_size(f'SCBAMBottleneck({c1}, {c2})', kernel_size))
+        self.sigmoid = nn.Sigmoid()
+        self.ratio = ratio
+
+    accumulates = folds_pooled = False                           # like Bottleneck: takes dx_out / accumulate, not walked that way
+    reduction = 1
+
+    def forward(self, x, out=None):
+        c1, c2 = self.cv1.conv.in_channels, self.cv2.conv.out_channels
+        _cbam_limits(f'SCBAMBottleneck({c1}, {c2})', c2, self.ratio, unpadded=True)
+        pool = {} if self.training else None
+        x2 = self.cv2(self.cv1(x), pool=pool)                     # training: the BatchNorm + SiLU pass also takes the attention's global pools
+        return self._gate_forward(x2, 'sigmoid_sum', x if self.add else None, out, (pool['avg'], pool['max']) if pool else None)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        d, pooled = self._gate_backward(dout, defer=True)
+        d = self.cv2.backward(d, pooled=pooled)
+        c1 = self.cv1.conv.in_channels
+        fuse = self.add and pad4(c1) == c1 and dout.coff % 4 == 0
+        dx = self.cv1.backward(d, dx_out=dx_out, accumulate=accumulate, need_dx=need_dx, also_add=dout if fuse else None)
+        if self.add and not fuse and dx is not None:
+            ops.add_(dx.t, dx.coff, dout.t, dout.coff, c1)
+        return dx
+
+
+class CBAMBottleneckDWC(_TailGate):
+    """x2 = cv2(cv1(x));  t1 = ca(x2) * x2 (ratio 16);  out = sa(t1) * t1 (+ x), sa the depthwise-separable gate (models/common.py:953-972).
+    The signature is the reference's: e comes BEFORE k.  The gated tensor is the block's output: the combine pass writes `out`'s slice."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5, k=(3, 3), ratio=16, kernel_size=7):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, k[0], 1)
+        self.cv2 = Conv(c_, c2, k[1], 1, g=g)
+        self.add = shortcut and c1 == c2
+        self.channel_attention = ChannelAttentionModule(c2, ratio)
+        self.spatial_attention = SpatialAttentionModuleDWC(kernel_size)
+        self.ratio = ratio
+
+    accumulates = folds_pooled = False                           # like Bottleneck: takes dx_out / accumulate, not walked that way
+    reduction = 1
+
+    def forward(self, x, out=None):
+        c1, c2 = self.cv1.conv.in_channels, self.cv2.conv.out_channels
+        _cbam_limits(f'CBAMBottleneckDWC({c1}, {c2})', c2, self.ratio, unpadded=True)
+        if self.training and ops.SYNC_BN is not None:
+            raise NotImplementedError(f'CBAMBottleneckDWC({c1}, {c2}): the gate\'s two BatchNorms take local batch statistics; not under ops.SYNC_BN')
+        pool = {} if self.training else None
+        x2 = self.cv2(self.cv1(x), pool=pool)
+        return self._gate_forward(x2, 'product', x if self.add else None, out, (pool['avg'], pool['max']) if pool else None)
+
+    backward = SCBAMBottleneck.backward
+
+
+class C3CBAM(_TailGate):
+    """A bare CBAM on its input as a row of its own: out = sa(ca(x) * x) * (ca(x) * x) (models/common.py:494-504).  Ratio 16, 7x7 gate; c2 is
+    ignored, the channels pass through.  Never in place: other rows may read its input."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.kernel_size = 7
+        self.channel_attention = ChannelAttentionModule(c1)
+        self.spatial_attention = SpatialAttentionModule(self.kernel_size)
+
+    accumulates = folds_pooled = False                           # takes dx_out / accumulate, not walked that way
+    reduction = 1
+
+    def forward(self, x, out=None):
+        c = self.channel_attention.shared_MLP[0].in_features
+        if x.c != c:
+            raise RuntimeError(f'C3CBAM over {c} channels got a map of {x.c}')
+        _cbam_limits(f'C3CBAM({c})', c, 16, unpadded=True)
+        return self._gate_forward(x, 'product', None, out)
+
+    def backward(self, dout, dx_out=None, accumulate=False, need_dx=True):
+        """-> the gradient of the input as an Act (a tensor of its own, or dx_out's slice, added to it with `accumulate`); None without need_dx
+        (the gates' parameter gradients are still taken)."""
+        if not need_dx:
+            self._gate_backward(dout, defer=True)
+            return None
+        return self._gate_backward(dout, dx_out, accumulate and dx_out is not None)[0]
+
+
+class _C3Gated(C3):
+    """A C3 whose bottlenecks carry CBAM-style attention; `_limits` refuses the widths the attention kernels do not take before any launch."""
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def forward(self, x):
+        self._limits()
+        return super().forward(x)
+
+
+class C3_CBAM(_C3Gated):
+    """C3 whose bottlenecks are CBAMBottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0, kernel_size=7) (models/common.py:1640-1648):
+    ratio 8, attention between cv1 (1x1) and cv2; repeated inside (models/yolo.py:1473, 1487).  C3.backward takes each bottleneck's input
+    gradient as a returned tensor (CBAMBottleneck.backward's returning form)."""
+    KERNEL = 7
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5, kernel_size=None):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        k = _gate_kernel_size(f'{type(self).__name__}({c1}, {c2})', self.KERNEL if kernel_size is None else kernel_size)
+        self.m = nn.Sequential(*(CBAMBottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0, kernel_size=k) for _ in range(n)))
+
+    accumulates = folds_pooled = False                           # C3's backward, dx_out / accumulate included; the walk adds its gradient itself
+    reduction = 1
+
+    def _limits(self):
+        c1, c_, c2 = self.cv1.conv.in_channels, self.cv1.conv.out_channels, self.cv3.conv.out_channels
+        _cbam_limits(f'{type(self).__name__}({c1}, {c2})', c_, 8, train_whole=self.training)
+
+
+class C3_CBAMS(C3_CBAM):
+    """C3_CBAM with a 3x3 spatial gate (models/common.py:1662-1670)."""
+    KERNEL = 3
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+
+class C3_SCBAM(_C3Gated):
+    """C3 whose bottlenecks are SCBAMBottleneck(c_, c_, shortcut, g, e=1.0) (models/common.py:1700-1705); repeated inside
+    (models/yolo.py:1477, 1490).  The last bottleneck's combine pass writes C3's concat slice."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(SCBAMBottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def _limits(self):
+        c1, c_, c2 = self.cv1.conv.in_channels, self.cv1.conv.out_channels, self.cv3.conv.out_channels
+        _cbam_limits(f'C3_SCBAM({c1}, {c2})', c_, 16, unpadded=True)
+
+
+class _C3DWC(_C3Gated):
+    KERNEL = 7
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5, kernel_size=None):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        k = self.KERNEL if kernel_size is None else kernel_size
+        if k not in (3, 7):
+            raise NotImplementedError(f'{type(self).__name__}({c1}, {c2}): kernel_size {k} of the depthwise-separable gate is not built, only 3 and 7')
+        self.m = nn.Sequential(*(CBAMBottleneckDWC(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0, kernel_size=k) for _ in range(n)))
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+    def _limits(self):
+        c1, c_, c2 = self.cv1.conv.in_channels, self.cv1.conv.out_channels, self.cv3.conv.out_channels
+        _cbam_limits(f'{type(self).__name__}({c1}, {c2})', c_, 16, unpadded=True)
+        if self.training and ops.SYNC_BN is not None:
+            raise NotImplementedError(f'{type(self).__name__}({c1}, {c2}): the gate\'s two BatchNorms take local batch statistics; not under ops.SYNC_BN')
+
+
+class C3_CBAM_DWC(_C3DWC):
+    """C3 whose bottlenecks are CBAMBottleneckDWC(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0, kernel_size=7) (models/common.py:1651-1659);
+    repeated inside (models/yolo.py:1474, 1488)."""
+    KERNEL = 7
+
+    accumulates = folds_pooled = False
+    reduction = 1
+
+
+class C3_CBAMS_DWC(_C3DWC):
+    """C3_CBAM_DWC with a 3x3 depthwise gate (models/common.py:1673-1681)."""
+    KERNEL = 3
+
+    accumulates = folds_pooled = False
     reduction = 1
 
 

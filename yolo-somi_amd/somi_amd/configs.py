@@ -319,6 +319,29 @@ def yolov5_cpca_cfg(width=0.50, depth=0.33, nc=80, anchors=None, where='c3'):
     return cfg
 
 
+CBAM_VARIANTS = {'cbam': 'C3_CBAM', 'cbams': 'C3_CBAMS', 'cbam_dwc': 'C3_CBAM_DWC', 'cbams_dwc': 'C3_CBAMS_DWC', 'scbam': 'C3_SCBAM', 'row': 'C3CBAM'}
+
+
+def yolov5_cbam_cfg(width=0.50, depth=0.33, nc=80, anchors=None, variant='cbam'):
+    """yolov5s 6.0 with the CBAM C3 family (models/common.py:494-504, 1640-1705).  The reference registers the names in its parser
+    (models/yolo.py:1473-1477, 1487-1490) but ships no yaml that names them.  variant 'cbam' / 'cbams' / 'cbam_dwc' / 'cbams_dwc' / 'scbam': the
+    four backbone C3 rows become C3_CBAM / C3_CBAMS / C3_CBAM_DWC / C3_CBAMS_DWC / C3_SCBAM, repeated inside like C3; 'row': a
+    [-1, 1, 'C3CBAM', [1024]] row behind SPPF (it must name its input's width, which it passes through), the head's absolute indices one up."""
+    if variant not in CBAM_VARIANTS:
+        raise ValueError(f'variant must be one of {tuple(CBAM_VARIANTS)}, got {variant!r}')
+    cfg = yolov5_cfg(width, depth, nc, anchors)
+    if variant != 'row':
+        for row in cfg['backbone']:
+            if row[2] == 'C3':
+                row[2] = CBAM_VARIANTS[variant]
+        return cfg
+    cfg['backbone'].append([-1, 1, 'C3CBAM', [1024]])
+    for row in cfg['head']:
+        if isinstance(row[0], list):
+            row[0] = [j + 1 if j >= 10 else j for j in row[0]]
+    return cfg
+
+
 SIMAM_WHERE = ('row', 'slicing', 'sws', 'ps')
 
 

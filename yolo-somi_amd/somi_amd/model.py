@@ -21,7 +21,10 @@ pair `GSConv` and `VoVGSCSPCBAM` (width-scaled like Conv and C3, the latter repe
 (repeated inside), `ConvMix` and `CSPCM` (n > 1 a Repeat of whole modules; a `ConvMix` row must name the channels behind it, which it passes
 through); and efficient multi-scale attention: `EMA`, `iRMB_EMA`, `iRMB_EMABottleneck` and `C2f_iRMB_EMA` rows, built from the yaml
 arguments as written (the reference's generic branch), which must name the width of their input; and `ACmix`, self-attention mixed with
-convolution, width-scaled like Conv (models/yolo.py:1496-1501).
+convolution, width-scaled like Conv (models/yolo.py:1496-1501); and the CBAM C3 family (models/yolo.py:1473-1477): `C3_CBAM`, `C3_CBAMS`,
+`C3_CBAM_DWC`, `C3_CBAMS_DWC` (the gate a depthwise-separable conv with two BatchNorms) and `C3_SCBAM`, width-scaled and repeated inside like
+C3, and the bare `C3CBAM` row, which must name the width of its input (it passes it through; not repeated inside, and n > 1, the
+reference's nn.Sequential of whole modules, stays refused).
 """
 import math
 from copy import deepcopy
@@ -52,10 +55,14 @@ _CH = {'Conv': B.Conv, 'SPPF': B.SPPF, 'C2fCBAM': B.C2fCBAM, 'SEAM': B.SEAM, 'Bo
        'GSConv': B.GSConv, 'VoVGSCSPCBAM': B.VoVGSCSPCBAM,
        # the ConvNeXt / ConvMixer blocks: CNeB has a branch of its own that repeats inside (models/yolo.py:1523-1530); ConvMix and CSPCM share
        # one that does not (:1531-1535), so n > 1 is an nn.Sequential of n whole modules
-       'CNeB': B.CNeB, 'ConvMix': B.ConvMix, 'CSPCM': B.CSPCM}
+       'CNeB': B.CNeB, 'ConvMix': B.ConvMix, 'CSPCM': B.CSPCM,
+       # the CBAM C3 family, models/yolo.py:1473-1477; the three C3 variants repeated inside (:1487-1490), the bare C3CBAM row not
+       'C3_CBAM': B.C3_CBAM, 'C3_CBAMS': B.C3_CBAMS, 'C3_SCBAM': B.C3_SCBAM, 'C3CBAM': B.C3CBAM,
+       'C3_CBAM_DWC': B.C3_CBAM_DWC, 'C3_CBAMS_DWC': B.C3_CBAMS_DWC}
 _SIMAM_SLICED = {'SimAMWithSlicing': B.SimAMWithSlicing, 'SimAMWithFlexibleSlicing': B.SimAMWithFlexibleSlicing}      # models/yolo.py:1504-1513
 # models/yolo.py:1487-1492.  C3_CA is NOT in the reference's list: n > 1 is an nn.Sequential of n C3_CA blocks with one bottleneck each (a Repeat)
-_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM', 'CNeB')
+_REPEAT_INSIDE = ('C2fCBAM', 'C3', 'C3Ghost', 'C2f', 'C2fCIB', 'BottleneckCSP', 'C3STR', 'C2f_DWR', 'C3CPCA', 'VoVGSCSPCBAM', 'CNeB',
+                  'C3_CBAM', 'C3_CBAMS', 'C3_SCBAM', 'C3_CBAM_DWC', 'C3_CBAMS_DWC')
 # efficient multi-scale attention: none of the four is in a list of the reference's parser, so its generic branch builds them from the yaml
 # arguments as written and records the input's width for the rows behind (models/yolo.py:1648-1650)
 _EMA = {'EMA': B.EMA, 'iRMB_EMA': B.iRMB_EMA, 'iRMB_EMABottleneck': B.iRMB_EMABottleneck, 'C2f_iRMB_EMA': B.C2f_iRMB_EMA}
@@ -86,6 +93,9 @@ def parse_model(d, ch):
                 n = 1
             elif name == 'ConvMix' and c2 != c1:                  # the module ignores dim1 and returns its input's width
                 raise ValueError(f"a 'ConvMix' row that names {c2} channels (scaled) behind {c1}: the module passes its input's width through, "
+                                 f'and the reference would size the following rows by {c2}')
+            elif name == 'C3CBAM' and c2 != c1:                   # the module ignores c2 and returns its input's width
+                raise ValueError(f"a 'C3CBAM' row that names {c2} channels (scaled) behind {c1}: the module passes its input's width through, "
                                  f'and the reference would size the following rows by {c2}')
             elif name == 'CSPCM' and n > 1 and c1 != c2:
                 raise NotImplementedError(f'{n} repeats of CSPCM from {c1} to {c2} channels: the reference repeats the whole block with the same '
@@ -177,7 +187,7 @@ def parse_model(d, ch):
                 args[1] = [list(range(args[1] * 2))] * len(f)
         else:
             raise NotImplementedError(f'module {name!r} is outside the SOMI hot path (SURVEY.md section 8a)')
-        if n > 1 and (name not in _CH or isinstance(f, (list, tuple))):
+        if n > 1 and (name not in _CH or isinstance(f, (list, tuple)) or name == 'C3CBAM'):
             raise NotImplementedError(f'{n} repeats of {name!r} as an nn.Sequential are not on the path (single-input (c1, c2, ...) modules only)')
         if name in _HEADS and len(f) > 5:
             raise NotImplementedError(f'at most 5 detection levels, got {len(f)}')

@@ -1249,6 +1249,110 @@ def argmax_pixel(x, mx, c, x_coff=0):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- tail attention of the CBAM C3 family (cbam_c3.hip)
+GATE_MODES = {'product': 0, 'sigmoid_sum': 1}     # SOMI_GATE_PRODUCT, SOMI_GATE_SIGMOID_SUM
+
+
+def _gate_args(t, ca, sa, c, what):
+    B, H, W, _ = t.shape
+    if tuple(ca.shape) != (B, c) or tuple(sa.shape) != (B, H, W):
+        raise RuntimeError(f'{what}: ca must be ({B}, {c}) and sa ({B}, {H}, {W}), got {tuple(ca.shape)} and {tuple(sa.shape)}')
+    return B, H * W, _ptr(_f32c(ca)), _ptr(_f32c(sa))
+
+
+def gate_combine(t, ca, sa, c, mode, t_coff=0, *, residual=None, res_coff=0, out=None, o_coff=0):
+    """out = t * ca * sa (mode 'product') or sigmoid(t * (ca + sa)) ('sigmoid_sum'), + residual when given, over the channel slices
+    [coff, coff + c) of t / residual / out; ca (B, c), sa (B, H, W).  -> out (a new (B,H,W,c) tensor when None)."""
+    B, HW, pca, psa = _gate_args(t, ca, sa, c, 'gate_combine')
+    if out is None:
+        out = torch.empty(*t.shape[:3], c, device=t.device, dtype=torch.float32)
+    res = _NO_SLICE if residual is None else _slice(_map(residual, t, 'gate_combine: residual'), res_coff)
+    check(_lib.lib().somi_gate_combine_nhwc_f32(_slice(t, t_coff), pca, psa, res, _slice(_map(out, t, 'gate_combine: out'), o_coff), B, HW, c,
+                                                GATE_MODES[mode], _stream()), 'gate_combine')
+    return out
+
+
+def gate_combine_backward_pixel(dout, t, ca, sa, c, mode, do_coff=0, t_coff=0, *, t_max=None, logit=False):
+    """The per-pixel half of gate_combine's backward -> (dsa (B,H,W): the gradient of sa, times sa * (1 - sa) with `logit`; amaxc (B,H,W)
+    int32: the first channel of every pixel's maximum of t * ca; amaxp (B, c) int32: the first pixel of every (image, channel) maximum of t,
+    found from t_max (B, c), the maxima global_pool took - None without t_max)."""
+    B, HW, pca, psa = _gate_args(t, ca, sa, c, 'gate_combine_backward_pixel')
+    dsa = torch.empty(*t.shape[:3], device=t.device, dtype=torch.float32)
+    amaxc = torch.empty(*t.shape[:3], device=t.device, dtype=torch.int32)
+    amaxp = None if t_max is None else torch.empty(B, c, device=t.device, dtype=torch.int32)
+    check(_lib.lib().somi_gate_combine_bwd_pixel_f32(_slice(_map(dout, t, 'gate_combine_backward_pixel: dout'), do_coff), _slice(t, t_coff), pca, psa,
+                                                     None if t_max is None else _ptr(_f32c(t_max)), _ptr(dsa), _ptr(amaxc), _ptr(amaxp), B, HW, c,
+                                                     GATE_MODES[mode], int(logit), _stream()), 'gate_combine_backward_pixel')
+    return dsa, amaxc, amaxp
+
+
+def gate_combine_backward_chan(dout, t, ca, sa, dstats, amaxc, c, mode, do_coff=0, t_coff=0, *, dt=None, dt_coff=0, accumulate=False):
+    """The per-element half: dstats (B,H,W,2) = the gradient of [mean_c, max_c] of t * ca from the spatial gate's backward.  -> (dt, dca): dt the
+    gradient of t through both gates and the statistics, written into slice dt_coff of `dt` (a new (B,H,W,c) tensor when None; added to it
+    with `accumulate`), dca (B, c) the gradient of the channel gate."""
+    B, HW, pca, psa = _gate_args(t, ca, sa, c, 'gate_combine_backward_chan')
+    if dt is None:
+        if accumulate:
+            raise RuntimeError('gate_combine_backward_chan: accumulate needs the tensor to add to')
+        dt = torch.empty(*t.shape[:3], c, device=t.device, dtype=torch.float32)
+    dca = torch.empty(B, c, device=t.device, dtype=torch.float32)
+    L = _lib.lib()
+    ws = torch.empty(max(L.somi_gate_combine_bwd_workspace_floats(B, HW, c), 4), device=t.device, dtype=torch.float32)
+    check(L.somi_gate_combine_bwd_chan_f32(_slice(_map(dout, t, 'gate_combine_backward_chan: dout'), do_coff), _slice(t, t_coff), pca, psa,
+                                           _ptr(_f32c(dstats)), _ptr(amaxc), _slice(_map(dt, t, 'gate_combine_backward_chan: dt'), dt_coff), _ptr(dca),
+                                           _ptr(ws), ws.numel(), B, HW, c, GATE_MODES[mode], int(accumulate), _stream()), 'gate_combine_backward_chan')
+    return dt, dca
+
+
+def spatial_attn_backward(dlogit, stats, w, k, dw, db, dw_chw=True):
+    """Step B of train_blocks.hip on its own: dlogit (B,H,W) = the gradient of the k x k gate conv's output, stats (B,H,W,2) its input, w the
+    [k][k][2] packed weight.  -> dstats (B,H,W,2); dw ((1,2,k,k) with dw_chw, else [k][k][2]) and db are accumulated."""
+    B, H, W, _ = stats.shape
+    dstats = torch.empty_like(stats)
+    ws = torch.empty(((B * H * W + 511) // 512) * (2 * k * k + 1), device=stats.device, dtype=torch.float32)
+    check(_lib.lib().somi_spatial_attn_bwd_f32(_ptr(_f32c(dlogit)), _ptr(_f32c(stats)), _ptr(w), _ptr(dstats), _ptr(dw), _ptr(db), _ptr(ws), B, H, W, k,
+                                               int(dw_chw), _stream()), 'spatial_attn_bwd')
+    return dstats
+
+
+def _dwc_ws(B, H, W, k, dev):
+    return torch.empty(max(_lib.lib().somi_dwc_gate_workspace_floats(B, H, W, k), 4), device=dev, dtype=torch.float32)
+
+
+def dwc_gate_eval(stats, params, run, k, eps):
+    """The depthwise-separable spatial gate with running statistics: stats (B,H,W,2) -> sa (B,H,W), one launch.  params: 2 k k + 11 floats,
+    run: 6 (somi_dwc_gate_eval_f32)."""
+    B, H, W, _ = stats.shape
+    sa = torch.empty(B, H, W, device=stats.device, dtype=torch.float32)
+    check(_lib.lib().somi_dwc_gate_eval_f32(_ptr(_f32c(stats)), _ptr(_f32c(params)), _ptr(_f32c(run)), _ptr(sa), B, H, W, k, float(eps), _stream()),
+          'dwc_gate_eval')
+    return sa
+
+
+def dwc_gate_train(stats, params, run, k, eps, momentum):
+    """The gate with batch statistics -> (sa, u (B,H,W,2), p (B,H,W), st (8)): what backward needs; `run` (6 floats, or None) is moved in place."""
+    B, H, W, _ = stats.shape
+    if B * H * W == 1:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {(B, 2, H, W)}')
+    dev = stats.device
+    sa, u = torch.empty(B, H, W, device=dev, dtype=torch.float32), torch.empty(B, H, W, 2, device=dev, dtype=torch.float32)
+    p, st = torch.empty(B, H, W, device=dev, dtype=torch.float32), torch.zeros(8, device=dev, dtype=torch.float32)
+    ws = _dwc_ws(B, H, W, k, dev)
+    check(_lib.lib().somi_dwc_gate_train_f32(_ptr(_f32c(stats)), _ptr(_f32c(params)), _ptr(u), _ptr(p), _ptr(st), _ptr(run), float(momentum),
+                                             float(eps), _ptr(sa), _ptr(ws), ws.numel(), B, H, W, k, _stream()), 'dwc_gate_train')
+    return sa, u, p, st
+
+
+def dwc_gate_backward(dsa, stats, u, p, st, params, k, dparams):
+    """dsa: the RAW gradient of sa (B,H,W) -> dstats (B,H,W,2); the parameter gradients are added to dparams (the layout of params)."""
+    B, H, W, _ = stats.shape
+    dstats = torch.empty_like(stats)
+    ws = _dwc_ws(B, H, W, k, stats.device)
+    check(_lib.lib().somi_dwc_gate_bwd_f32(_ptr(_f32c(dsa)), _ptr(_f32c(stats)), _ptr(_f32c(u)), _ptr(_f32c(p)), _ptr(st), _ptr(_f32c(params)),
+                                           _ptr(dstats), _ptr(_f32c(dparams)), _ptr(ws), ws.numel(), B, H, W, k, _stream()), 'dwc_gate_backward')
+    return dstats
+
+
 def _spp_k(k):
     k = [int(v) for v in k]
     return [len(k)] + (k + [0, 0, 0])[:3]
